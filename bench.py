@@ -3,6 +3,7 @@
 MAC hot path on MI355X, with the CPU paths timed beside it.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config c4|c2|c3|c5a|c5b|c5|c5s|c4s|c2s] [--mode all|shard|replicas|ipc_eig]
+                    [--full] [--dump-outputs DIR]
 
 One "step" = one Frank-Wolfe iteration (mac/optimization/frankwolfe.py:53-76 with
 problem = MAC.problem): assemble L(x) -> Fiedler pair to the reference's stop rule at tol 1e-8 ->
@@ -11,13 +12,22 @@ lists, x0, start vector) are resident in HBM before the timed region starts.
 
 Default workload (N = 1): BASELINE.json configs[3], the configuration the north star quotes its target on
 (ER N = 100 000, ~2M candidate edges, chain fixed, K = 10 %); it fits one GPU.  The timed region is a PASS of
-exactly K iterations from x0; passes are repeated until >= --min-seconds of wall time have been measured and
-the MEDIAN pass is reported (`repeats`, `pass_ms`), so the figure is reproducible and visible from outside.
+exactly K iterations from x0, after W untimed iterations from x0.  A plain run times ONE pass, so --steps is the
+number of timed steps and `ms_per_step` the time of one of them.  With --full, passes are repeated until
+>= --min-seconds (default 2) of wall time have been measured and the MEDIAN pass is reported (`repeats`, `pass_ms`).
 
-Every cold eigen-solve starts from the reference's start column (fiedler.py:27-32) multiplied by the landscape weighting of DESIGN
-section 4.2 (inside the timed region: five launches per solve); the object `cold_start` of the line holds the same pass with the
-weighting off and -- configs[1] / configs[3] -- both settings on the reference's own 20 iterates (tests/golden).  `warm_start`: the
-same pass with use_cache=True made real.
+--full also runs everything beside the headline, each on runs of its own: `warm_start`, `cold_start`, `roofline` (with the
+measured streaming peak and the two rocprofv3 --pmc child passes), `cpu_baseline` / `cpu_baseline_strong` and the same-node
+point, and the one-at-a-time comparisons of the batched and sweep configs (`sequential_value`).  Every cold eigen-solve starts
+from the reference's start column (fiedler.py:27-32) multiplied by the landscape weighting of DESIGN section 4.2 (inside the
+timed region: five launches per solve); the object `cold_start` holds the same pass with the weighting off and -- configs[1] /
+configs[3] -- both settings on the reference's own 20 iterates (tests/golden).  `warm_start`: the same pass with use_cache=True
+made real.
+
+--dump-outputs DIR (one process, --gpus 1): after the timed steps, the results of the last timed pass -- what a caller of
+machip_fw_run / machip_fw_sweep receives -- are written as DIR/<name>.npy (float64): lambda_2 (`f`), dual bound and gradient
+norm per iteration, the running upper bound and the final iterate x.  The inputs are the same from run to run, so two builds
+can be compared output for output.
 
 --gpus N > 1 (default --mode all): ONE invocation runs, in one process group and in this order,
   * the SHARD pass (headline `value`, "scaling": "strong"; the north star's split): the candidates
@@ -65,34 +75,47 @@ STEP_HEADS = ("k_pipe_vec", "k_pipe_stream", "k_pan_mul")                    # o
 # reference-equivalent CPU path at sizes where it does finish (measured in the build
 # container, 1 core): seconds per Fiedler solve of the same ER family -- the extrapolation points for configs[3]
 # NOT measured on the node this bench runs on: constants from the 8-vCPU build container, reported under a key that says so;
-# the same-node point is measured by every default run (cpu_same_node_point below)
+# the same-node point is measured by every --full run (cpu_same_node_point below)
 REF_EXTRAPOLATION = {"N=20000 (m=200k cands)": 88.0, "N=40000 (m=800k cands)": 448.0, "N=100000": "> 3000 (did not finish in 50 min)"}
 
 
 # ---------------------------------------------------------------------------------------------
 # workloads
 # ---------------------------------------------------------------------------------------------
+def gnp_edges(n, p, seed):
+    """The edges (i < j) of networkx.fast_gnp_random_graph(n, p, seed=seed) in G.edges() order, without building the graph
+    (~1 s at N = 100k instead of ~10 s).  The same walk: random.Random(seed)'s Mersenne Twister stream (replayed by NumPy's
+    MT19937, which turns two words into a double the same way), geometric skips int(log(1 - r) / log(1 - p)) over the lower
+    triangle row by row; G.edges() lists each edge under its smaller end, in the order the larger ends were drawn.
+    tests/test_host_cpu.py holds it to networkx."""
+    import math
+    import random
+    key = random.Random(seed).getstate()[1]
+    rs = np.random.RandomState()
+    rs.set_state(("MT19937", np.array(key[:624], dtype=np.uint32), key[624]))
+    lp = math.log(1.0 - p)
+    total = n * (n - 1) // 2                      # positions v (v - 1) / 2 + w of the pairs w < v
+    chunks, last = [], -1
+    while last < total:
+        r = rs.random_sample(int(1.02 * p * total) + 1024)
+        lr = np.fromiter(map(math.log, (1.0 - r).tolist()), np.float64, len(r))      # math.log, as networkx calls it
+        pos = last + np.cumsum((lr / lp).astype(np.int64) + 1)
+        chunks.append(pos)
+        last = int(pos[-1])
+    pos = np.concatenate(chunks)
+    pos = pos[pos < total]
+    v = ((1.0 + np.sqrt(8.0 * pos + 1.0)) // 2).astype(np.int64)
+    v -= v * (v - 1) // 2 > pos
+    v += (v + 1) * v // 2 <= pos
+    w = pos - v * (v - 1) // 2
+    o = np.lexsort((v, w))
+    return w[o], v[o]
+
+
 def er_workload(n, p, seed, name):
-    cache = os.path.join(tempfile.gettempdir(), f"machip_wl_{n}_{seed}_{os.getuid()}.npz")
-    if os.path.exists(cache):
-        try:
-            z = np.load(cache)
-            ci, cj = z["ci"], z["cj"]
-        except Exception:
-            ci = None
-    else:
-        ci = None
-    if ci is None:
-        import networkx as nx
-        G = nx.fast_gnp_random_graph(n, p, seed=seed)
-        e = np.array([(min(a, b), max(a, b)) for a, b in G.edges() if abs(a - b) != 1], dtype=np.int32)
-        ci, cj = e[:, 0].copy(), e[:, 1].copy()
-        try:        # generation takes ~20 s at N = 100k; the PMC / rank children of one run reuse it
-            tmp = cache + f".{os.getpid()}.tmp.npz"
-            np.savez(tmp, ci=ci, cj=cj)
-            os.replace(tmp, cache)
-        except OSError:
-            pass
+    i, j = gnp_edges(n, p, seed)
+    keep = j - i != 1                             # chain edges are the fixed ones
+    ci, cj = i[keep].astype(np.int32), j[keep].astype(np.int32)
     m = len(ci)
     k = m // 10
     x0 = np.zeros(m)
@@ -152,6 +175,24 @@ def run_pass(P, k, iters, x0, tol=1e-8):
                         support=int(st.support), gpu_ms=float(st.gpu_ms), step_ms=float(st.step_ms), steps_timed=int(st.steps_timed),
                         steps_lowp=int(st.steps_lowp), residual=float(st.residual), mode=r["modes"][it]))
     return rec
+
+
+DUMP_MAX_ENTRIES = 1 << 21          # 16 MB of float64 per array; the largest dump (configs[3]: x, 2.0 M entries) is written whole
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs: every array as d/<name>.npy in float64.  An array of more than DUMP_MAX_ENTRIES entries (the B x m
+    iterates of the c4s sweep) is replaced by a fixed sample of them: the same sorted positions, drawn from default_rng(0),
+    in every run."""
+    os.makedirs(d, exist_ok=True)
+    total = 0
+    for name, a in arrays.items():
+        a = np.asarray(a, dtype=np.float64)
+        if a.size > DUMP_MAX_ENTRIES:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, DUMP_MAX_ENTRIES, replace=False))]
+        total += a.nbytes
+        assert total <= 64 << 20, f"--dump-outputs: more than 64 MB at {name}"
+        np.save(os.path.join(d, name + ".npy"), a)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -400,10 +441,10 @@ def bench_c5_batched(args):
         run_pass(P, w["k"], args.warmup, w["x0"])
         P.set_x(w["x0"]); P.synchronize()
         Ps.append(P)
-    fs = [None, None]
+    recs = [None, None]
 
     def work(i):
-        fs[i] = [r["f"] for r in run_pass(Ps[i], ws[i]["k"], args.steps, ws[i]["x0"])]
+        recs[i] = run_pass(Ps[i], ws[i]["k"], args.steps, ws[i]["x0"])
     t0 = time.perf_counter()
     th = [threading.Thread(target=work, args=(i,)) for i in range(2)]
     for t in th:
@@ -413,11 +454,19 @@ def bench_c5_batched(args):
     for P in Ps:
         P.synchronize()
     el = time.perf_counter() - t0
-    t1 = time.perf_counter()
-    for i in range(2):
-        run_pass(Ps[i], ws[i]["k"], args.steps, ws[i]["x0"])
-        Ps[i].synchronize()
-    seq = time.perf_counter() - t1
+    if args.dump_outputs:
+        out = {}
+        for i, g in enumerate(("c5b", "c5a")):
+            out.update({f"{nm}_{g}": [r_[nm] for r_ in recs[i]] for nm in ("f", "dual", "gnorm")})
+            out[f"x_{g}"] = Ps[i].get_x()
+        dump_outputs(args.dump_outputs, out)
+    seq = None
+    if args.full:
+        t1 = time.perf_counter()
+        for i in range(2):
+            run_pass(Ps[i], ws[i]["k"], args.steps, ws[i]["x0"])
+            Ps[i].synchronize()
+        seq = 2 * args.steps / (time.perf_counter() - t1)
     print(json.dumps({"metric": "frank_wolfe_iters_per_sec", "value": 2 * args.steps / el, "unit": "iter/s", "n_gpus": 1,
                       "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * el / (2 * args.steps),
                       "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
@@ -428,7 +477,7 @@ def bench_c5_batched(args):
                                                 "measured SLOWER than the fp64 default on this hardware (DESIGN 4.2, docs/log_r1_r4.md 4.2d)"),
                                  "precision_note": "default --precision 0 (fp64) is the faster mode; --precision 1 is the fp32 + fp64-refinement arithmetic configs[4] names",
                                  "fw_iters_each": args.steps, "parallelism": "replicas: one stream + host thread per graph"},
-                      "sequential_value": 2 * args.steps / seq, "lambda2_last": [fs[0][-1], fs[1][-1]]}))
+                      **({} if seq is None else {"sequential_value": seq}), "lambda2_last": [recs[0][-1]["f"], recs[1][-1]["f"]]}))
     for P in Ps:
         P.close()
 
@@ -476,11 +525,16 @@ def bench_c5_sweep(args):
             break
     el = sorted(passes)[(len(passes) - 1) // 2]
     its = sum(int(r["iters"].sum()) for r in res)
-    t1 = time.perf_counter()
-    for i in range(2):                    # the same budgets one after the other, one at a time (what a loop over MAC.solve does)
-        for j, k in enumerate(ks[i]):
-            run_pass(Ps[i], k, args.steps, X0[i][j])
-    seq = time.perf_counter() - t1
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {f"{nm}_{g}": res[i][key] for i, g in enumerate(("c5b", "c5a"))
+                                         for nm, key in (("f", "f_traj"), ("upper", "upper"), ("iters", "iters"), ("x", "x"))})
+    seq = None
+    if args.full:
+        t1 = time.perf_counter()
+        for i in range(2):                    # the same budgets one after the other, one at a time (what a loop over MAC.solve does)
+            for j, k in enumerate(ks[i]):
+                run_pass(Ps[i], k, args.steps, X0[i][j])
+        seq = its / (time.perf_counter() - t1)
     print(json.dumps({"metric": "frank_wolfe_iters_per_sec", "value": its / el, "unit": "iter/s", "n_gpus": 1,
                       "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * el / its, "higher_is_better": True,
                       "scaling": "weak", "vs_baseline": None, "dtype": "f64" if args.precision == 0 else "f32 iterate + f64 Rayleigh/residual refinement",
@@ -490,7 +544,7 @@ def bench_c5_sweep(args):
                                  "budgets_per_graph": len(pcts), "fw_iters_each": args.steps,
                                  "parallelism": "evaluation lanes: up to 12 budgets per graph at a time, one host thread per lane"},
                       "repeats": len(passes), "pass_ms": [round(1e3 * p, 3) for p in passes], "iterations_per_pass": its,
-                      "sequential_value": its / seq,
+                      **({} if seq is None else {"sequential_value": seq}),
                       "lambda2_last": [[float(r["f_traj"][j, -1]) for j in (0, len(pcts) - 1)] for r in res]}))
     for P in Ps:
         P.close()
@@ -528,25 +582,29 @@ def bench_er_sweep(args, base):
             ts.append(time.perf_counter() - t0)
         its = int(res["iters"].sum())
         scan[lanes] = dict(value=its / sorted(ts)[1], pass_ms=[round(1e3 * t, 3) for t in ts], lambda2_last=[float(res["f_traj"][b, -1]) for b in range(B)])
-    for b in range(B):
-        run_pass(P, ks[b], 1, X0[b])
-    t1 = time.perf_counter()
-    seq_f = []
-    for b in range(B):
-        rec = run_pass(P, ks[b], args.steps, X0[b])
-        seq_f.append(rec[-1]["f"])
-    P.synchronize()
-    seq = B * args.steps / (time.perf_counter() - t1)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"f": res["f_traj"], "upper": res["upper"], "iters": res["iters"], "x": res["x"]})
     best = max(scan, key=lambda l: scan[l]["value"])
-    print(json.dumps({"metric": "frank_wolfe_iters_per_sec", "value": scan[best]["value"], "unit": "iter/s", "n_gpus": 1, "steps": args.steps,
-                      "warmup": args.warmup, "ms_per_step": 1e3 / scan[best]["value"], "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-                      "dtype": "f64", "data": "synthetic",
-                      "config": {"workload": w["name"] + f" as the reference's budget sweep: {B} budgets K_b = K (0.5 + b/{B - 1}) x {args.steps} Frank-Wolfe iterations, "
-                                             "concurrently on one GPU (machip_fw_sweep)", "N": n, "m_candidates": m, "K": ks, "lanes": best,
-                                 "parallelism": f"{best} evaluation lanes, one host thread and one hardware queue each"},
-                      "lane_scan": {str(l): v for l, v in scan.items()}, "sequential_value": seq,
-                      "aggregate_vs_one_at_a_time": scan[best]["value"] / seq,
-                      "lambda2_last_equal_to_sequential": [scan[best]["lambda2_last"][b] == seq_f[b] for b in range(B)]}))
+    out = {"metric": "frank_wolfe_iters_per_sec", "value": scan[best]["value"], "unit": "iter/s", "n_gpus": 1, "steps": args.steps,
+           "warmup": args.warmup, "ms_per_step": 1e3 / scan[best]["value"], "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+           "dtype": "f64", "data": "synthetic",
+           "config": {"workload": w["name"] + f" as the reference's budget sweep: {B} budgets K_b = K (0.5 + b/{B - 1}) x {args.steps} Frank-Wolfe iterations, "
+                                  "concurrently on one GPU (machip_fw_sweep)", "N": n, "m_candidates": m, "K": ks, "lanes": best,
+                      "parallelism": f"{best} evaluation lanes, one host thread and one hardware queue each"},
+           "lane_scan": {str(l): v for l, v in scan.items()}}
+    if args.full:
+        for b in range(B):
+            run_pass(P, ks[b], 1, X0[b])
+        t1 = time.perf_counter()
+        seq_f = []
+        for b in range(B):
+            rec = run_pass(P, ks[b], args.steps, X0[b])
+            seq_f.append(rec[-1]["f"])
+        P.synchronize()
+        seq = B * args.steps / (time.perf_counter() - t1)
+        out.update({"sequential_value": seq, "aggregate_vs_one_at_a_time": scan[best]["value"] / seq,
+                    "lambda2_last_equal_to_sequential": [scan[best]["lambda2_last"][b] == seq_f[b] for b in range(B)]})
+    print(json.dumps(out))
     P.close()
 
 
@@ -928,7 +986,11 @@ def main():
     ap.add_argument("--mode", default="all", choices=["all", "shard", "replicas", "ipc_eig"],
                     help="N > 1: all = candidate shard (headline, strong) + replicas (weak) + row-partitioned eigen-solve, one JSON line; or one leg only")
     ap.add_argument("--precision", type=int, default=0, help="0 = f64 throughout; 1 = f32 Krylov iterate + f64 Rayleigh/residual refinement (configs[4])")
-    ap.add_argument("--min-seconds", type=float, default=2.0, help="repeat the K-iteration pass until this much wall time is measured")
+    ap.add_argument("--full", action="store_true", help="also measure everything beside the headline (warm / cold start, roofline with the PMC passes, "
+                    "CPU baselines, one-at-a-time comparisons) and repeat the timed pass for --min-seconds; a plain run times one pass of --steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the results of the last timed pass as DIR/<name>.npy (float64; --gpus 1)")
+    ap.add_argument("--min-seconds", type=float, default=None, help="repeat the K-iteration pass until this much wall time is measured "
+                    "(default: 2 with --full, else one pass)")
     ap.add_argument("--max-repeats", type=int, default=50)
     ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline legs")
     ap.add_argument("--no-roofline", action="store_true")
@@ -939,6 +1001,10 @@ def main():
                     "one all-gather and the IPC buffer exchange on a tiny problem, no workload; prints one JSON line")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.min_seconds is None:
+        args.min_seconds = 2.0 if args.full else 0.0
+    if args.dump_outputs and args.gpus > 1:
+        raise SystemExit("--dump-outputs: one process only (--gpus 1)")
 
     if args.gpus > 1 and "RANK" not in os.environ:
         return self_launch(args)
@@ -1046,10 +1112,12 @@ def main():
             break
     order = sorted(range(len(passes)), key=lambda i: passes[i][0])
     el, rec = passes[order[(len(order) - 1) // 2]]       # the median pass (lower median)
+    if args.dump_outputs:                 # the last timed pass, as machip_fw_run handed it back, and the iterate it left resident
+        dump_outputs(args.dump_outputs, {"f": r["f"], "dual": r["dual"], "gnorm": r["gnorm"], "upper": [r["upper"]], "x": P.get_x()})
     # ---- the reference's own micro-benchmark is cache on / off (tests/benchmarks/test_cache_performance.py:10-48): the same
     #      pass with use_cache=True semantics (every eigen-solve but the first starts from the previous Fiedler vector) ----
     warm = None
-    if world == 1 and not args.no_warm and not args.pmc_child:
+    if world == 1 and args.full and not args.no_warm and not args.pmc_child:
         wp = []
         for _ in range(3):
             P.set_x(w["x0"])
@@ -1069,7 +1137,7 @@ def main():
     #      (tests/golden): free-running trajectories part at the first near-tie of the top-K selection (configs[1]: from iterate 5 on,
     #      the reference's own run included), so only the teacher-forced pair compares the same matrices ----
     cold = None
-    if world == 1 and not args.no_warm and not args.pmc_child:
+    if world == 1 and args.full and not args.no_warm and not args.pmc_child:
         def _passes(nrep=3):
             cp = []
             for _ in range(nrep):
@@ -1182,7 +1250,7 @@ def main():
             out["predicted_vs_1gpu"] = {"factor": pred, "why": why}
     # ---- roofline of the dominant kernel: in-solve duration from the hipEvents that bracket the Krylov chunks
     #      on the handle's stream (machip_solve_stats.step_ms / steps_timed), summed over EVERY timed pass ----
-    if not args.no_roofline and rank == 0:
+    if args.full and not args.no_roofline and rank == 0:
         top, mode_list = roofline_by_mode(passes, n, args.precision)
         if top is not None and top[0] in (1, 2, 3):
             # the fused step in whichever forms ran (gather on sparse iterates, panel on dense ones): ONE unit, as in rounds 1-4
@@ -1242,7 +1310,7 @@ def main():
                                                   "/ step time / (128 channels x 2.1 GHz): the bound the one-kernel step runs into; the "
                                                   "panel form serves the gathers from LDS and issues ~6x fewer",
                                "note": note}
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu:
         small = n <= 20000 and cfg != "c2"
         cb = cpu_baseline_bounded(cfg, "tracemin", budget_s=12.0, hard_s=20.0 if small else 45.0)
         ft = cb.pop("f_traj")

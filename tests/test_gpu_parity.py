@@ -2268,13 +2268,13 @@ def test_bench_refuses_more_ranks_than_gpus():
 
 
 def test_bench_line_contract_on_a_small_config():
-    """One JSON line with the contract's fields, `roofline` from the in-solve step timer and both CPU baselines."""
+    """One JSON line with the contract's fields, `roofline` from the in-solve step timer and both CPU baselines (--full)."""
     import json
     env = dict(os.environ)
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT", "MASTER_ADDR"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "c5a", "--steps", "6", "--warmup", "1", "--min-seconds", "0.2",
-                        "--no-pmc"], env=env, capture_output=True, text=True, timeout=600)
+                        "--no-pmc", "--full"], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -2290,6 +2290,32 @@ def test_bench_line_contract_on_a_small_config():
         assert d["cpu_parity_lambda2_rel"] < 1e-8
     else:       # (a host so slow that the bounded CPU leg did not finish one iteration: the line must say so)
         assert d["cpu_baseline"].get("upper_bound") is True
+
+
+def test_bench_plain_run_times_exactly_its_steps_and_dumps_what_they_computed(tmp_path):
+    """A plain bench run (no --full) times ONE pass of --steps iterations and measures nothing else; --dump-outputs writes that
+    pass's results as float64 .npy files, and a second run with the same arguments writes the same bits."""
+    import json
+    env = dict(os.environ)
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT", "MASTER_ADDR"):
+        env.pop(k, None)
+    lines = []
+    for d in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--config", "c5a", "--steps", "4", "--warmup", "1",
+                            "--dump-outputs", str(tmp_path / d)], env=env, capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines.append([l for l in r.stdout.splitlines() if l.startswith("{")])
+    assert len(lines[0]) == 1
+    d = json.loads(lines[0][0])
+    assert d["steps"] == 4 and d["repeats"] == 1 and abs(d["ms_per_step"] - d["pass_ms"][0] / 4) < 1e-2
+    for k in ("roofline", "cpu_baseline", "cpu_baseline_strong", "warm_start", "cold_start"):
+        assert k not in d, k
+    out = {nm: np.load(tmp_path / "a" / (nm + ".npy")) for nm in ("f", "dual", "gnorm", "upper", "x")}
+    assert all(a.dtype == np.float64 for a in out.values()) and sum(a.nbytes for a in out.values()) <= 64 << 20
+    assert out["f"].shape == (4,) and [out["f"][0], out["f"][-1]] == d["lambda2_first_last"]
+    assert out["x"].shape == (d["config"]["m_candidates"],) and out["upper"][0] == out["dual"].min()
+    for nm, a in out.items():
+        assert np.array_equal(a, np.load(tmp_path / "b" / (nm + ".npy"))), nm
 
 
 def test_graft_entry_smoke():

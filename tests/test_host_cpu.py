@@ -180,6 +180,27 @@ def test_bench_refuses_to_launch_ranks_without_devices():
     assert r.returncode != 0 and "refusing" in (r.stderr + r.stdout) and '"metric"' not in r.stdout
 
 
+@pytest.mark.parametrize("n,p,seed", [(3000, 0.01, 0), (6000, 0.002, 1), (300, 0.05, 3), (40, 0.6, 7)])
+def test_bench_er_edges_are_networkx_fast_gnp_random_graph(n, p, seed):
+    """bench.gnp_edges replays nx.fast_gnp_random_graph(n, p, seed) without building the graph: the same edges in G.edges() order."""
+    import networkx as nx
+    import bench
+    i, j = bench.gnp_edges(n, p, seed)
+    e = np.array([(min(a, b), max(a, b)) for a, b in nx.fast_gnp_random_graph(n, p, seed=seed).edges()], dtype=np.int64).reshape(-1, 2)
+    assert np.array_equal(i, e[:, 0]) and np.array_equal(j, e[:, 1])
+
+
+def test_bench_dump_outputs_writes_float64_within_the_size_cap(tmp_path):
+    """bench.py --dump-outputs: float64 .npy files; an array above DUMP_MAX_ENTRIES becomes the same fixed sample every time."""
+    import bench
+    big = np.arange(bench.DUMP_MAX_ENTRIES + 5, dtype=np.float64)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"f": np.array([1.5, 2.5]), "iters": np.array([3, 4], dtype=np.int32), "x": big})
+    f, it, x = (np.load(tmp_path / "a" / (nm + ".npy")) for nm in ("f", "iters", "x"))
+    assert f.dtype == it.dtype == x.dtype == np.float64 and list(it) == [3.0, 4.0]
+    assert x.size == bench.DUMP_MAX_ENTRIES and np.all(np.diff(x) > 0) and np.array_equal(x, np.load(tmp_path / "b" / "x.npy"))
+
+
 def test_panel_plan_covers_every_row_and_column_within_the_kernel_limits():
     """Shape arithmetic of the column-panel Lanczos step (solver.h plan_panel, exported as machip_panel_plan; host only):
     the panels cover every column, the row blocks every row, a panel fits the LDS next to the row block's image

@@ -44,30 +44,30 @@ f)  # how many groups of chunk loads leave before the panel is in LDS (PAN_U_AHE
     ;;
 g)  # full GPU test suite + default bench line
     timeout 2400 python -m pytest tests -x -q -m gpu > $out/tests.txt 2>&1; tail -15 $out/tests.txt
-    timeout 900 python bench.py > $out/bench_c4.json 2> $out/bench_c4.err; cut -c1-1500 $out/bench_c4.json
+    timeout 900 python bench.py --full > $out/bench_c4.json 2> $out/bench_c4.err; cut -c1-1500 $out/bench_c4.json
     ;;
 h)  # advisor fixes + landscape gate: full GPU suite, X-block probe, pose-graph benches, default bench
     timeout 2400 python -m pytest tests -x -q -m gpu > $out/tests.txt 2>&1; tail -8 $out/tests.txt
     timeout 300 python tools/xblock_probe.py > $out/xblock.txt 2>&1; cat $out/xblock.txt
-    for c in c5b c5a c3 c2; do timeout 600 python bench.py --config $c --no-cpu > $out/bench_$c.json 2> $out/bench_$c.err; python -c "import json,sys; d=json.loads(open('$out/bench_$c.json').read().strip().splitlines()[-1]); print('$c', d['value'], d.get('lanczos_steps_per_iter'), d['roofline']['frac'] if d.get('roofline') else None)"; done
-    timeout 900 python bench.py > $out/bench_c4.json 2> $out/bench_c4.err; python -c "import json,sys; d=json.loads(open('$out/bench_c4.json').read().strip().splitlines()[-1]); print('c4', d['value'], d.get('lanczos_steps_per_iter'), d['roofline']['frac'], d['roofline']['traffic'])"
+    for c in c5b c5a c3 c2; do timeout 600 python bench.py --config $c --no-cpu --full > $out/bench_$c.json 2> $out/bench_$c.err; python -c "import json,sys; d=json.loads(open('$out/bench_$c.json').read().strip().splitlines()[-1]); print('$c', d['value'], d.get('lanczos_steps_per_iter'), d['roofline']['frac'] if d.get('roofline') else None)"; done
+    timeout 900 python bench.py --full > $out/bench_c4.json 2> $out/bench_c4.err; python -c "import json,sys; d=json.loads(open('$out/bench_c4.json').read().strip().splitlines()[-1]); print('c4', d['value'], d.get('lanczos_steps_per_iter'), d['roofline']['frac'], d['roofline']['traffic'])"
     ;;
 j)  # mixed panel mode (late fp32 tiles) + everything since h
     timeout 900 python -m pytest tests/test_gpu_parity.py -x -q -k "teacher_forced_config4 or x_block or landscape or mixed or precision" > $out/tests_a.txt 2>&1; tail -6 $out/tests_a.txt
-    for p in 0 1; do timeout 600 python bench.py --config c4 --no-cpu --no-warm --no-pmc --no-same-node --precision $p > $out/bench_c4_p$p.json 2> $out/bench_c4_p$p.err; python -c "import json,sys; d=json.loads(open('$out/bench_c4_p$p.json').read().strip().splitlines()[-1]); print('c4 precision $p', d['value'], d.get('lanczos_steps_per_iter'), d['roofline']['frac'], d['roofline']['solver_modes'])"; done
+    for p in 0 1; do timeout 600 python bench.py --config c4 --no-cpu --no-warm --no-pmc --no-same-node --precision $p --full > $out/bench_c4_p$p.json 2> $out/bench_c4_p$p.err; python -c "import json,sys; d=json.loads(open('$out/bench_c4_p$p.json').read().strip().splitlines()[-1]); print('c4 precision $p', d['value'], d.get('lanczos_steps_per_iter'), d['roofline']['frac'], d['roofline']['solver_modes'])"; done
     timeout 2400 python -m pytest tests -x -q -m gpu > $out/tests.txt 2>&1; tail -6 $out/tests.txt
     ;;
 final)  # measurement round: bench lines of every config, rocprofv3 summaries (c4, c2, c3, c5b), the mixed leg, two ranks on one GPU
     R=${2:-r6}
-    timeout 900 python bench.py > $out/${R}_bench_c4.json 2> $out/bench_c4.err
-    for c in c2 c3 c5a c5b; do timeout 600 python bench.py --config $c > $out/${R}_bench_$c.json 2> $out/bench_$c.err; done
-    timeout 300 python bench.py --config c5 > $out/${R}_bench_c5.json 2>> $out/bench_c5.err
-    timeout 300 python bench.py --config c5 --precision 1 > $out/${R}_bench_c5_mixed.json 2>> $out/bench_c5.err
-    timeout 600 python bench.py --config c4 --precision 1 --no-cpu --no-same-node > $out/${R}_bench_c4_mixed.json 2>> $out/bench_c4m.err
-    timeout 300 python bench.py --config c5s > $out/${R}_bench_c5s.json 2>> $out/bench_c5.err
-    timeout 600 python bench.py --config c4s > $out/${R}_bench_c4s.json 2>> $out/bench_c4s.err
-    timeout 600 python bench.py --config c2s > $out/${R}_bench_c2s.json 2>> $out/bench_c4s.err
-    MACHIP_SHARE_GPU=1 timeout 900 python bench.py --gpus 2 --steps 20 --warmup 2 > $out/${R}_bench_c4_2ranks_one_gpu.json 2> $out/bench_2r.err
+    timeout 900 python bench.py --full > $out/${R}_bench_c4.json 2> $out/bench_c4.err
+    for c in c2 c3 c5a c5b; do timeout 600 python bench.py --config $c --full > $out/${R}_bench_$c.json 2> $out/bench_$c.err; done
+    timeout 300 python bench.py --config c5 --full > $out/${R}_bench_c5.json 2>> $out/bench_c5.err
+    timeout 300 python bench.py --config c5 --precision 1 --full > $out/${R}_bench_c5_mixed.json 2>> $out/bench_c5.err
+    timeout 600 python bench.py --config c4 --precision 1 --no-cpu --no-same-node --full > $out/${R}_bench_c4_mixed.json 2>> $out/bench_c4m.err
+    timeout 300 python bench.py --config c5s --full > $out/${R}_bench_c5s.json 2>> $out/bench_c5.err
+    timeout 600 python bench.py --config c4s --full > $out/${R}_bench_c4s.json 2>> $out/bench_c4s.err
+    timeout 600 python bench.py --config c2s --full > $out/${R}_bench_c2s.json 2>> $out/bench_c4s.err
+    MACHIP_SHARE_GPU=1 timeout 900 python bench.py --gpus 2 --steps 20 --warmup 2 --full > $out/${R}_bench_c4_2ranks_one_gpu.json 2> $out/bench_2r.err
     for c in c4 c2 c3 c5b; do bash tools/profile_round.sh ${R}_$c --config $c --warmup 0 > $out/prof_$c.log 2>&1; done
     for t in ${R}_c4 ${R}_c2 ${R}_c3 ${R}_c5b; do python tools/summarize_profile.py $t > $out/summarize_$t.log 2>&1; f=$(find gpurun_out/$t/trace -name "t_kernel_stats.csv" | head -1); cp "$f" $out/${t}_kernel_stats.csv; cp profiles/${t}_summary.md profiles/${t}_summary.json $out/; rm -rf gpurun_out/$t; done
     for f in $out/${R}_bench_*.json; do python - $f <<'PY'
