@@ -8,9 +8,15 @@ the reference keeps its import lines --
     from mac.optimization.frankwolfe import frank_wolfe
 
 -- and runs the MI355X implementation (``mac_amd``): this package holds no code of its own, it registers the ``mac_amd``
-modules under the reference's module names.  The reference's baselines outside the hot path (``mac.solvers.greedy_esp``,
-``greedy_eig``, ``mac.utils.cholesky``: SURVEY section 8, out of scope) are not provided: importing them raises ImportError, as
-it does in the reference without its optional SuiteSparse dependency.
+modules under the reference's module names.
+
+GreedyESP is provided as ``from mac.solvers import GreedyESP`` (``mac_amd/solvers/esp.py``, on the GPU).  The reference's
+module path ``mac.solvers.greedy_esp`` is not: ``mac.solvers`` is the ``mac_amd.solvers`` package object, so a module of that
+name there would answer the reference's import line, which stays an ImportError -- a script written against the reference
+changes that one line (examples/g2o_experiment.py: ``from mac.solvers.greedy_esp import GreedyESP`` ->
+``from mac.solvers import GreedyESP``).  The other baselines (``greedy_eig``, ``mac.utils.cholesky``: SURVEY section 8, out of
+scope) are not provided: importing them raises ImportError, as it does in the reference without its optional SuiteSparse
+dependency.
 """
 import importlib
 import sys

@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define MACHIP_ABI_VERSION 6   /* 6: machip_solve_stats.drift, machip_panel_plan fills 12 entries; 5: per-handle option table (machip_set_option), machip_comm_drop_ipc; 4: inter-process communicator */
+#define MACHIP_ABI_VERSION 7   /* 7: GreedyESP handle (machip_esp_*); 6: machip_solve_stats.drift, machip_panel_plan fills 12 entries; 5: per-handle option table (machip_set_option), machip_comm_drop_ipc; 4: inter-process communicator */
 
 typedef enum machip_status {
     MACHIP_OK = 0,
@@ -351,6 +351,27 @@ int machip_host_tridiag_smallest(const double* a, const double* b, int J, double
  * the estimate there.  The reference's counterpart is the per-iteration test of nx:246. */
 int machip_host_follow_records(const double* tri3, int J, int n, double e_target, double tiny_l, int jcap, int* points, int cap,
                                int* npoints, int* jeff, double* est);
+
+/* GreedyESP (mac/solvers/greedy_esp.py of the reference: the greedy k-edge selection by weighted effective resistance,
+ * Khosoussi et al.; mac_amd/csrc/esp.h).  Node 0 pinned, L_red = the fixed graph's reduced Laplacian, Sigma = (L_red + beta I)^-1
+ * kept dense on the device.  Every step selects the unselected candidate of largest w_e r_e (r_e = a_e^T Sigma a_e; ties: lowest
+ * index, exact fp64 equality) and adds it by a rank-1 update.  beta: 0 when the fixed graph is connected; otherwise
+ * MACHIP_DISCONNECTED when a node other than 0 has no fixed edge, else 1e-4.  Limits: n <= 32768 when the fixed edges are
+ * exactly the chain (i, i+1) (closed-form Sigma), n <= 16384 otherwise (dense Gauss-Jordan inverse); beyond them MACHIP_BAD_ARG. */
+typedef struct machip_esp machip_esp;
+#define MACHIP_ESP_DENSE_INVERSE 1   /* flags: build Sigma by the dense inverse even for a chain (cross-checks) */
+/* fold: pending rank-1 updates folded into Sigma every `fold` steps (1..256; 0 = 64).  Builds Sigma0. */
+int machip_esp_create(int device, int64_t n, int64_t n_fixed, const int32_t* fi, const int32_t* fj, const double* fw,
+                      int64_t m, const int32_t* ci, const int32_t* cj, const double* cw, int fold, int flags, machip_esp** out);
+void machip_esp_destroy(machip_esp* h);
+/* One greedy run from Sigma0 up to K = ks[nb-1] selections (ks positive, non-decreasing, K <= m): order_out[K] = candidate
+ * indices in selection order, gain_out[K] = the score s* of each pick (sum log(1 + gain) = logdet growth), t_ms_out[nb] = device
+ * time from the call's start until budget ks[i] was reached.  Any output may be NULL. */
+int machip_esp_select(machip_esp* h, int nb, const int64_t* ks, int32_t* order_out, double* gain_out, double* t_ms_out);
+/* w_e r_e of every candidate (m doubles) in the current graph: F plus the last machip_esp_select's selections. */
+int machip_esp_weighted_resistances(machip_esp* h, double* r_out);
+/* info4 = {form (0 chain, 1 dense inverse), leading dimension of Sigma, fold, updates pending since the last fold}; beta. */
+int machip_esp_info(machip_esp* h, int32_t* info4, double* beta);
 
 #ifdef __cplusplus
 }

@@ -100,6 +100,12 @@ SIGNATURES = {
                                              C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_double)]),
     "machip_release_cache": (None, []),
     "machip_panel_plan": (C.c_int, [C.c_int64, C.c_int64, C.c_int, C.POINTER(C.c_int)]),
+    "machip_esp_create": (C.c_int, [C.c_int, C.c_int64, C.c_int64, _i32p, _i32p, _f64p, C.c_int64, _i32p, _i32p, _f64p,
+                                    C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+    "machip_esp_destroy": (None, [C.c_void_p]),
+    "machip_esp_select": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int64), _i32p, _f64p, _f64p]),
+    "machip_esp_weighted_resistances": (C.c_int, [C.c_void_p, _f64p]),
+    "machip_esp_info": (C.c_int, [C.c_void_p, _i32p, C.POINTER(C.c_double)]),
 }
 
 
@@ -446,6 +452,62 @@ class Problem:
 
     def synchronize(self):
         check(self._lib.machip_synchronize(self._h))
+
+
+ESP_DENSE_INVERSE = 1      # MACHIP_ESP_DENSE_INVERSE
+
+
+class Esp:
+    """Owns one ``machip_esp`` handle: GreedyESP's (L_red + beta I)^-1 resident on one GPU (mac_amd/csrc/esp.h)."""
+
+    def __init__(self, n, fi, fj, fw, ci, cj, cw, fold=64, dense_inverse=False, device=0):
+        lib = load()
+        require_device()
+        self.n = int(n)
+        fi, fj, fw = i32(fi), i32(fj), f64(fw)
+        ci, cj, cw = i32(ci), i32(cj), f64(cw)
+        self.m = int(len(cw))
+        h = C.c_void_p()
+        check(lib.machip_esp_create(int(device), self.n, len(fw), p_i32(fi), p_i32(fj), p_f64(fw), self.m,
+                                    p_i32(ci), p_i32(cj), p_f64(cw), int(fold), ESP_DENSE_INVERSE if dense_inverse else 0,
+                                    C.byref(h)))
+        self._h = h
+        self._lib = lib
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.machip_esp_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def select(self, ks):
+        """One greedy run up to ks[-1] picks: (order int32[K], gain float64[K], t_ms float64[len(ks)])."""
+        ks = np.ascontiguousarray(ks, dtype=np.int64)
+        K = int(ks[-1]) if len(ks) else 0
+        order = np.empty(max(K, 1), dtype=np.int32)
+        gain = np.empty(max(K, 1))
+        t = np.empty(max(len(ks), 1))
+        check(self._lib.machip_esp_select(self._h, len(ks), ks.ctypes.data_as(C.POINTER(C.c_int64)), p_i32(order),
+                                          p_f64(gain), p_f64(t)))
+        return order[:K], gain[:K], t[:len(ks)]
+
+    def weighted_resistances(self):
+        """w_e r_e of every candidate in F plus the last run's selections."""
+        r = np.empty(max(self.m, 1))
+        check(self._lib.machip_esp_weighted_resistances(self._h, p_f64(r)))
+        return r[:self.m]
+
+    def info(self):
+        """dict(form = "chain" | "dense", ld, fold, pending, beta)."""
+        a = np.zeros(4, dtype=np.int32)
+        b = C.c_double()
+        check(self._lib.machip_esp_info(self._h, p_i32(a), C.byref(b)))
+        return dict(form="chain" if a[0] == 0 else "dense", ld=int(a[1]), fold=int(a[2]), pending=int(a[3]), beta=b.value)
 
 
 class _stdout_to_stderr:

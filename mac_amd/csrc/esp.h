@@ -1,0 +1,257 @@
+// mac_amd/csrc/esp.h -- GreedyESP (Khosoussi et al., "Tree-connectivity", arXiv:1604.01116, Algorithm 1) on the device.
+//
+// The greedy that maximises the weighted number of spanning trees: with node 0 pinned, L_red the fixed graph's reduced
+// Laplacian (n' = n - 1) and  Sigma = (L_red + beta I)^-1,  every candidate e = (u, v, w) scores  s_e = w a_e^T Sigma a_e  (its
+// weighted effective resistance; a_e = e_{u-1} - e_{v-1}, node-0 terms dropped).  Each step takes the argmax e* (ties: lowest
+// index), then adds it to the graph by Sherman-Morrison:
+//     z = Sigma a_{e*},   c = w* / (1 + s*),   Sigma <- Sigma - c z z^T,   s_e <- s_e - w_e c (z_u - z_v)^2.
+// Sigma lives dense in HBM (fp64, leading dimension n' rounded up to 64).  The rank-1 updates are not applied one by one
+// (16 n'^2 bytes each: 1.6 GB at n' = 10^4): the last j <= B pending z's stay in Zb (ld x B, with their c's) and the z of the
+// next step is  Sigma[u,:] - Sigma[v,:] - Zb diag(c) (Zb[u,:] - Zb[v,:])^T;  every B steps  Sigma <- Sigma - Zb diag(c) Zb^T  on
+// the f64 matrix cores ("fold").  Per step three launches: k_esp_z (z into Zb, order / gain), k_esp_update (all m scores +
+// per-workgroup (max, lowest index) partials), k_esp_argmax (one workgroup); no host round trip until the last budget.
+//
+// Sigma0, the inverse of the fixed graph:
+//   * chain form: F is exactly the path (i, i+1), i = 0..n-2 (parallel links summed) -> Sigma0_ij = R[min(i, j)] with R the
+//     prefix sums of 1 / w_link (the resistance from node 0): one fill kernel;
+//   * general form: the dense L_red + beta I inverted by the blocked Gauss-Jordan elimination of woodbury.h (k_gj_step, ld / 32
+//     launches, ping-pong between the handle's two ld x ld buffers -- the second one is the working copy afterwards).
+// beta (mac/solvers/greedy_esp.py of the reference: Cholesky with beta = 0, else beta = 1e-4 unless a reduced row is all zero)
+// is decided on the host by a union-find over F: connected -> 0; some node other than 0 without a fixed edge -> error; else 1e-4.
+#pragma once
+#include <climits>
+#include <vector>
+
+#include "woodbury.h"
+
+namespace machip {
+
+constexpr int kEspChainMaxN = 32768;   // chain form: 2 x 8.6 GB of Sigma at the limit
+constexpr int kEspDenseMaxN = 16384;   // general form: 512 Gauss-Jordan launches over 2 x 2.1 GB (k_gj_step indexes with int: ld^2 < 2^31)
+constexpr int kEspMaxFold = 256;
+constexpr int kEspDefaultFold = 64;
+constexpr int kEspGrid = 256;          // workgroups of the score / update pass (= partials of the argmax)
+constexpr int kEspGjLookMin = 1024;    // look-ahead pivot blocks from this many rows on (solver.h: option gj_look_min)
+
+struct EspBest {
+    double val;
+    int idx;
+    int pad;
+};
+
+struct EspView {
+    int np, ld, m;
+    const int *cu, *cv;     // reduced endpoints (node - 1; -1 = node 0)
+    const double* cw;
+    double* s;              // current scores w_e r_e
+    int* sel;               // 1 = selected in this run
+    double *Zb, *cb;        // pending columns of the low-rank block (ld x fold, column b at Zb + b ld) and their c's
+    double* pv;             // per-workgroup partials of the argmax
+    int* pi;
+    EspBest* best;
+    int* order;
+    double* gain;
+    int* bad;
+};
+
+// (v2, i2) beats (v, i): larger value, then lower index.  NaN never wins.
+__device__ __forceinline__ void esp_better(double& v, int& i, double v2, int i2) {
+    if (v2 > v || (v2 == v && i2 < i)) { v = v2; i = i2; }
+}
+// Workgroup (256 threads) argmax: every thread gets the winner.  The winner of a total order does not depend on the
+// reduction order -- deterministic.
+__device__ __forceinline__ void esp_block_argmax(double& v, int& i, double* sv, int* si) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const double v2 = __shfl_xor(v, o, kWave);
+        const int i2 = __shfl_xor(i, o, kWave);
+        esp_better(v, i, v2, i2);
+    }
+    const int w = threadIdx.x >> 6;
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) { sv[w] = v; si[w] = i; }
+    __syncthreads();
+    v = sv[0]; i = si[0];
+#pragma unroll
+    for (int q = 1; q < kBlock / kWave; ++q) esp_better(v, i, sv[q], si[q]);
+}
+
+// ---- Sigma0, chain form: Sigma_ij = R[min(i, j)] inside n' x n', identity beyond.  grid = (ceil(ld / 256), ld) ----
+__global__ __launch_bounds__(kBlock) void k_esp_chain_fill(double* __restrict__ S, const double* __restrict__ R, int np, int ld) {
+    const int i = blockIdx.y, j = blockIdx.x * kBlock + threadIdx.x;
+    if (j >= ld) return;
+    S[(size_t)i * ld + j] = (i < np && j < np) ? R[min(i, j)] : (i == j ? 1.0 : 0.0);
+}
+
+// ---- Sigma0, general form: the non-zeros of L_red + beta I (identity beyond n') into a zeroed ld x ld buffer ----
+__global__ __launch_bounds__(kBlock) void k_esp_scatter(double* __restrict__ S, const int64_t* __restrict__ pos,
+                                                        const double* __restrict__ val, int cnt) {
+    for (int e = blockIdx.x * kBlock + threadIdx.x; e < cnt; e += gridDim.x * kBlock) S[pos[e]] = val[e];
+}
+
+// s_e = w (S_uu + S_vv - 2 S_uv), node-0 terms 0; the off-diagonal entry is read from the upper triangle (a pair and its
+// reverse score the same bits).
+__device__ __forceinline__ double esp_score(const double* __restrict__ S, int ld, int u, int v, double w) {
+    const double uu = u >= 0 ? S[(size_t)u * ld + u] : 0.0;
+    const double vv = v >= 0 ? S[(size_t)v * ld + v] : 0.0;
+    const double uv = (u >= 0 && v >= 0) ? S[(size_t)min(u, v) * ld + max(u, v)] : 0.0;
+    return w * (uu + vv - 2.0 * uv);
+}
+
+// ---- score pass: s_e for all m from S (no pending block); mask != 0: partials of the argmax over the unselected ----
+__global__ __launch_bounds__(kBlock) void k_esp_scores(EspView V, const double* __restrict__ S, int mask) {
+    __shared__ double sv[kBlock / kWave];
+    __shared__ int si[kBlock / kWave];
+    double bv = -INFINITY;
+    int bi = INT_MAX;
+    for (int e = blockIdx.x * kBlock + threadIdx.x; e < V.m; e += gridDim.x * kBlock) {
+        const double s = esp_score(S, V.ld, V.cu[e], V.cv[e], V.cw[e]);
+        V.s[e] = s;
+        if (mask && !V.sel[e]) esp_better(bv, bi, s, e);
+    }
+    if (!mask) return;
+    esp_block_argmax(bv, bi, sv, si);
+    if (threadIdx.x == 0) { V.pv[blockIdx.x] = bv; V.pi[blockIdx.x] = bi; }
+}
+
+// ---- final argmax over the P partials: one workgroup ----
+__global__ __launch_bounds__(kBlock) void k_esp_argmax(EspView V, int P) {
+    __shared__ double sv[kBlock / kWave];
+    __shared__ int si[kBlock / kWave];
+    double bv = -INFINITY;
+    int bi = INT_MAX;
+    for (int p = threadIdx.x; p < P; p += kBlock) esp_better(bv, bi, V.pv[p], V.pi[p]);
+    esp_block_argmax(bv, bi, sv, si);
+    if (threadIdx.x == 0) {
+        if (bi < 0 || bi >= V.m) {      // no finite score among the unselected: flag it, keep the next launch in bounds
+            *V.bad = 1;
+            bi = 0;
+            bv = 0.0;
+        }
+        V.best->val = bv;
+        V.best->idx = bi;
+    }
+}
+
+// ---- z = Sigma a_{e*} = S[u,:] - S[v,:] - sum_{b<j} alpha_b Zb[:,b],  alpha_b = c_b (Zb[u,b] - Zb[v,b]);  into Zb[:,j].
+// grid = ceil(ld / 256) (rows n'..ld get 0: the fold reads whole tiles).  Workgroup 0 records the step. ----
+__global__ __launch_bounds__(kBlock) void k_esp_z(EspView V, const double* __restrict__ S, int j, int k) {
+    __shared__ double alpha[kEspMaxFold];
+    const int e = V.best->idx;
+    const int u = V.cu[e], v = V.cv[e];
+    const size_t ld = V.ld;
+    for (int b = threadIdx.x; b < j; b += kBlock) {
+        const double* zc = V.Zb + (size_t)b * ld;
+        alpha[b] = V.cb[b] * ((u >= 0 ? zc[u] : 0.0) - (v >= 0 ? zc[v] : 0.0));
+    }
+    __syncthreads();
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (i < V.ld) {
+        double z = 0.0;
+        if (i < V.np) {
+            z = (u >= 0 ? S[(size_t)u * ld + i] : 0.0) - (v >= 0 ? S[(size_t)v * ld + i] : 0.0);
+            for (int b = 0; b < j; ++b) z = __builtin_fma(-alpha[b], V.Zb[(size_t)b * ld + i], z);
+        }
+        V.Zb[(size_t)j * ld + i] = z;
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        const double sstar = V.best->val;
+        V.cb[j] = V.cw[e] / (1.0 + sstar);
+        V.order[k] = e;
+        V.gain[k] = sstar;
+        V.sel[e] = 1;
+    }
+}
+
+// ---- s_e <- s_e - w_e c (z_u - z_v)^2 for all m, z = Zb[:,j]; partials of the argmax over the unselected ----
+__global__ __launch_bounds__(kBlock) void k_esp_update(EspView V, int j) {
+    __shared__ double sv[kBlock / kWave];
+    __shared__ int si[kBlock / kWave];
+    const double* z = V.Zb + (size_t)j * V.ld;
+    const double c = V.cb[j];
+    double bv = -INFINITY;
+    int bi = INT_MAX;
+    for (int e = blockIdx.x * kBlock + threadIdx.x; e < V.m; e += gridDim.x * kBlock) {
+        const int u = V.cu[e], v = V.cv[e];
+        const double d = (u >= 0 ? z[u] : 0.0) - (v >= 0 ? z[v] : 0.0);
+        const double s = V.s[e] - V.cw[e] * c * d * d;
+        V.s[e] = s;
+        if (!V.sel[e]) esp_better(bv, bi, s, e);
+    }
+    esp_block_argmax(bv, bi, sv, si);
+    if (threadIdx.x == 0) { V.pv[blockIdx.x] = bv; V.pi[blockIdx.x] = bi; }
+}
+
+// ---- fold: S <- S - Zb[:, :j] diag(c) Zb[:, :j]^T on the matrix cores.  Workgroup = one 64 x 64 tile (grid = tiles x tiles),
+// wave = a 32 x 32 quadrant of 2 x 2 v_mfma_f64_16x16x4_f64 blocks (the tile idiom of k_gj_step): A[i = l & 15][k = l >> 4] =
+// -c_k Zb[row i, k], B[k = l >> 4][j = l & 15] = Zb[col j, k], accumulator = the tile itself in the result layout
+// D[row = (l >> 4) + 4 reg][col = l & 15].  Zb's 4 columns of a k-step come from L2 (ld x j doubles, shared by all tiles). ----
+__global__ __launch_bounds__(256) void k_esp_fold(double* __restrict__ S, const double* __restrict__ Zb, const double* __restrict__ cb,
+                                                  int ld, int j) {
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int li = lane & 15, lk = lane >> 4, wr = wv >> 1, wc = wv & 1;
+    const int r0 = blockIdx.y * kGjT + 32 * wr, c0 = blockIdx.x * kGjT + 32 * wc;
+    gj_d4 acc[2][2];
+#pragma unroll
+    for (int bi = 0; bi < 2; ++bi)
+#pragma unroll
+        for (int bj = 0; bj < 2; ++bj)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) acc[bi][bj][q] = S[(size_t)(r0 + 16 * bi + lk + 4 * q) * ld + c0 + 16 * bj + li];
+    for (int kk = 0; kk < (j + 3) / 4; ++kk) {
+        const int k = 4 * kk + lk;
+        const bool ok = k < j;
+        const double* zc = Zb + (size_t)(ok ? k : 0) * ld;
+        const double nc = ok ? -cb[k] : 0.0;
+        double a[2], b[2];
+#pragma unroll
+        for (int bi = 0; bi < 2; ++bi) a[bi] = ok ? nc * zc[r0 + 16 * bi + li] : 0.0;
+#pragma unroll
+        for (int bj = 0; bj < 2; ++bj) b[bj] = ok ? zc[c0 + 16 * bj + li] : 0.0;
+#pragma unroll
+        for (int bi = 0; bi < 2; ++bi)
+#pragma unroll
+            for (int bj = 0; bj < 2; ++bj) acc[bi][bj] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[bi], b[bj], acc[bi][bj], 0, 0, 0);
+    }
+#pragma unroll
+    for (int bi = 0; bi < 2; ++bi)
+#pragma unroll
+        for (int bj = 0; bj < 2; ++bj)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) S[(size_t)(r0 + 16 * bi + lk + 4 * q) * ld + c0 + 16 * bj + li] = acc[bi][bj][q];
+}
+
+}  // namespace machip
+
+// ---- the handle (include/machip.h: machip_esp) ----
+struct machip_esp {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    int n = 0, np = 0, ld = 0, m = 0, fold = machip::kEspDefaultFold;
+    int form = 0;                 // 0 chain, 1 general (dense Gauss-Jordan inverse)
+    double beta = 0.0;
+    double *bufA = nullptr, *bufB = nullptr;
+    double* sig0 = nullptr;       // pristine Sigma0 (one of bufA / bufB)
+    double* sig = nullptr;        // working copy (the other one)
+    bool live = false;            // sig holds the state after the last selection run
+    int pending = 0;              // columns of Zb not yet folded into sig
+    int *cu = nullptr, *cv = nullptr, *sel = nullptr, *pi = nullptr, *order = nullptr, *bad = nullptr;
+    double *cw = nullptr, *s = nullptr, *Zb = nullptr, *cb = nullptr, *pv = nullptr, *gain = nullptr, *piv = nullptr;
+    machip::EspBest* best = nullptr;
+    std::vector<hipEvent_t> ev;
+
+    machip::EspView view() const {
+        machip::EspView V;
+        V.np = np; V.ld = ld; V.m = m; V.cu = cu; V.cv = cv; V.cw = cw; V.s = s; V.sel = sel; V.Zb = Zb; V.cb = cb;
+        V.pv = pv; V.pi = pi; V.best = best; V.order = order; V.gain = gain; V.bad = bad;
+        return V;
+    }
+    int grid_m() const { return std::max(1, std::min(machip::kEspGrid, (m + machip::kBlock - 1) / machip::kBlock)); }
+
+    // Sigma <- Sigma - Zb diag(c) Zb^T over the j pending columns
+    void fold_into(double* S, int j) {
+        if (j <= 0) return;
+        const int tiles = ld / machip::kGjT;
+        machip::k_esp_fold<<<dim3(tiles, tiles), 256, 0, stream>>>(S, Zb, cb, ld, j);
+    }
+};

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "solver.h"
+#include "esp.h"
 
 namespace machip {
 thread_local std::string g_err;
@@ -1553,6 +1554,231 @@ int machip_host_follow_records(const double* tri3, int J, int n, double e_target
         if (F.triggered()) { *jeff = F.Jeff; break; }
         if (a >= fc.jcap) break;
     }
+    return MACHIP_OK;
+}
+
+// ---- GreedyESP (esp.h) ----
+
+int machip_esp_create(int device, int64_t n, int64_t n_fixed, const int32_t* fi, const int32_t* fj, const double* fw,
+                      int64_t m, const int32_t* ci, const int32_t* cj, const double* cw, int fold, int flags, machip_esp** out) {
+    if (!out) return fail(MACHIP_BAD_ARG, "out is NULL");
+    *out = nullptr;
+    if (n < 2) return fail(MACHIP_BAD_ARG, "num_nodes must be at least 2");
+    if (n_fixed < 0 || m < 0 || m > 2000000000ll) return fail(MACHIP_BAD_ARG, "bad edge counts");
+    if ((n_fixed && (!fi || !fj || !fw)) || (m && (!ci || !cj || !cw))) return fail(MACHIP_BAD_ARG, "NULL edge array");
+    if (fold == 0) fold = kEspDefaultFold;
+    if (fold < 1 || fold > kEspMaxFold) return fail(MACHIP_BAD_ARG, "fold must be in [1, 256]");
+    if (flags & ~MACHIP_ESP_DENSE_INVERSE) return fail(MACHIP_BAD_ARG, "unknown flags");
+    if (n > kEspChainMaxN) return fail(MACHIP_BAD_ARG, "GreedyESP keeps (L_red + beta I)^-1 dense: num_nodes must be <= 32768 (chain-fixed graphs), <= 16384 otherwise");
+    for (int64_t e = 0; e < n_fixed; ++e)
+        if (fi[e] < 0 || fi[e] >= n || fj[e] < 0 || fj[e] >= n || !std::isfinite(fw[e])) return fail(MACHIP_BAD_ARG, "fixed edge out of range or weight not finite");
+    for (int64_t e = 0; e < m; ++e)
+        if (ci[e] < 0 || ci[e] >= n || cj[e] < 0 || cj[e] >= n || !std::isfinite(cw[e])) return fail(MACHIP_BAD_ARG, "candidate edge out of range or weight not finite");
+    // beta (the reference: Cholesky with beta = 0; on failure raise if a reduced row is all zero, else beta = 1e-4), decided by a
+    // union-find over F
+    const int N = (int)n, np = N - 1;
+    std::vector<int> par(N), has(N, 0);
+    std::iota(par.begin(), par.end(), 0);
+    auto root = [&](int a) { while (par[a] != a) { par[a] = par[par[a]]; a = par[a]; } return a; };
+    int comps = N;
+    for (int64_t e = 0; e < n_fixed; ++e) {
+        if (fi[e] == fj[e] || fw[e] == 0.0) continue;
+        has[fi[e]] = has[fj[e]] = 1;
+        const int a = root(fi[e]), b = root(fj[e]);
+        if (a != b) { par[a] = b; --comps; }
+    }
+    double beta = 0.0;
+    if (comps > 1) {
+        for (int i = 1; i < N; ++i)
+            if (!has[i]) return fail(MACHIP_DISCONNECTED, "node " + std::to_string(i) + " has no fixed edge: row " + std::to_string(i - 1) + " of L_fixed is all zeros");
+        beta = 1e-4;
+    }
+    // chain form: F is exactly the path (i, i+1), parallel links summed
+    std::vector<double> link((size_t)np, 0.0);
+    bool chain = !(flags & MACHIP_ESP_DENSE_INVERSE) && comps == 1;
+    for (int64_t e = 0; chain && e < n_fixed; ++e) {
+        const int a = std::min(fi[e], fj[e]), b = std::max(fi[e], fj[e]);
+        if (b != a + 1) chain = false;
+        else link[(size_t)a] += fw[e];
+    }
+    for (int i = 0; chain && i < np; ++i) if (!(link[(size_t)i] > 0.0)) chain = false;
+    if (!chain && n > kEspDenseMaxN)
+        return fail(MACHIP_BAD_ARG, "GreedyESP inverts L_red + beta I densely when the fixed edges are not exactly the chain (i, i+1): num_nodes must be <= 16384");
+    if (machip_device_count() <= 0) return fail(MACHIP_NO_DEVICE, "no HIP device visible");
+    HIP_TRY(hipSetDevice(device));
+    machip_esp* h = new machip_esp();
+    h->device = device; h->n = N; h->np = np; h->m = (int)m; h->fold = fold; h->beta = beta; h->form = chain ? 0 : 1;
+    h->ld = (np + kGjT - 1) / kGjT * kGjT;
+    auto body = [&]() -> int {
+        HIP_TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+        const size_t ld = (size_t)h->ld, ms = (size_t)std::max<int64_t>(m, 1);
+        ST_TRY(dev_alloc(&h->bufA, ld * ld)); ST_TRY(dev_alloc(&h->bufB, ld * ld));
+        ST_TRY(dev_alloc(&h->cu, ms)); ST_TRY(dev_alloc(&h->cv, ms)); ST_TRY(dev_alloc(&h->cw, ms)); ST_TRY(dev_alloc(&h->s, ms));
+        ST_TRY(dev_alloc(&h->sel, ms)); ST_TRY(dev_alloc(&h->order, ms)); ST_TRY(dev_alloc(&h->gain, ms));
+        ST_TRY(dev_alloc(&h->Zb, ld * (size_t)fold)); ST_TRY(dev_alloc(&h->cb, (size_t)fold));
+        ST_TRY(dev_alloc(&h->pv, (size_t)kEspGrid)); ST_TRY(dev_alloc(&h->pi, (size_t)kEspGrid)); ST_TRY(dev_alloc(&h->best, 1));
+        ST_TRY(dev_alloc(&h->bad, 1)); ST_TRY(dev_alloc(&h->piv, (size_t)2 * kGjB * kGjB));
+        HIP_TRY(hipMemsetAsync(h->Zb, 0, sizeof(double) * ld * (size_t)fold, h->stream));
+        HIP_TRY(hipMemsetAsync(h->cb, 0, sizeof(double) * (size_t)fold, h->stream));
+        HIP_TRY(hipMemsetAsync(h->bad, 0, sizeof(int), h->stream));
+        if (m) {
+            std::vector<int> u((size_t)m), v((size_t)m);
+            for (int64_t e = 0; e < m; ++e) { u[(size_t)e] = ci[e] - 1; v[(size_t)e] = cj[e] - 1; }
+            HIP_TRY(hipMemcpyAsync(h->cu, u.data(), sizeof(int) * (size_t)m, hipMemcpyHostToDevice, h->stream));
+            HIP_TRY(hipMemcpyAsync(h->cv, v.data(), sizeof(int) * (size_t)m, hipMemcpyHostToDevice, h->stream));
+            HIP_TRY(hipMemcpyAsync(h->cw, cw, sizeof(double) * (size_t)m, hipMemcpyHostToDevice, h->stream));
+            HIP_TRY(hipStreamSynchronize(h->stream));     // (host staging goes out of scope)
+        }
+        if (chain) {
+            std::vector<double> R((size_t)np);
+            double acc = 0.0;
+            for (int i = 0; i < np; ++i) { acc += 1.0 / link[(size_t)i]; R[(size_t)i] = acc; }
+            double* dR = nullptr;
+            ST_TRY(dev_alloc(&dR, (size_t)np));
+            HIP_TRY(hipMemcpyAsync(dR, R.data(), sizeof(double) * (size_t)np, hipMemcpyHostToDevice, h->stream));
+            k_esp_chain_fill<<<dim3((unsigned)((ld + kBlock - 1) / kBlock), (unsigned)ld), kBlock, 0, h->stream>>>(h->bufA, dR, np, (int)ld);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipStreamSynchronize(h->stream));
+            (void)hipFree(dR);
+            h->sig0 = h->bufA; h->sig = h->bufB;
+            return MACHIP_OK;
+        }
+        // general form: dense L_red + beta I (identity beyond n'), entries summed on the host in edge order, then inverted
+        std::vector<double> diag((size_t)np, beta);
+        std::vector<std::pair<int64_t, double>> off;
+        off.reserve((size_t)n_fixed);
+        for (int64_t e = 0; e < n_fixed; ++e) {
+            const int a = fi[e] - 1, b = fj[e] - 1;
+            if (a == b) continue;
+            if (a >= 0) diag[(size_t)a] += fw[e];
+            if (b >= 0) diag[(size_t)b] += fw[e];
+            if (a >= 0 && b >= 0) off.emplace_back((int64_t)std::min(a, b) * (int64_t)ld + std::max(a, b), fw[e]);
+        }
+        std::stable_sort(off.begin(), off.end(), [](const std::pair<int64_t, double>& x, const std::pair<int64_t, double>& y) { return x.first < y.first; });
+        std::vector<int64_t> pos;
+        std::vector<double> val;
+        for (int i = 0; i < (int)ld; ++i) { pos.push_back((int64_t)i * (int64_t)ld + i); val.push_back(i < np ? diag[(size_t)i] : 1.0); }
+        for (size_t q = 0; q < off.size();) {
+            size_t r = q;
+            double w = 0.0;
+            for (; r < off.size() && off[r].first == off[q].first; ++r) w += off[r].second;
+            const int64_t a = off[q].first / (int64_t)ld, b = off[q].first % (int64_t)ld;
+            pos.push_back(a * (int64_t)ld + b); val.push_back(-w);
+            pos.push_back(b * (int64_t)ld + a); val.push_back(-w);
+            q = r;
+        }
+        int64_t* dpos = nullptr;
+        double* dval = nullptr;
+        ST_TRY(dev_alloc(&dpos, pos.size())); ST_TRY(dev_alloc(&dval, val.size()));
+        HIP_TRY(hipMemsetAsync(h->bufA, 0, sizeof(double) * ld * ld, h->stream));
+        HIP_TRY(hipMemcpyAsync(dpos, pos.data(), sizeof(int64_t) * pos.size(), hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(hipMemcpyAsync(dval, val.data(), sizeof(double) * val.size(), hipMemcpyHostToDevice, h->stream));
+        const int cnt = (int)pos.size();
+        k_esp_scatter<<<std::max(1, std::min(kMaxGrid, (cnt + kBlock - 1) / kBlock)), kBlock, 0, h->stream>>>(h->bufA, dpos, dval, cnt);
+        // (L_red + beta I)^-1: ld / 32 blocked Gauss-Jordan steps on the matrix cores, ping-pong between the two buffers, look-ahead
+        // pivot blocks from 1 024 rows on -- exactly as solver.h inverts the capacitance matrix (woodbury.h)
+        const int tiles = (int)ld / kGjT;
+        double *src = h->bufA, *dst = h->bufB;
+        const bool look = (int)ld >= kEspGjLookMin;
+        for (int kb = 0, k = 0; kb < (int)ld; kb += kGjB, ++k) {
+            if (look) k_gj_step<0><<<dim3(tiles, tiles), 256, 0, h->stream>>>(src, dst, (int)ld, kb, h->bad, k ? h->piv + (size_t)(k & 1) * kGjB * kGjB : nullptr,
+                                                                               h->piv + (size_t)((k + 1) & 1) * kGjB * kGjB);
+            else k_gj_step<0><<<dim3(tiles, tiles), 256, 0, h->stream>>>(src, dst, (int)ld, kb, h->bad);
+            std::swap(src, dst);
+        }
+        HIP_TRY(hipGetLastError());
+        int hbad = 0;
+        HIP_TRY(hipMemcpyAsync(&hbad, h->bad, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        (void)hipFree(dpos); (void)hipFree(dval);
+        if (hbad) return fail(MACHIP_NOT_CONVERGED, "L_red + beta I is not positive definite numerically (a non-positive Gauss-Jordan pivot)");
+        h->sig0 = src; h->sig = dst;
+        return MACHIP_OK;
+    };
+    const int st = body();
+    if (st != MACHIP_OK) { machip_esp_destroy(h); return st; }
+    *out = h;
+    return MACHIP_OK;
+}
+
+void machip_esp_destroy(machip_esp* h) {
+    if (!h) return;
+    (void)hipSetDevice(h->device);
+    if (h->stream) (void)hipStreamSynchronize(h->stream);
+    for (hipEvent_t e : h->ev) (void)hipEventDestroy(e);
+    void* bufs[] = {h->bufA, h->bufB, h->cu, h->cv, h->sel, h->pi, h->order, h->bad, h->cw, h->s, h->Zb, h->cb, h->pv, h->gain, h->piv, h->best};
+    for (void* q : bufs) if (q) (void)hipFree(q);
+    if (h->stream) (void)hipStreamDestroy(h->stream);
+    delete h;
+}
+
+int machip_esp_info(machip_esp* h, int32_t* info4, double* beta) {
+    if (!h) return fail(MACHIP_BAD_ARG, "NULL handle");
+    if (info4) { info4[0] = h->form; info4[1] = h->ld; info4[2] = h->fold; info4[3] = h->live ? h->pending : 0; }
+    if (beta) *beta = h->beta;
+    return MACHIP_OK;
+}
+
+int machip_esp_select(machip_esp* h, int nb, const int64_t* ks, int32_t* order_out, double* gain_out, double* t_ms_out) {
+    if (!h || nb < 1 || !ks) return fail(MACHIP_BAD_ARG, "NULL handle, no budgets or ks is NULL");
+    if (ks[0] <= 0) return fail(MACHIP_BAD_ARG, "budgets must be positive");
+    for (int i = 0; i + 1 < nb; ++i) if (ks[i] > ks[i + 1]) return fail(MACHIP_BAD_ARG, "budgets must be monotonically increasing");
+    if (ks[nb - 1] > h->m) return fail(MACHIP_BAD_ARG, "not enough candidate edges to satisfy the largest budget");
+    HIP_TRY(hipSetDevice(h->device));
+    while ((int)h->ev.size() < nb + 1) {
+        hipEvent_t e;
+        HIP_TRY(hipEventCreate(&e));
+        h->ev.push_back(e);
+    }
+    const int K = (int)ks[nb - 1], B = h->fold, P = h->grid_m(), zg = (h->ld + kBlock - 1) / kBlock;
+    const EspView V = h->view();
+    hipStream_t st = h->stream;
+    h->live = false;
+    HIP_TRY(hipEventRecord(h->ev[0], st));
+    HIP_TRY(hipMemcpyAsync(h->sig, h->sig0, sizeof(double) * (size_t)h->ld * (size_t)h->ld, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipMemsetAsync(h->sel, 0, sizeof(int) * (size_t)h->m, st));
+    HIP_TRY(hipMemsetAsync(h->bad, 0, sizeof(int), st));
+    k_esp_scores<<<P, kBlock, 0, st>>>(V, h->sig, 1);
+    k_esp_argmax<<<1, kBlock, 0, st>>>(V, P);
+    for (int k = 0, b = 0; k < K; ++k) {
+        const int j = k % B;
+        k_esp_z<<<zg, kBlock, 0, st>>>(V, h->sig, j, k);
+        if (k + 1 < K) {
+            k_esp_update<<<P, kBlock, 0, st>>>(V, j);
+            k_esp_argmax<<<1, kBlock, 0, st>>>(V, P);
+        }
+        if (j == B - 1) h->fold_into(h->sig, B);
+        while (b < nb && ks[b] == k + 1) HIP_TRY(hipEventRecord(h->ev[1 + b++], st));
+    }
+    HIP_TRY(hipGetLastError());
+    h->pending = K % B;
+    int hbad = 0;
+    if (order_out) HIP_TRY(hipMemcpyAsync(order_out, h->order, sizeof(int) * (size_t)K, hipMemcpyDeviceToHost, st));
+    if (gain_out) HIP_TRY(hipMemcpyAsync(gain_out, h->gain, sizeof(double) * (size_t)K, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&hbad, h->bad, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (t_ms_out)
+        for (int i = 0; i < nb; ++i) {
+            float ms = 0.0f;
+            HIP_TRY(hipEventElapsedTime(&ms, h->ev[0], h->ev[1 + i]));
+            t_ms_out[i] = ms;
+        }
+    h->live = true;
+    if (hbad) return fail(MACHIP_NOT_CONVERGED, "no finite score among the unselected candidates");
+    return MACHIP_OK;
+}
+
+int machip_esp_weighted_resistances(machip_esp* h, double* r_out) {
+    if (!h || (!r_out && h->m)) return fail(MACHIP_BAD_ARG, "NULL handle or output");
+    HIP_TRY(hipSetDevice(h->device));
+    double* S = h->live ? h->sig : h->sig0;
+    if (h->live && h->pending) { h->fold_into(S, h->pending); h->pending = 0; }
+    if (h->m) {
+        k_esp_scores<<<h->grid_m(), kBlock, 0, h->stream>>>(h->view(), S, 0);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(r_out, h->s, sizeof(double) * (size_t)h->m, hipMemcpyDeviceToHost, h->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(h->stream));
     return MACHIP_OK;
 }
 

@@ -1,5 +1,6 @@
-"""Public solver surface of the drop-in (the names mac/solvers/__init__.py exports)."""
+"""Public solver surface of the drop-in (the names mac/solvers/__init__.py exports, plus GreedyESP)."""
 from mac_amd.solvers.baseline import NaiveGreedy  # noqa: F401
+from mac_amd.solvers.esp import GreedyESP  # noqa: F401
 from mac_amd.solvers.mac import MAC  # noqa: F401
 
-__all__ = ["MAC", "NaiveGreedy"]
+__all__ = ["MAC", "NaiveGreedy", "GreedyESP"]
