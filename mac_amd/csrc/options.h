@@ -32,10 +32,7 @@ namespace machip {
     X(lob_patience) X(lob_small_s) X(lob_fuse)                                                                                     \
     /* select / assembly / lanes / communicators (the handle-creation ones are read when the handle, or its first lane, is made) */ \
     X(sel_small) X(sel_fuse) X(asm_g) X(asm_maxgrid) X(vbudget_mb) X(vcap) X(lanes) X(lane_vbudget_mb) X(lane_queues) X(shard_eig) X(ipc_panel) \
-    X(rccl_timeout_s)                                                                                                              \
-    /* experiments (compiled in with -DMACHIP_EXPERIMENTS only: tools/) */                                                         \
-    X(cheb_deg) X(cheb_after) X(cheb_chunk) X(cheb_depth) X(panel_fused) X(panel_spin_us) X(lob_pan2)                              \
-    X(blocklan) X(blocklan_min_steps) X(blk_chunk) X(blk_chunk_near)
+    X(rccl_timeout_s)
 
 enum OptId {
 #define X(n) kOpt_##n,
@@ -73,7 +70,6 @@ inline long option_parse(int id, const char* s) {
         if (!strcmp(s, "auto")) return 0;
         if (!strcmp(s, "lanczos")) return 1;
         if (!strcmp(s, "lobpcg")) return 2;
-        if (!strcmp(s, "jacobi")) return 3;
     }
     if (id == kOpt_spmv) {
         if (!strcmp(s, "stream")) return 1;

@@ -141,7 +141,6 @@ struct PanPlan {
     int grid2 = 1, block2 = 256;     // launch shape of k_pan_fin
     bool band = false;               // diagonal + columns r -/+ 1 kept out of the tiles and added by k_pan_fin (evens out the diagonal cells)
     bool verify = false;             // a row is longer than 127 entries: the build must confirm that no (row, panel) count exceeds 127
-    bool fused = false;              // one launch per step (k_pan_step) instead of k_pan_mul + k_pan_fin (measured SLOWER: profiles/r4_c4_one_launch_step.md)
     bool u = false;                  // shifted recurrence with an 8-byte operand (panel_u.h: k_pan_mul8<LPT, TWT> + k_pan_finu); C is even then
     int LPT = 1, TWT = 8;            // ... 16-byte operand loads per thread, tiles per worker wave the instantiation holds (3 | 5 | 8)
 };
@@ -246,12 +245,7 @@ inline PanPlan plan_panel(const Options& opt, int n, long nnz, int maxlen, bool 
                C <= (pp.TWT == 3 ? pan_u_cols(pp.LPT, 3) : pp.TWT == 5 ? pan_u_cols(pp.LPT, 5) : pan_u_cols(pp.LPT, 8));
         if (!pp.u) return plan_panel(opt, n, nnz, maxlen, allowed, nnz_cap, shape_only, false);      // the record form's shape rules
     }
-    // MACHIP_PANEL_FUSED=1: the one-launch form (k_pan_step; tickets for 256 row blocks, one partial-sum slot per slice).  Off by
-    // default: 26.9 against 19.1 us per step at configs[3] -- the in-launch hand-off costs more than the launch it saves.
-#ifdef MACHIP_EXPERIMENTS
-    pp.fused = OPT(panel_fused, 0) != 0 && nb <= 256 && nb * np <= 256 && pp.cells == 1 && !pp.u;
-#endif
-    pp.band = OPT(panel_band, 1) != 0 && (nnz_cap >= 0 ? nnz_cap : nnz) < (1l << 28);     // (CSR positions are packed with 3 count bits; the LOBPCG kernels finish rows without the band terms: solver.h passes band = false there)
+    pp.band = OPT(panel_band, 1) != 0 && (nnz_cap >= 0 ? nnz_cap : nnz) < (1l << 28);     // (CSR positions are packed with 3 count bits)
     pp.block2 = OPT(panel_b2, 512);
     if (pp.block2 != 256 && pp.block2 != 512 && pp.block2 != 1024) pp.block2 = 256;
     pp.grid2 = (int)std::max<long>(1, std::min<long>(OPT(panel_g2, grid_cap(opt)), ((long)n + pp.block2 - 1) / pp.block2));

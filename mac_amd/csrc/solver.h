@@ -31,10 +31,6 @@
 #include "plan.h"
 #include "tridiag.h"
 #include "follow.h"
-#ifdef MACHIP_EXPERIMENTS
-#include "band.h"
-#include "blocklan.h"
-#endif
 
 namespace machip {
 
@@ -191,7 +187,6 @@ struct Solver {
     PanView panv{};
     bool pan_live = false;         // the panel form (shifted-recurrence shape) of the matrix being solved is built: plain products may use it (panel_spmv)
     bool pan_u = false;            // the running sequence's panel steps are those of the shifted recurrence (panel_u.h): 8-byte operand
-    bool pan_u_off = false;        // ... ruled out for the rest of this solve (the drift monitor tripped)
     PanU pu{};
     PeerSet* d_ps = nullptr; PeerSet h_ps{};      // the row-partitioned panel step's peer set, in device memory
     double *pu_sig = nullptr, *pu_U0 = nullptr, *pu_U1 = nullptr;     // (pu.U0 / U1 point at these, or at the record buffers under an inter-process communicator)
@@ -265,11 +260,6 @@ struct Solver {
             for (void* q : pk) if (q) (void)hipFree(q);
         }
         if (h_lrec) (void)hipHostFree(h_lrec);
-#ifdef MACHIP_EXPERIMENTS
-        if (h_brec) (void)hipHostFree(h_brec);
-        if (h_bs) (void)hipHostFree(h_bs);
-        { void* pb2[] = {bZ0, bZ1, bpart, bU0, bwarm, bsdev, brec, (void*)bclk}; for (void* q : pb2) if (q) (void)hipFree(q); }
-#endif
         for (void* p : ptrs) if (p) (void)hipFree(p);
         if (h_tri) (void)hipHostFree(h_tri);
         if (h_flag) (void)hipHostFree(h_flag);
@@ -406,19 +396,7 @@ struct Solver {
             default: k_lan_persist<6, T><<<1, kPersistThreads, 0, stream>>>(ppack, L, steps); break;
         }
     }
-    void launch_persist(const CsrView& A, int steps, bool f32 = false, const PersistCheb& ch = PersistCheb()) {
-#ifdef MACHIP_EXPERIMENTS
-        if (ch.deg >= 2) {       // Chebyshev-filtered recurrence (fp64; measured slower: DESIGN "negatives")
-            const PersistView L = persist_view<double>();
-            switch ((n + 2 * kPersistThreads - 1) / (2 * kPersistThreads)) {
-                case 1: k_lan_persist<2, double, true><<<1, kPersistThreads, 0, stream>>>(ppack, L, steps, ch); break;
-                case 2: k_lan_persist<4, double, true><<<1, kPersistThreads, 0, stream>>>(ppack, L, steps, ch); break;
-                default: k_lan_persist<6, double, true><<<1, kPersistThreads, 0, stream>>>(ppack, L, steps, ch); break;
-            }
-            return;
-        }
-#endif
-        (void)ch;
+    void launch_persist(const CsrView& A, int steps, bool f32 = false) {
         if (f32) launch_persist_t<float>(A, steps); else launch_persist_t<double>(A, steps);
     }
 
@@ -447,7 +425,7 @@ struct Solver {
     int pan_row_buffers(const PanPlan& pn, bool band) {
         bool dropped = false;
         if ((size_t)pn.NP * (size_t)n > pan_y_cap) {
-            ST_TRY(pan_regrow(&panv.ypart, (size_t)pn.NP * ((size_t)n + 2), &dropped));     // (k_pan_step: even plane stride, pairs of rows)
+            ST_TRY(pan_regrow(&panv.ypart, (size_t)pn.NP * ((size_t)n + 2), &dropped));
             ST_TRY(pan_regrow(&panv.ps, ((size_t)pn.NP + 1) * (size_t)n, &dropped));
             pan_y_cap = (size_t)pn.NP * (size_t)n;
             pan_rows_ready = false;
@@ -462,7 +440,7 @@ struct Solver {
     }
     // (Re)build the panel form of A on the stream: buffers grow on demand (cached chunk graphs carry their addresses).
     // rows_ready: the assembly has already written the per-row tables (ps, band) for this shape -- k_pan_rows is not needed.
-    int ensure_panel(const CsrView& A, long nnz, const PanPlan& pn, bool band = false, bool rows_ready = false) {
+    int ensure_panel(const CsrView& A, long nnz, const PanPlan& pn, bool band, bool rows_ready) {
         const size_t cells = (size_t)pn.NB * pn.NP, NTP = (size_t)kPanWork * pn.TWW;
         const size_t NT = cells * NTP;
         bool dropped = false;
@@ -472,11 +450,9 @@ struct Solver {
         }
         ST_TRY(pan_row_buffers(pn, band));
         if (!panv.coef) ST_TRY(dev_alloc(&panv.coef, 8));
-        if (!panv.tick) { ST_TRY(dev_alloc(&panv.tick, 256)); ST_TRY(dev_alloc(&panv.claim, 4096)); }     // (NB <= 256, NB NP <= 4096: plan_panel)
         // band mode (Lanczos form, two launches): diagonal and chain neighbours stay out of the tiles -- k_pan_fin adds them
         panv.band = band ? 1 : 0;
         panv.rev = OPT(panel_rev, 1) != 0 ? 1 : 0;     // odd steps of the shifted form walk each wave's chunks backwards (panel_u.h: what the XCD's L2 still holds comes first); 0: forwards always
-        panv.spin_ticks = OPT(panel_spin_us, 20) * 100;
 #ifdef PAN_CLOCKS
         if (!panv.clk) { ST_TRY(dev_alloc(&panv.clk, (size_t)16 * kMaxGrid)); HIP_TRY(hipMemsetAsync(panv.clk, 0, sizeof(long long) * 16 * kMaxGrid, stream)); }
 #endif
@@ -546,18 +522,6 @@ struct Solver {
 #endif
     void launch_pan_step(const PipeView& L, int s, int jhost = -1) {
         const int g1 = pan.NB * pan.NP;
-#ifdef MACHIP_EXPERIMENTS
-        if (pan.fused) {     // one launch per step (k_pan_step; measured slower: profiles/r4_c4_one_launch_step.md)
-            switch (pan.RPT) {
-#define MACHIP_PAN_CASE(R) case R: k_pan_step<R><<<g1, kPanThreads, 0, stream>>>(PAN_STEP_ARGS(panv, L, s)); break;
-                MACHIP_PAN_CASE(1) MACHIP_PAN_CASE(2) MACHIP_PAN_CASE(3) MACHIP_PAN_CASE(4) MACHIP_PAN_CASE(5) MACHIP_PAN_CASE(6)
-                MACHIP_PAN_CASE(7) MACHIP_PAN_CASE(8) MACHIP_PAN_CASE(9) MACHIP_PAN_CASE(10) MACHIP_PAN_CASE(11) MACHIP_PAN_CASE(12)
-#undef MACHIP_PAN_CASE
-                default: k_pan_step<13><<<g1, kPanThreads, 0, stream>>>(PAN_STEP_ARGS(panv, L, s)); break;
-            }
-            return;
-        }
-#endif
         if (pan_u) {             // shifted recurrence (panel_u.h): 8-byte operand, no prologue in the matrix kernel; the row kernel leads
             if (pan32 && jhost >= 0 && jhost >= pan32_from) {      // mixed mode: this step reads fp32 tile values (TWT = 3 shapes only: solve() checks)
                 switch (pan.LPT) {
@@ -608,23 +572,6 @@ struct Solver {
         else if (pan.block2 == 512) k_pan_fin<512><<<pan.grid2, 512, 0, stream>>>(PAN_FIN_ARGS(panv, L, s));
         else k_pan_fin<256><<<pan.grid2, 256, 0, stream>>>(PAN_FIN_ARGS(panv, L, s));
     }
-
-#ifdef MACHIP_EXPERIMENTS
-    // y_p = L[block, panel p] w for a plain operand vector (k_pan_mul<RPT, RAW = true>): the diagonally preconditioned mode's product
-    void launch_pan_mul_raw(const double* w) {
-        const int g1 = pan.NB * pan.NP;
-        PipeView L{};        // (unused by the RAW instantiation: no records, no prologue)
-        L.n = n; L.part = lx_part + (size_t)2 * kLobNS * kMaxGrid; L.st = st;      // (part: w^T L w per (row block, panel) cell)
-        const Z2* wz = reinterpret_cast<const Z2*>(w);
-        switch (pan.RPT) {
-#define MACHIP_PAN_CASE(R) case R: k_pan_mul<R, true><<<g1, kPanThreads, 0, stream>>>(wz, L.part, L.st, panv.tptr, panv.thead, panv.n, panv.C, panv.NP, panv.TWW, panv, L, 0); break;
-            MACHIP_PAN_CASE(1) MACHIP_PAN_CASE(2) MACHIP_PAN_CASE(3) MACHIP_PAN_CASE(4) MACHIP_PAN_CASE(5) MACHIP_PAN_CASE(6)
-            MACHIP_PAN_CASE(7) MACHIP_PAN_CASE(8) MACHIP_PAN_CASE(9) MACHIP_PAN_CASE(10) MACHIP_PAN_CASE(11) MACHIP_PAN_CASE(12)
-#undef MACHIP_PAN_CASE
-            default: k_pan_mul<13, true><<<g1, kPanThreads, 0, stream>>>(wz, L.part, L.st, panv.tptr, panv.thead, panv.n, panv.C, panv.NP, panv.TWW, panv, L, 0); break;
-        }
-    }
-#endif
 
     // ---- row-partitioned chunk: per step one launch per rank, ordered by events (ShardGroup) ----
     void shard_split(const SpmvPlan& pl) {
@@ -926,10 +873,7 @@ struct Solver {
         if (!lob_ready) {
             ST_TRY(dev_alloc(&lx_x, n)); ST_TRY(dev_alloc(&lx_Lx, n)); ST_TRY(dev_alloc(&lx_p, n));
             ST_TRY(dev_alloc(&lx_Lp, n)); ST_TRY(dev_alloc(&lx_Lw, n));
-            const bool jsave = lob_jacobi;
-            lob_jacobi = false;
             const size_t tcap = std::max((size_t)lob_c() * (size_t)lob_stride(), (size_t)n);   // chunk-transposed, zero padded past n
-            lob_jacobi = jsave;
             double** tr[] = {&lx_rT, &lx_wT, &lx_tl, &lx_tdinv, &lx_tcu, &lx_ba, &lx_bd, &lx_bu};
             for (double** q : tr) {
                 ST_TRY(dev_alloc(q, tcap));
@@ -941,7 +885,7 @@ struct Solver {
                 ST_TRY(dev_alloc(&lx_as, fcap)); ST_TRY(dev_alloc(&lx_bs, fcap));
                 ST_TRY(dev_alloc(&lx_maps, 4 * (size_t)kMaxGrid));   // one map per workgroup and direction
             }
-            ST_TRY(dev_alloc(&lx_part, (size_t)(2 * kLobNS + 1) * kMaxGrid)); ST_TRY(dev_alloc(&lx_partR, 2 * kMaxGrid));     // (two parities of the 15 sums + w^T L w per panel cell: k_lob_update_pan)
+            ST_TRY(dev_alloc(&lx_part, (size_t)kLobNS * kMaxGrid)); ST_TRY(dev_alloc(&lx_partR, 2 * kMaxGrid));
             ST_TRY(dev_alloc(&lx_bad, 1)); ST_TRY(dev_alloc(&lx_st, 1));
             HIP_TRY(hipHostMalloc((void**)&h_lrec, sizeof(double) * 4 * (size_t)(kLobCap + kLobMaxChunk + 4), hipHostMallocMapped));
             memset(h_lrec, 0, sizeof(double) * 4 * (size_t)(kLobCap + kLobMaxChunk + 4));
@@ -957,13 +901,8 @@ struct Solver {
     }
     // layout of the tridiagonal solver: up to n = 16 384 one workgroup, c = ceil(n/1024) unknowns per thread;
     // beyond, 4 unknowns per thread and as many 1024-thread workgroups as that takes
-    bool lob_jacobi = false;   // the running preconditioned solve uses the diagonal preconditioner (natural layout, c = 1)
-    bool lob_pan = false;      // ... and its product runs in column-panel form
-    int lob_par0 = 0;          // parity of the iterate count at the start of the chunk being enqueued
-    bool lob_pan2 = false;     // ... with two launches per iteration (k_lob_update_pan; MACHIP_LOB_PAN2=0: k_pan_find + k_lob_update)
-    int lob_c() const { return lob_jacobi ? 1 : n > kTriMaxN ? kTriBigC : (n + kTriThreads - 1) / kTriThreads; }
+    int lob_c() const { return n > kTriMaxN ? kTriBigC : (n + kTriThreads - 1) / kTriThreads; }
     int lob_stride() const {
-        if (lob_jacobi) return n;
         if (n <= kTriMaxN) return kTriThreads;
         const int q = (n + kTriBigC - 1) / kTriBigC;
         return (q + kTriThreads - 1) / kTriThreads * kTriThreads;
@@ -1001,34 +940,11 @@ struct Solver {
             }
             launch_spmv(pl, stream, AT, L.wT, op);
             if (fuse && s + 1 < steps) k_lob_fused<CMAX><<<1, kTriThreads, 0, stream>>>(L, W0, s);
-            else k_lob_update<false><<<L.P_a, kBlock, 0, stream>>>(L, s);
+            else k_lob_update<<<L.P_a, kBlock, 0, stream>>>(L, s);
         }
         k_lob_tail<<<1, 64, 0, stream>>>(L, steps);
     }
     void lob_launch_chunk(const CsrView& AT, const SpmvPlan& pl, const LobView& L, int steps) {
-#ifdef MACHIP_EXPERIMENTS
-        if (lob_jacobi) {          // diagonal preconditioner: two launches per iteration (three with the column-panel product)
-            OpLob op;
-            op.L = L;
-            for (int s = 0; s < steps; ++s) {
-                if (lob_pan && lob_pan2) {     // two launches per iteration: product (+ w^T L w per cell), then sums + Rayleigh-Ritz + update + next sums
-                    launch_pan_mul_raw(L.wT);
-                    const double* pw = lx_part + (size_t)2 * kLobNS * kMaxGrid;
-                    if (pan.block2 == 512) k_lob_update_pan<512><<<pan.grid2, 512, 0, stream>>>(L, panv.ypart, panv.NP, pw, pan.NB * pan.NP, s, (lob_par0 + s + 1) & 1);
-                    else if (pan.block2 == 1024) k_lob_update_pan<1024><<<pan.grid2, 1024, 0, stream>>>(L, panv.ypart, panv.NP, pw, pan.NB * pan.NP, s, (lob_par0 + s + 1) & 1);
-                    else k_lob_update_pan<256><<<pan.grid2, 256, 0, stream>>>(L, panv.ypart, panv.NP, pw, pan.NB * pan.NP, s, (lob_par0 + s + 1) & 1);
-                    continue;
-                }
-                if (lob_pan) {     // Lw = L w in column-panel form (panel.h: gathers served by LDS), then partial sums + inner products
-                    launch_pan_mul_raw(L.wT);
-                    k_pan_find<<<L.P_c, kBlock, 0, stream>>>(op, panv.ypart, panv.NP);
-                } else launch_spmv(pl, stream, AT, L.wT, op);
-                k_lob_update<true><<<L.P_a, kBlock, 0, stream>>>(L, s);
-            }
-            k_lob_tail<<<1, 64, 0, stream>>>(L, steps);
-            return;
-        }
-#endif
         if (n > kTriMaxN) {
             OpLob op;
             op.L = L;
@@ -1044,7 +960,7 @@ struct Solver {
                     k_wb_w<<<(int)std::min<size_t>(kMaxGrid, W.cap / kWbwRows), kWbwThreads, 0, stream>>>(L, W);
                 }
                 launch_spmv(pl, stream, AT, L.wT, op);
-                k_lob_update<false><<<L.P_a, kBlock, 0, stream>>>(L, s);
+                k_lob_update<<<L.P_a, kBlock, 0, stream>>>(L, s);
             }
             k_lob_tail<<<1, 64, 0, stream>>>(L, steps);
             return;
@@ -1061,7 +977,7 @@ struct Solver {
     int lob_enqueue_chunk(const CsrView& A, const CsrView& AT, const SpmvPlan& pl, const LobView& L, int steps) {
         if (!use_graph() || wb_active.s > 0) { lob_launch_chunk(AT, pl, L, steps); return MACHIP_OK; }   // (closure count is baked into the launches)
         if (graph_csr_key != (const void*)A.val) { drop_graphs(); graph_csr_key = (const void*)A.val; }
-        const auto key = std::make_tuple(1000 + pl.variant, pl.width, pl.grid, L.c + (n > kTriMaxN ? 100 : 0) + (lob_jacobi ? 1000 : 0) + (lob_pan ? 2000 + 10000 * pan.NP + 1000000 * pan.NB : 0) + (lob_pan2 ? 500 + 250 * lob_par0 : 0), steps);
+        const auto key = std::make_tuple(1000 + pl.variant, pl.width, pl.grid, L.c + (n > kTriMaxN ? 100 : 0), steps);
         auto it = graphs.find(key);
         if (it == graphs.end()) it = graphs.emplace(key, std::array<hipGraphExec_t, 2>{nullptr, nullptr}).first;
         hipGraphExec_t& ge = it->second[(size_t)(graph_flip++ & 1)];
@@ -1171,29 +1087,10 @@ struct Solver {
     // Returns MACHIP_OK (converged: yvec, *lam, *res set), MACHIP_NOT_CONVERGED (caller falls back to
     // Lanczos) or an error.
     int solve_lob(const CsrView& A, long nnz, double lnorm, double tol, int max_steps, int start_mode,
-                  double* lam, double* res, long* iters, long* spmvs, long* restarts_out, bool jacobi = false) {
-#ifndef MACHIP_EXPERIMENTS
-        jacobi = false;
-#endif
-        lob_jacobi = jacobi;
-        lob_pan = false;
-        ST_TRY(lob_alloc(jacobi ? 0 : nnz));
-        // (explicit-check kernels may use the whole chip at large n, cf. solve_lanczos)
-        SpmvPlan pl = plan_spmv(opt, n, nnz, kAuto, jacobi && n > 32768 ? kMaxGrid : 0);
-#ifdef MACHIP_EXPERIMENTS
-        if (jacobi) {
-            pan = plan_panel(opt, n, nnz, maxlen_hint, pan_allowed && precision == 0 && !shard && !ipc, (long)csr_cap, false, false);
-            lob_pan = false; lob_pan2 = false;
-            if (pan.on && !pan.verify) {
-                ST_TRY(ensure_panel(A, nnz, pan));
-                lob_pan = true;
-                lob_pan2 = OPT(lob_pan2, 1) != 0 && pan.NB * pan.NP <= 256 && pan.grid2 <= 256 && pan.cells == 1;
-            }
-        }
-#endif
+                  double* lam, double* res, long* iters, long* spmvs, long* restarts_out) {
+        ST_TRY(lob_alloc(nnz));
+        SpmvPlan pl = plan_spmv(opt, n, nnz, kAuto);
         LobView L = lview(pl);
-        if (lob_pan) L.P_c = std::min(256, vgrid());           // partial sums come from k_pan_find's workgroups
-        if (lob_pan && lob_pan2) L.P_a = pan.grid2;            // ... ||r||_1 partials from k_lob_update_pan's (and k_lob_start's) pan.grid2 workgroups
         const int g2 = vgrid();
         const bool debug = OPT(debug, 0) != 0;
         const double scale = lnorm > 0 ? lnorm : 1.0;
@@ -1201,7 +1098,7 @@ struct Solver {
         wb_active.s = 0;
         int wb_s = 0;
         lob_escalate = false;
-        const bool wb_enabled = !jacobi && OPT(woodbury, 1) != 0 && chain_like && support_hint >= 0;
+        const bool wb_enabled = OPT(woodbury, 1) != 0 && chain_like && support_hint >= 0;
         const bool may_escalate = wb_enabled && support_hint > wb_limit_now && support_hint <= wb_hard();
         if (wb_enabled && support_hint <= wb_limit_now) {
             ST_TRY(wb_alloc());
@@ -1233,10 +1130,6 @@ struct Solver {
         // the device; gather indices in the solver's layout ----
         const double sigma = (wb_s > 0 ? 1e-8 : 2.5e-7) * scale;
         HIP_TRY(hipMemsetAsync(lx_bad, 0, sizeof(int), stream));
-#ifdef MACHIP_EXPERIMENTS
-        if (jacobi) k_jac_dinv<<<g2, kBlock, 0, stream>>>(A, lx_tdinv, lx_bad);
-        else
-#endif
         if (n > kTriMaxN) k_tri_factor_big<<<1, kTriThreads, 0, stream>>>(A, L.stride, sigma, lx_tl, lx_tdinv, lx_tcu, lx_as, lx_bs, lx_bad, chain_only);
         else {
             k_tri_band<<<g2, kBlock, 0, stream>>>(A, L.c, L.stride, lx_ba, lx_bd, lx_bu);
@@ -1250,10 +1143,8 @@ struct Solver {
             }
         }
         CsrView AT = A;
-        if (!jacobi) {
-            k_lob_perm_cols<<<(int)std::min<long>(kMaxGrid, (nnz + kBlock - 1) / kBlock), kBlock, 0, stream>>>(A.col, nnz, L.c, L.stride, lx_colT);
-            AT.col = lx_colT;
-        }
+        k_lob_perm_cols<<<(int)std::min<long>(kMaxGrid, (nnz + kBlock - 1) / kBlock), kBlock, 0, stream>>>(A.col, nnz, L.c, L.stride, lx_colT);
+        AT.col = lx_colT;
         if (wb_s > 0) {
             const int st = wb_build(L, wb_s);
             if (st != MACHIP_OK && st != MACHIP_NOT_CONVERGED) return st;
@@ -1284,12 +1175,7 @@ struct Solver {
         int best_it = 0;
         while (true) {
             ++epoch;
-#ifdef MACHIP_EXPERIMENTS
-            if (jacobi && lob_pan && lob_pan2) k_lob_start<true, true><<<pan.grid2, kBlock, 0, stream>>>(L, yvec, w2, rq_dev, it_enq, epoch);     // (same grid as k_lob_update_pan: its prologue counts gridDim partials)
-            else if (jacobi) k_lob_start<true><<<g2, kBlock, 0, stream>>>(L, yvec, w2, rq_dev, it_enq, epoch);
-            else
-#endif
-            k_lob_start<false><<<g2, kBlock, 0, stream>>>(L, yvec, w2, rq_dev, it_enq, epoch);
+            k_lob_start<<<g2, kBlock, 0, stream>>>(L, yvec, w2, rq_dev, it_enq, epoch);
             std::deque<int> pend;
             std::deque<std::pair<int, double>> hist;
             double to_go = 1e18, est = 1e300;
@@ -1303,7 +1189,6 @@ struct Solver {
                     ramp = std::min(chunk0, ramp * 2);
                     if (near) chunk = std::min(chunk, std::max(2, (int)(0.75 * to_go) + 1));
                     chunk = std::min(chunk, cap - it_enq);
-                    lob_par0 = it_enq & 1;      // (parity of the chunk's first iterate: baked into k_lob_update_pan's launches and the graph key)
                     ST_TRY(lob_enqueue_chunk(A, AT, pl, L, chunk));
                     it_enq += chunk;
                     *spmvs += chunk;
@@ -1362,253 +1247,12 @@ struct Solver {
         }
     }
 
-#ifdef MACHIP_EXPERIMENTS      // (measured: ties with the scalar recurrence on city10000 -- profiles/r5_city_block.md)
-    // ---- block Lanczos mode (blocklan.h, band.h) --------------------------------------------------------------------------------
-    static constexpr int kBlockFallback = 1001;       // internal status of solve_block: the scalar recurrence takes over
-    BRec* bZ0 = nullptr; BRec* bZ1 = nullptr;
-    double* bpart = nullptr;      // 2 x kBQ x kMaxGrid partial sums
-    double* bU0 = nullptr;        // start block, column-major n x 4
-    double* bwarm = nullptr;      // Ritz vectors 2..4 of the last block solve (n x 3): columns 1..3 of the next start block
-    double* bsdev = nullptr;      // their coefficient vectors (3 x (vcap + 2))
-    double* h_bs = nullptr;       // ... pinned staging
-    double* brec = nullptr;       // records in device memory
-    double* h_brec = nullptr; double* d_hbrec = nullptr;      // records, kBRec doubles per block step (pinned, device-mapped)
-    size_t brec_steps = 0;
-    bool blk_have_warm = false;
-    long long* bclk = nullptr;    // (probe)
-    long hist_blk_steps = -1;     // block steps of the last block solve (counts only: the mode choice stays reproducible)
-    band::Factor bfac; band::Smallest bsm; std::vector<double> bh, bguess, bwk;
-
-    int blk_G(long nnz) const { const long mean = nnz / std::max(1, n); return mean < 5 ? 2 : mean < 12 ? 4 : 8; }
-    int blk_threads(long) const { return kBlkThreads; }
-    int blk_rpb(long nnz) const { return (blk_threads(nnz) - 64) / blk_G(nnz); }
-    bool blk_fits(long nnz) const {
-        const int rpb = blk_rpb(nnz);
-        return n > 256 && (n + rpb - 1) / rpb <= kBlkMaxGrid && vcap >= 256 && precision == 0 && !shard && !ipc;
-    }
-    BlkView bview(int grid) const {
-        BlkView L; L.n = n; L.st = st; L.Z0 = bZ0; L.Z1 = bZ1; L.V = V; L.rec = brec; L.hrec = d_hbrec; L.hflag = d_hflag; L.part = bpart; L.P = grid; L.clk = bclk; L.inv_n = 1.0 / (double)n;
-        return L;
-    }
-    int blk_alloc() {
-        if (bZ0) return MACHIP_OK;
-        ST_TRY(dev_alloc(&bZ0, (size_t)n)); ST_TRY(dev_alloc(&bZ1, (size_t)n));
-        ST_TRY(dev_alloc(&bpart, (size_t)2 * kBQ * kMaxGrid));
-        ST_TRY(dev_alloc(&bU0, (size_t)n * kBW)); ST_TRY(dev_alloc(&bwarm, (size_t)n * (kBW - 1)));
-        ST_TRY(dev_alloc(&bsdev, (size_t)(kBW - 1) * (vcap + 2)));
-        brec_steps = vcap / kBW + 2;
-        ST_TRY(dev_alloc(&brec, brec_steps * kBRec));
-        HIP_TRY(hipHostMalloc((void**)&h_brec, brec_steps * kBRec * sizeof(double), hipHostMallocMapped));
-        HIP_TRY(hipHostGetDevicePointer((void**)&d_hbrec, h_brec, 0));
-        HIP_TRY(hipHostMalloc((void**)&h_bs, (size_t)(kBW - 1) * (vcap + 2) * sizeof(double), 0));
-        return MACHIP_OK;
-    }
-    void blk_launch_chunk(const CsrView& A, int G, int threads, int grid, int steps) {
-        const BlkView L = bview(grid);
-        for (int s = 0; s < steps; ++s) {
-            if (G == 2) k_blk_vec<2, kBlkThreads><<<grid, threads, 0, stream>>>(A, L, s);
-            else if (G == 4) k_blk_vec<4, kBlkThreads><<<grid, threads, 0, stream>>>(A, L, s);
-            else k_blk_vec<8, kBlkThreads><<<grid, threads, 0, stream>>>(A, L, s);
-        }
-        k_blk_tail<<<1, 64, 0, stream>>>(L, steps);
-    }
-    int blk_enqueue_chunk(const CsrView& A, int G, int threads, int grid, int steps) {
-        if (!use_graph()) { blk_launch_chunk(A, G, threads, grid, steps); HIP_TRY(hipGetLastError()); return MACHIP_OK; }
-        if (graph_csr_key != (const void*)A.val) {   // different matrix buffers: cached graphs are stale
-            for (auto& kv : graphs) for (hipGraphExec_t ge : kv.second) if (ge) (void)hipGraphExecDestroy(ge);
-            graphs.clear();
-            graph_csr_key = (const void*)A.val;
-        }
-        const auto key = std::make_tuple(9000 + G, 0, grid, threads, steps);
-        auto it = graphs.find(key);
-        if (it == graphs.end()) it = graphs.emplace(key, std::array<hipGraphExec_t, 2>{nullptr, nullptr}).first;
-        hipGraphExec_t& ge = it->second[(size_t)(graph_flip++ & 1)];
-        if (!ge) {
-            hipGraph_t g = nullptr;
-            HIP_TRY(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
-            blk_launch_chunk(A, G, threads, grid, steps);
-            HIP_TRY(hipStreamEndCapture(stream, &g));
-            HIP_TRY(hipGraphInstantiate(&ge, g, nullptr, nullptr, 0));
-            (void)hipGraphDestroy(g);
-        }
-        HIP_TRY(hipGraphLaunch(ge, stream));
-        return MACHIP_OK;
-    }
-
-    // Block Lanczos solve.  Returns MACHIP_OK (pair in yvec / *lambda2, passed the explicit check), kBlockFallback (breakdown of the
-    // block, basis full, or no convergence within the step budget: the caller continues with the scalar recurrence), or an error.
-    int solve_block(const CsrView& A, long nnz, double lnorm, double tol, int max_steps, int start_mode, double* lambda2,
-                    machip_solve_stats* stats) {
-        ST_TRY(blk_alloc());
-        if (OPT(debug, 0) == 2 && !bclk) { HIP_TRY(hipMalloc((void**)&bclk, sizeof(long long) * 16 * 256)); HIP_TRY(hipMemset(bclk, 0, sizeof(long long) * 16 * 256)); }
-        const SpmvPlan pl = plan_spmv(opt, n, nnz, 0, n > 32768 ? kMaxGrid : 0);
-        const int G = blk_G(nnz), threads = blk_threads(nnz), rpb = blk_rpb(nnz), grid = (n + rpb - 1) / rpb, g2 = vgrid();
-        const bool debug = OPT(debug, 0) != 0;
-        const double tiny_l = (lnorm > 0 ? lnorm : 1.0);
-        HIP_TRY(hipEventRecord(ev0, stream));
-        ev1_at_check = false;
-        // ---- start block: column 0 as the scalar recurrence would start, the others from the last block solve's Ritz vectors ----
-        if (start_mode == 1 && have_prev) HIP_TRY(hipMemcpyAsync(bU0, yvec, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, stream));
-        else if (have_start) HIP_TRY(hipMemcpyAsync(bU0, start, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, stream));
-        else k_fill_start<<<g2, kBlock, 0, stream>>>(bU0, n, 0x1234567ull);
-        if (blk_have_warm && start_mode == 1) HIP_TRY(hipMemcpyAsync(bU0 + (size_t)n, bwarm, sizeof(double) * (size_t)n * (kBW - 1), hipMemcpyDeviceToDevice, stream));
-        else for (int c = 1; c < kBW; ++c) k_fill_start<<<g2, kBlock, 0, stream>>>(bU0 + (size_t)c * n, n, 0x1234567ull + 0x9E37ull * (unsigned long long)c);
-        ++epoch;
-        k_blk_init<<<grid, kBlock, 0, stream>>>(bview(grid), bU0, (int)epoch);
-        HIP_TRY(hipGetLastError());
-        const int cap_steps = (int)std::min<size_t>(std::min<size_t>((vcap - 2) / kBW, brec_steps - 2), (size_t)std::max(8, (n - 1) / kBW)) & ~1;
-        const int chunk0 = std::max(2, OPT(blk_chunk, 16) & ~1), chunk_near = std::max(2, OPT(blk_chunk_near, 4) & ~1);
-        const double trigger_slack = 0.01 * OPT(trigger_pct, 110);
-        if (max_steps <= 0) max_steps = 200000;
-        std::deque<std::pair<int, int>> bp;       // (jstart, jend) of the chunks in flight
-        std::deque<std::pair<int, double>> hist;
-        int J_enq = 0, J = 0;
-        double to_go = 1e18, est_latest = 1e300, last_check_est = 1e300, theta_prev = 0.0, lam = 0.0, res = 0.0;
-        bguess.clear();
-        const double qnan = std::numeric_limits<double>::quiet_NaN();
-        const double ltarget = std::log(std::max(tol * tiny_l, 1e-300));
-        bool converged = false, fallback = false;
-        long checks = 0;
-        HIP_TRY(hipEventRecord(evs0, stream));
-        while (!converged && !fallback) {
-            const bool near = to_go < 2.0 * chunk0 || (to_go >= 1e17 && est_latest < 1e3 * tol * lnorm);
-            const int depth = near ? 1 : 2;
-            while ((int)bp.size() < depth && J_enq < cap_steps && J_enq < max_steps) {
-                int chunk = near ? chunk_near : chunk0;
-                if (near && to_go < 1e17) chunk = std::min(chunk0, std::max(chunk_near, ((int)(0.75 * to_go) + 1) & ~1));
-                chunk = std::min(chunk, cap_steps - J_enq);
-                if (chunk <= 0) break;
-                const int hi = J_enq + chunk;
-                // poison what this chunk delivers for the first time: B_j for j in (J_enq, hi] (and B_0), A_j / l1_j for j in [J_enq, hi)
-                for (int j = J_enq ? J_enq + 1 : 0; j <= hi; ++j) for (int i = 0; i < 16; ++i) h_brec[(size_t)j * kBRec + 16 + i] = qnan;
-                for (int j = J_enq; j < hi; ++j) { for (int i = 0; i < 16; ++i) h_brec[(size_t)j * kBRec + i] = qnan; for (int i = 0; i < 4; ++i) h_brec[(size_t)j * kBRec + 32 + i] = qnan; }
-                ST_TRY(blk_enqueue_chunk(A, G, threads, grid, chunk));
-                if (debug) fprintf(stderr, "[machip] block enqueue J=%d chunk=%d depth=%d\n", J_enq, chunk, depth);
-                bp.emplace_back(J_enq, hi);
-                J_enq = hi;
-            }
-            if (bp.empty()) { fallback = true; break; }
-            const std::pair<int, int> p = bp.front();
-            bp.pop_front();
-            ST_TRY(wait_flag(((unsigned long long)epoch << 32) | (unsigned long long)(unsigned int)p.second));
-            {
-                unsigned long budget = 5000000ul;
-                auto wait_slot = [&](size_t idx) { volatile double* slot = h_brec + idx; while (*slot != *slot && budget) { --budget; __builtin_ia32_pause(); } };
-                for (int j = p.first ? p.first + 1 : 0; j <= p.second && budget; ++j) for (int i = 0; i < 16; ++i) wait_slot((size_t)j * kBRec + 16 + i);
-                for (int j = p.first; j < p.second && budget; ++j) { for (int i = 0; i < 16; ++i) wait_slot((size_t)j * kBRec + i); for (int i = 0; i < 4; ++i) wait_slot((size_t)j * kBRec + 32 + i); }
-                if (!budget) { fallback = true; break; }         // (a genuine NaN: the scalar path reports it)
-            }
-            J = p.second;
-            // ---- breakdown: a vanishing pivot of some B_j ----
-            bool broke = false;
-            for (int j = 0; j <= J && !broke; ++j) for (int c = 0; c < kBW; ++c) if (!(h_brec[(size_t)j * kBRec + 16 + c * 5] > 0.0)) { broke = true; break; }
-            if (broke) { if (debug) fprintf(stderr, "[machip] block J=%d: breakdown\n", J); fallback = true; break; }
-            // ---- banded matrix of the J blocks, its smallest pair ----
-            const int N = J * kBW;
-            bh.assign((size_t)(kBW + 1) * N, 0.0);
-            for (int j = 0; j < J; ++j) {
-                const double* Aj = h_brec + (size_t)j * kBRec;
-                for (int c = 0; c < kBW; ++c) for (int r = c; r < kBW; ++r) bh[(size_t)(r - c) * N + 4 * j + c] = Aj[r * 4 + c];
-                if (j + 1 < J) {
-                    const double* Bn = h_brec + (size_t)(j + 1) * kBRec + 16;
-                    for (int r = 0; r < kBW; ++r) for (int c = r; c < kBW; ++c) bh[(size_t)(kBW + r - c) * N + 4 * j + c] = Bn[r * 4 + c];
-                }
-            }
-            band::smallest_eigpair(bh.data(), N, kBW, bguess.data(), (int)bguess.size(), theta_prev, bsm, bfac, bwk,
-                                   /*rough=*/est_latest > 1e4 * tol * lnorm);
-            bguess = bsm.s; theta_prev = bsm.theta;
-            const double* BJ = h_brec + (size_t)J * kBRec + 16;
-            const double* l1 = h_brec + (size_t)(J - 1) * kBRec + 32;
-            double est = 0.0;
-            for (int r = 0; r < kBW; ++r) {
-                double rho = 0.0;
-                for (int c = r; c < kBW; ++c) rho += BJ[r * 4 + c] * bsm.s[(size_t)N - kBW + c];
-                est += std::fabs(rho) * (l1[r] > 0 ? l1[r] : std::sqrt((double)n));
-            }
-            est_latest = est;
-            if (est > 0.0) {
-                hist.emplace_back(J, std::log(est));
-                while (hist.size() > 2 && hist[1].first <= J - 32) hist.pop_front();
-                to_go = 1e18;
-                if (hist.front().first < J) {
-                    const double slope = (hist.front().second - hist.back().second) / (double)(J - hist.front().first);
-                    if (slope > 1e-7) to_go = std::max(0.0, (hist.back().second - ltarget) / slope);
-                }
-            }
-            if (debug) fprintf(stderr, "[machip] block J=%d theta=%.15g est=%.3e to_go=%.0f pend=%zu fact=%d\n", J, bsm.theta, est / tiny_l, std::min(to_go, 1e9), bp.size(), bsm.factorisations);
-            const bool at_cap = J >= cap_steps || J >= max_steps;
-            const bool trig = est < trigger_slack * tol * lnorm;
-            if ((trig && est < 0.5 * last_check_est) || at_cap) {
-                double rq = 0.0, r1 = 0.0;
-                HIP_TRY(hipEventRecord(evs1, stream));
-                spec_likely = est < 0.01 * OPT(spec_slack_pct, 105) * tol * lnorm;
-                ST_TRY(explicit_check(A, pl, N, bsm.s.data(), &rq, &r1, false));      // syncs the stream
-                spec_likely = true;
-                ++checks;
-                last_check_est = std::max(est, 1e-300);
-                lam = rq; res = lnorm > 0 ? r1 / lnorm : r1;
-                if (debug) fprintf(stderr, "[machip]    block check J=%d rq=%.15g res=%.3e (tol %.1e)\n", J, rq, res, tol);
-                if (res < tol) { converged = true; final_check_seq = check_seq; break; }
-                if (at_cap) { fallback = true; break; }
-            }
-        }
-        if (!bp.empty()) HIP_TRY(hipStreamSynchronize(stream));
-        bp.clear();
-        if (bclk) {
-            std::vector<long long> hc(16 * 256);
-            HIP_TRY(hipMemcpy(hc.data(), bclk, sizeof(long long) * hc.size(), hipMemcpyDeviceToHost));
-            for (int b : {0, grid / 2, grid - 1}) {
-                const long long* c = hc.data() + 16 * b; const long long t0 = std::min(c[0], c[8]);
-                fprintf(stderr, "[machip] blk clocks wg %d (x10 ns from kernel start): prologue loads %lld tot %lld G %lld chol %lld Ri %lld published %lld wave0 at barrier %lld | rows start %lld gathered %lld past barrier %lld finished %lld end %lld\n", b, c[1] - t0, c[2] - t0, c[5] - t0, c[6] - t0, c[3] - t0, c[7] - t0, c[4] - t0, c[8] - t0, c[9] - t0, c[10] - t0, c[11] - t0, c[12] - t0);
-            }
-        }
-        if (fallback || !converged) {
-            if (debug) fprintf(stderr, "[machip] block mode gives up at J=%d: the scalar recurrence takes over\n", J);
-            hist_blk_steps = 1l << 40;          // (never again for this handle unless a caller forces it)
-            return kBlockFallback;
-        }
-        // ---- start block of the next solve: the Ritz vectors behind the next three Ritz values (good start vectors is all they
-        // have to be: a few sweeps of subspace iteration) ----
-        {
-            const int N = J * kBW;
-            std::vector<double> th, S;
-            band::lowest_block(bh.data(), N, kBW, kBW, bsm.theta, bsm.s.data(), th, S, bfac, 3);
-            const int KS = std::max(1, std::min(ks_max, N / 8));
-            for (int c = 1; c < kBW; ++c) memcpy(h_bs + (size_t)(c - 1) * (vcap + 2), S.data() + (size_t)c * N, sizeof(double) * (size_t)N);
-            HIP_TRY(hipMemcpyAsync(bsdev, h_bs, sizeof(double) * (size_t)(kBW - 1) * (vcap + 2), hipMemcpyHostToDevice, stream));
-            for (int c = 1; c < kBW; ++c) {
-                k_ritz_partial<<<dim3(g2, KS), kBlock, 0, stream>>>(V, n, N, bsdev + (size_t)(c - 1) * (vcap + 2), ypart);
-                k_ritz_combine<<<g2, kBlock, 0, stream>>>(ypart, n, KS, bwarm + (size_t)(c - 1) * n, part_c);
-            }
-            HIP_TRY(hipGetLastError());
-            blk_have_warm = true;
-        }
-        have_prev = true; last_was_lob = true; J_last = 0; last_seq_sharded = false; last_seq_f32 = false;
-        last_steps = J_enq; last_steps_lowp = 0; hist_blk_steps = J_enq;
-        last_mode = 9;
-        float ms = 0.f, sms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, ev0, ev1));
-        HIP_TRY(hipEventElapsedTime(&sms, evs0, evs1));
-        *lambda2 = lam;
-        if (stats) {
-            stats->lanczos_steps = J_enq; stats->spmv_total = (long)J_enq * kBW + checks; stats->vec_passes = (long)J_enq * 7 * kBW;
-            stats->restarts = 0; stats->nnz = nnz; stats->residual = res; stats->lnorm = lnorm; stats->gpu_ms = ms;
-            stats->step_ms = sms; stats->steps_timed = J_enq; stats->steps_lowp = 0;
-        }
-        if (lam < 1e-12 * tiny_l) return fail(MACHIP_DISCONNECTED, "lambda_2 ~ 0: the graph is not connected");
-        return MACHIP_OK;
-    }
-
-#endif
-
     // start_mode: 0 = stored cold-start vector (or device pseudo-random if none), 1 = previous
     // Fiedler vector (warm start).
     int solve(const CsrView& A, long nnz, double lnorm, double tol, int max_steps, int start_mode,
               int forced_variant, double* lambda2, machip_solve_stats* stats) {
         int mode = opt.is_set(kOpt_solver) ? OPT(solver, 0) : solver_mode;      // (option "solver" overrides machip_set_solver: 0 auto, 1 Lanczos, 2 preconditioned)
-#ifndef MACHIP_EXPERIMENTS
-        if (mode == 3) mode = 0;      // (3 = diagonally preconditioned LOBPCG: experiments build only)
-#endif
+        if (mode == 3) mode = 0;      // (3 was the diagonally preconditioned LOBPCG of earlier builds: automatic now)
         // auto: chain-dominated graphs with few active closures per node (measured cross-over)
         const bool eligible = n > 256 && n <= kTriBigMaxN;
         // One preconditioned iteration costs about `ratio` Lanczos steps (three launches, one of them a
@@ -1663,13 +1307,12 @@ struct Solver {
                           (mode == 2 || (mode == 0 && chain_like && support_hint >= 0 && ((sparse && !slow_lob) || stiff || exact_small || exact_big)));
         last_was_lob = false;
         final_check_seq = -2;
-        const bool want_jac = mode == 3 && n > 256;
         // No history (or one that spoke for Lanczos): start with Lanczos, but let it hand over to the exact mode once ITS OWN forecast
         // says the rest of the solve costs more than that (city10000's first iterate: forecast > 1 000 steps from step 128 on -> 0.7 ms
         // of Lanczos + 3.0 ms exact instead of 7.3 ms).  Forecasts come from device results that are bit-reproducible: so is the choice.
         bool after_switch = false;
         long pre_steps = 0;
-        if (!((eligible && want) || want_jac) && mode == 0 && eligible && chain_dominated && chain_like && !small && n <= kTriMaxN && !throughput_lane &&
+        if (!(eligible && want) && mode == 0 && eligible && chain_dominated && chain_like && !small && n <= kTriMaxN && !throughput_lane &&
             precision == 0 && forced_variant == 0 && support_hint > 0 && support_hint <= wb_soft() &&      // (sharded / inter-process solves too: every rank
             // holds the same tridiagonal records, takes the same decision at the same step, and runs the exact mode replicated)
             OPT(woodbury, 1) != 0 && OPT(exact_big, 1) != 0 && OPT(exact_switch, 1) != 0) {
@@ -1687,7 +1330,7 @@ struct Solver {
             pre_steps = last_steps;
             hist_lan_steps = last_steps + (long)std::min(switch_to_go, 1e6);     // (what the solve would have taken, by its own forecast)
         }
-        if ((eligible && want) || want_jac || after_switch) {
+        if ((eligible && want) || after_switch) {
             if (!after_switch) HIP_TRY(hipEventRecord(ev0, stream));      // (after a hand-over ev0 still marks the start of the Lanczos part)
             double lam = 0.0, res = 0.0;
             long iters = 0, spmvs = 0, rst = 0;
@@ -1695,7 +1338,7 @@ struct Solver {
             // an n x s product per application -- are kept to the cheap cases there, the tridiagonal preconditioner serves the rest and
             // a crawling solve still escalates; city10000, 9 budgets on 4 lanes: 422 -> 664 it/s, profiles/r4_exact_small.md)
             wb_limit_now = throughput_lane ? std::min(wb_soft(), OPT(wb_lane_max, 256)) : wb_soft();
-            int st = solve_lob(A, nnz, lnorm, tol, max_steps, start_mode, &lam, &res, &iters, &spmvs, &rst, want_jac);
+            int st = solve_lob(A, nnz, lnorm, tol, max_steps, start_mode, &lam, &res, &iters, &spmvs, &rst);
             if (st == MACHIP_NOT_CONVERGED && lob_escalate) {
                 long it1 = iters, sp1 = spmvs;
                 wb_limit_now = wb_hard();
@@ -1725,21 +1368,6 @@ struct Solver {
             if (st != MACHIP_NOT_CONVERGED) return st;
             // stagnated / T not positive definite: the Lanczos path takes over from its own start
         }
-#ifdef MACHIP_EXPERIMENTS
-        // Block Lanczos (blocklan.h) where the scalar recurrence has been seen to need many steps on a matrix small enough for the
-        // one-row-per-lane-group step: counts only (hist_lan_steps = steps of the last scalar solve, hist_blk_steps = block steps of
-        // the last block solve; a block step is priced at 1.5 scalar steps), so the choice is reproducible.  option blocklan: 0 never, 1 always.
-        {
-            const int bo = OPT(blocklan, 0);      // (experiments build: opt-in only)
-            const bool pmode_fits = OPT(persist, 1) != 0 && chain_like && persist_fits(n, nnz - n - 2 * chain_edges);
-            const bool auto_ok = bo < 0 && mode == 0 && !pmode_fits && forced_variant == 0 && hist_lan_steps > OPT(blocklan_min_steps, 400) &&
-                                 (hist_blk_steps < 0 || 3 * hist_blk_steps < 2 * hist_lan_steps);
-            if ((bo == 1 || auto_ok) && blk_fits(nnz) && n > 1024) {
-                const int sb = solve_block(A, nnz, lnorm, tol, max_steps, start_mode, lambda2, stats);
-                if (sb != kBlockFallback) return sb;
-            }
-        }
-#endif
         const int st = solve_lanczos(A, nnz, lnorm, tol, max_steps, start_mode, forced_variant, lambda2, stats);
         // (mixed precision: the fp32 pre-phase inflates the count by roughly a third of its length; the learning rule
         // above is calibrated on fp64 step counts)
@@ -1847,8 +1475,8 @@ struct Solver {
             }
         }
         if (pan.on) {
-            pp.variant = kPanel; pp.grid = pan.fused ? pan.NB * pan.NP : pan.grid2; pp.block = pan.fused ? kBlock : pan.block2;   // (grid = partial sums per quantity)
-            pp.width = pan.NP * 100 + pan.RPT; pp.unroll = pan.TWW; pp.defer = pan.NB + (pan.fused ? 1000 : 0) + 10000 * pan.cells + (pan.u ? 1000000 : 0);
+            pp.variant = kPanel; pp.grid = pan.grid2; pp.block = pan.block2;   // (grid = partial sums per quantity)
+            pp.width = pan.NP * 100 + pan.RPT; pp.unroll = pan.TWW; pp.defer = pan.NB + 10000 * pan.cells + (pan.u ? 1000000 : 0);
             if (pan.u) {
                 if (!pu_U0) {
                     ST_TRY(dev_alloc(&pu_U0, (size_t)n + 2)); ST_TRY(dev_alloc(&pu_U1, (size_t)n + 2)); ST_TRY(dev_alloc(&pu.W, (size_t)n));
@@ -1886,35 +1514,6 @@ struct Solver {
         const PipeView L = pview(pp);
         const int pchunk0 = std::min(kPersistMaxSteps, std::max(2, OPT(pchunk, 64)));
         const bool debug = OPT(debug, 0) != 0;
-        // ---- Chebyshev-filtered recurrence for the single-workgroup kernel (persist.h, CHEB): after a short plain
-        // sequence has produced a Ritz vector -- its Rayleigh quotient rq is a RIGOROUS upper bound of lambda_2 (unit
-        // vector orthogonal to 1) -- the solve restarts from that vector on C = -T_d(M), M mapping [a, b] onto [-1, 1] with
-        // a = 1.25 rq > lambda_2 and b = ||L||_inf >= lambda_max.  T_d(M(lambda)) decreases monotonically on [0, a] and
-        // stays within [-1, 1] beyond, so C's smallest eigenvalue on 1-perp belongs to lambda_2's eigenvector and to no
-        // other; the converged pair is checked on L itself by the same explicit test as always.
-        PersistCheb cheb;                        // deg = 0: plain recurrence
-        bool cheb_started = false;
-        double cheb_a = 0.0, cheb_b = 0.0;
-        // Measured on MI355X (tools/cheb_probe.py, bench c3 / c5a, round 3): correct on every pose-graph test, but SLOWER than
-        // the plain recurrence -- a filtered step costs 3.2 us + 0.55 us per product against 2.35 us for a plain step, and
-        // with a = 1.25 rq ~ 20 lambda_2 after 32 plain steps the filter needs 1.4-4x the products (intel 420-435 against
-        // 488 it/s, sphere2500 900-1 013 against 1 049 for degrees 8-24).  Off by default (MACHIP_CHEB_DEG=8 turns it on).
-#ifdef MACHIP_EXPERIMENTS
-        const int cheb_deg_max = OPT(cheb_deg, 0) & ~1;
-#else
-        const int cheb_deg_max = 0;
-#endif
-        const bool cheb_ok = pmode && precision == 0 && cheb_deg_max >= 2 && persist_fits_cheb(n, nnz - n - 2 * chain_edges);
-        const int cheb_after = std::max(8, OPT(cheb_after, 32));      // plain steps before the hand-over
-        const int cheb_chunk = std::max(4, OPT(cheb_chunk, 16) & ~1);  // filtered steps per launch
-        const int cheb_depth = std::max(1, OPT(cheb_depth, 2));
-        // T_d(x) and its derivative for x >= 1, and the inverse on that branch
-        auto cheb_T = [](int d, double x, double* dT) {
-            const double th = std::acosh(std::max(1.0, x));
-            const double sh = std::sqrt(std::max(0.0, x * x - 1.0));
-            if (dT) *dT = sh > 1e-8 ? d * std::sinh(d * th) / sh : (double)d * d;
-            return std::cosh(d * th);
-        };
         // ---- mixed precision (machip_set_precision(1)): the FIRST Krylov sequence stores matrix values, records and
         // basis in fp32 (inner products accumulated in fp64).  An fp32 recurrence cannot resolve lambda_2 beyond
         // ~eps_32 ||L||, so it only runs until its residual estimate reaches f32_switch ||L||_inf (or stalls); its Ritz
@@ -1960,10 +1559,6 @@ struct Solver {
                 ++epoch;
                 if (pan_u) k_pipe_init_u<<<pp.grid, kBlock, 0, stream>>>(L, pu, u, (int)epoch);
                 else k_pipe_init<<<pp.grid, kBlock, 0, stream>>>(L, u, (int)epoch);
-                if (pan.on && pan.fused) {      // (experiments build) arrival tickets / slice claims of k_pan_step count from the sequence's step 0
-                    HIP_TRY(hipMemsetAsync(panv.tick, 0, sizeof(unsigned int) * 256, stream));
-                    HIP_TRY(hipMemsetAsync(panv.claim, 0, sizeof(unsigned int) * 4096, stream));
-                }
                 if (shard && pp.variant == kVec) {       // row-partitioned sequence: every rank starts from the same records
                     seq_sharded = true; seq_plan = pp;
                     ST_TRY(shard_broadcast_init());
@@ -1978,7 +1573,7 @@ struct Solver {
             const double seq_tol = f32_seq ? f32_switch : tol;     // what this sequence's residual estimate aims for
             int J_enq = 0;        // steps enqueued in this sequence
             int prev_tailless = 0;   // step count of the last enqueued chunk if its records still wait for a successor's first step
-            const bool tail_ok = !pmode && !classic && !seq_sharded && cheb.deg == 0 && !(pan.on && pan.fused) && OPT(tailless, 1) != 0;
+            const bool tail_ok = !pmode && !classic && !seq_sharded && OPT(tailless, 1) != 0;
             int J_timed = 0;      // ... of which already accounted in step_ms
             HIP_TRY(hipEventRecord(evs0, stream));
             ha.clear(); hb.assign(1, 0.0); hl1.assign(1, 0.0);
@@ -2011,7 +1606,7 @@ struct Solver {
             // Row-partitioned sequences (every rank has to launch the same steps) and option stream = 2 feed the queue from the analyses
             // alone instead: one chunk with a tail kernel at a time, sized by the forecast once every record of its predecessor has been
             // analysed.  Same points, same rule, same final point: a partitioned solve still reproduces the single-rank one bit for bit.
-            const bool stream_mode = !pmode && !classic && cheb.deg == 0 && !(pan.on && pan.fused) && !f32_seq && OPT(stream, 1) != 0;
+            const bool stream_mode = !pmode && !classic && !f32_seq && OPT(stream, 1) != 0;
             const bool feed_chunks = seq_sharded || OPT(stream, 1) == 2 || OPT(tailless, 1) == 0;
             if (stream_mode) {
                 const double trig_s = 0.01 * OPT(stream_trigger_pct, 95);      // (the estimate predicts the measured residual to +/- 5 %: profiles/r5_c4_checks.txt)
@@ -2215,8 +1810,7 @@ struct Solver {
                 const bool near = sched ? (to_go < near_factor * chunk0 || (to_go >= 1e17 && est_latest < 1e3 * seq_tol * lnorm))
                                         : est_latest < 1e3 * seq_tol * lnorm;
                 const bool use_classic = classic && !pmode;
-                int depth = (use_classic || near) ? 1 : ((sched && to_go > 8.0 * chunk0) ? 3 : 2);
-                if (cheb.deg) depth = (to_go < 3.0 * cheb_chunk * cheb.deg) ? 1 : std::min(2, cheb_depth);     // (chunks are ~80 us: little to hide, much to overshoot)
+                const int depth = (use_classic || near) ? 1 : ((sched && to_go > 8.0 * chunk0) ? 3 : 2);
                 while ((int)pend.size() < depth && J_enq < jcap && steps_total < max_steps) {
                     // (the O(J) host analysis must keep up with the GPU: longer chunks once J is large -- a function of
                     // J only, so the step count at which convergence is noticed stays reproducible)
@@ -2226,11 +1820,6 @@ struct Solver {
                     if (pmode) {   // steps cost ~0.5 us here: long chunks, so the O(J) host analysis keeps up
                         chunk = pchunk0;
                         if (to_go < 1e17) chunk = std::min(pchunk0, std::max(16, ((int)(0.9 * to_go) + 1) & ~1));
-                        if (cheb_ok && cheb.deg == 0 && restarts == 0 && J_enq < cheb_after) chunk = std::min(chunk, cheb_after - J_enq);   // decide after a short plain sequence
-                        if (cheb.deg) {      // a filtered step is cheb.deg products (~5 us): short chunks, to_go counts products there
-                            chunk = std::min(chunk, cheb_chunk);
-                            if (to_go < 1e17) chunk = std::max(4, std::min(chunk, (int)(0.9 * to_go / cheb.deg) + 2) & ~1);
-                        }
                     }
                     if (use_classic) chunk = std::min(chunk, 16);
                     chunk = std::min(chunk, jcap - J_enq);
@@ -2244,7 +1833,7 @@ struct Solver {
                         for (int j = J_enq; j < hi; ++j) { h_tri[3 * (size_t)j] = qnan; h_tri[3 * (size_t)j + 2] = qnan; }   // alpha_j, l1_j
                     }
                     if (pmode) {
-                        launch_persist(A, chunk, f32_seq, cheb);
+                        launch_persist(A, chunk, f32_seq);
                         HIP_TRY(hipGetLastError());   // (157 KB of static LDS: a refused launch must surface, not time out)
                     } else if (classic) {
                         enqueue_classic(A, pl, chunk);
@@ -2272,7 +1861,7 @@ struct Solver {
                     }
                     pend.push_back(p);
                     J_enq = hi;
-                    steps_total += chunk; spmv_total += cheb.deg ? (long)chunk * cheb.deg : chunk;
+                    steps_total += chunk; spmv_total += chunk;
                     steps_used += chunk;
                     if (f32_seq) steps_lowp += chunk;
                 }
@@ -2326,9 +1915,8 @@ struct Solver {
                 // ---- breakdown: beta_j ~ 0 means span(v_0..v_{j-1}) is invariant ----
                 int Jeff = J;
                 bool broke = false;
-                const double bscale = cheb.deg ? 1.0 : tiny_l;         // (the filtered operator's spectrum is O(1))
                 for (int j = std::max(1, Jold); j <= J; ++j) {
-                    if (!(hb[(size_t)j] > 1e-13 * bscale)) { Jeff = j; broke = true; break; }
+                    if (!(hb[(size_t)j] > 1e-13 * tiny_l)) { Jeff = j; broke = true; break; }
                 }
                 // ---- host: smallest Ritz pair of T_Jeff ----
                 tri::smallest_eigpair(ha.data(), hb.data(), Jeff, guess.data(), (int)guess.size(), theta_prev, sm, wk);
@@ -2336,16 +1924,7 @@ struct Solver {
                 theta_prev = sm.theta;
                 const double rho = broke ? 0.0 : std::fabs(hb[(size_t)Jeff] * sm.s[(size_t)Jeff - 1]);
                 const double l1v = hl1[(size_t)Jeff - 1] > 0 ? hl1[(size_t)Jeff - 1] : std::sqrt((double)n);
-                double est = rho * l1v;   // predicted ||r||_1 (r = rho v_J; ||v_J||_1 ~ ||v_{J-1}||_1)
-                if (cheb.deg) {
-                    // residual of C = -p(L) -> residual of L: (C + p(lambda)) y ~ -p'(lambda) (L - lambda) y near an eigenpair,
-                    // lambda from the Ritz value through the inverse of p on [0, a]
-                    const double pv = -sm.theta;                                   // p(lambda-hat)
-                    double x = 1.0, dT = (double)cheb.deg * cheb.deg;
-                    if (pv > 1.0) { x = std::cosh(std::acosh(pv) / cheb.deg); (void)cheb_T(cheb.deg, x, &dT); }
-                    const double dp = dT * 2.0 / (cheb_b - cheb_a);                 // |p'(lambda-hat)| (>= its value at a)
-                    est /= dp;
-                }
+                const double est = rho * l1v;   // predicted ||r||_1 (r = rho v_J; ||v_J||_1 ~ ||v_{J-1}||_1)
                 est_latest = est;
                 if (!broke && est > 0.0) {
                     hist.emplace_back(J, std::log(est));
@@ -2353,12 +1932,12 @@ struct Solver {
                     to_go = 1e18;
                     if (hist.front().first < J) {
                         const double slope = (hist.front().second - hist.back().second) / (double)(J - hist.front().first);
-                        if (slope > 1e-7) to_go = std::max(0.0, (hist.back().second - ltarget) / slope) * (cheb.deg ? cheb.deg : 1);
+                        if (slope > 1e-7) to_go = std::max(0.0, (hist.back().second - ltarget) / slope);
                     }
                 }
                 const bool at_cap = (J >= jcap) || (steps_total >= max_steps && pend.empty());
                 const bool trig = broke || est < trigger_slack * seq_tol * lnorm;
-                if (switch_est_us > 0.0 && restarts == 0 && !f32_seq && cheb.deg == 0 && !broke && !trig && !at_cap && J >= 128 && to_go < 1e17 &&
+                if (switch_est_us > 0.0 && restarts == 0 && !f32_seq && !broke && !trig && !at_cap && J >= 128 && to_go < 1e17 &&
                     to_go * (4.2 + 2e-6 * (double)nnz) > 1.3 * switch_est_us) {
                     if (++switch_votes >= 2) {
                         if (debug) fprintf(stderr, "[machip]    J=%d: forecast %.0f steps to go -- handing over to the exact chain + closures mode (estimate %.0f us)\n", J, to_go, switch_est_us);
@@ -2367,13 +1946,10 @@ struct Solver {
                 } else switch_votes = 0;
 
                 if (debug) fprintf(stderr, "[machip] %s J=%d Jeff=%d theta=%.15g est=%.3e to_go=%.0f broke=%d pend=%zu passes=%d\n", pmode ? "persist" : (classic ? "classic" : "pipe"), J, Jeff, sm.theta, lnorm > 0 ? est / lnorm : est, std::min(to_go, 1e9), (int)broke, pend.size(), sm.passes);
-                bool handover = false;
-                if (cheb_ok && cheb.deg == 0 && restarts == 0 && !trig && !broke && !at_cap && J >= cheb_after &&
-                    (to_go > 4.0 * cheb_after || to_go >= 1e17)) handover = true;     // far from done: the filtered recurrence pays
-                if ((trig && est < 0.5 * last_check_est) || broke || at_cap || handover) {
+                if ((trig && est < 0.5 * last_check_est) || broke || at_cap) {
                     double rq = 0.0, r1 = 0.0;
                     HIP_TRY(hipEventRecord(evs1, stream));   // everything enqueued so far = steps [J_timed, J_enq)
-                    spec_likely = !f32_seq && !handover && est < 0.01 * OPT(spec_slack_pct, 105) * seq_tol * lnorm;
+                    spec_likely = !f32_seq && est < 0.01 * OPT(spec_slack_pct, 105) * seq_tol * lnorm;
                     ST_TRY(explicit_check(A, pl, Jeff, sm.s.data(), &rq, &r1, f32_seq));   // syncs the stream
                     spec_likely = true;
                     {
@@ -2390,18 +1966,6 @@ struct Solver {
                     res = lnorm > 0 ? r1 / lnorm : r1;
                     if (debug) fprintf(stderr, "[machip]    check J=%d rq=%.15g res=%.3e (tol %.1e)\n", Jeff, rq, res, tol);
                     if (res < tol) { converged = true; status = MACHIP_OK; final_check_seq = check_seq; break; }
-                    if (handover) {
-                        // rq = Rayleigh quotient of the unit Ritz vector (orthogonal to 1) >= lambda_2
-                        cheb_a = 1.25 * rq; cheb_b = 1.0001 * tiny_l;
-                        int d = cheb_deg_max;
-                        if (cheb_a > 0.0 && cheb_b > 4.0 * cheb_a) d = std::min(d, 2 * (int)(0.25 * std::sqrt(cheb_b / cheb_a)));
-                        else d = 0;
-                        if (d >= 2) {
-                            cheb.deg = d; cheb.c1 = 2.0 / (cheb_b - cheb_a); cheb.c0 = (cheb_b + cheb_a) / (cheb_b - cheb_a);
-                            if (debug) fprintf(stderr, "[machip]    hand-over to the filtered recurrence: a=%.6g b=%.6g deg=%d\n", cheb_a, cheb_b, d);
-                            need_restart = true; break;
-                        }
-                    }
                     if (broke || at_cap || f32_seq) { need_restart = true; break; }   // fp32 sequence: one check, then fp64
                 }
             }
@@ -2420,7 +1984,6 @@ struct Solver {
             if (steps_total >= max_steps) break;
             // restart from the best Ritz vector found so far (it sits normalised in yvec)
             HIP_TRY(hipMemcpyAsync(u, yvec, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, stream));
-            if (cheb.deg && !cheb_started) { cheb_started = true; continue; }   // the planned hand-over to the filtered recurrence
             if (f32_seq) {
                 f32_seq = false;   // the planned hand-over to fp64, not counted as a restart
                 // a start vector this good makes the pipelined beta a difference of nearly equal terms (it would report

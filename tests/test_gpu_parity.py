@@ -648,7 +648,7 @@ def test_teacher_forced_config4_all_twenty_iterates(form):
     gather step forced onto every iterate; and the panel step in the MIXED mode (machip_set_precision(1), BASELINE configs[4]'s technique at the one
     config whose step is bound by bytes): fp64 tile values until the residual estimate is below 3e-4 ||L||, their fp32 copy (6 bytes per entry
     instead of 10) from 32 steps behind that point on -- same stop rule on the fp64 matrix, lambda_2 to 1e-8 on every iterate.  (The one-launch panel step and the diagonally preconditioned LOBPCG forms of round 4
-    -- measured slower, profiles/r4_c4_one_launch_step.md -- are compiled only with -DMACHIP_EXPERIMENTS and no longer tested here.)"""
+    -- measured slower, profiles/r4_c4_one_launch_step.md -- have been removed from the library.)"""
     import bench
     w = bench.make_workload("c4")
     gv = load_golden("er100k_arpack")
@@ -1240,7 +1240,7 @@ def test_solver_variants_agree(opts):
     sizes, the classic two-kernel form and a basis so small that it forces restarts must all give the
     reference's lambda_2.  The variants are entries of the handle's option table (machip_set_option; creation-time ones
     -- asm_g, vcap -- as process defaults around the handle's creation): no environment, no subprocess.  (Round 4's
-    one-launch panel step and diagonally preconditioned LOBPCG forms are compiled with -DMACHIP_EXPERIMENTS only.)"""
+    one-launch panel step and diagonally preconditioned LOBPCG forms have been removed from the library.)"""
     for nm in ["er2000_xfrac", "er300_x0"]:
         g = load_golden(nm)
         with _lib.default_options(**opts):

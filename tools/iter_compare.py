@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Per Frank-Wolfe iteration: eigen-solver steps / iterations and device ms, for the solver modes given (MACHIP_SOLVER values).
-usage: iter_compare.py <config> <iters> mode [mode ...]   (modes may carry env settings: jacobi:MACHIP_PANEL=1)"""
+usage: iter_compare.py <config> <iters> mode [mode ...]   (modes may carry env settings: lobpcg:MACHIP_LOB_CHUNK=8)"""
 import os, subprocess, sys, json
 if len(sys.argv) > 1 and sys.argv[1] == "--child":
     sys.path.insert(0, "."); import bench
