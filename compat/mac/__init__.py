@@ -14,9 +14,10 @@ GreedyESP is provided as ``from mac.solvers import GreedyESP`` (``mac_amd/solver
 module path ``mac.solvers.greedy_esp`` is not: ``mac.solvers`` is the ``mac_amd.solvers`` package object, so a module of that
 name there would answer the reference's import line, which stays an ImportError -- a script written against the reference
 changes that one line (examples/g2o_experiment.py: ``from mac.solvers.greedy_esp import GreedyESP`` ->
-``from mac.solvers import GreedyESP``).  The other baselines (``greedy_eig``, ``mac.utils.cholesky``: SURVEY section 8, out of
-scope) are not provided: importing them raises ImportError, as it does in the reference without its optional SuiteSparse
-dependency.
+``from mac.solvers import GreedyESP``).  GreedyEig is provided both ways, ``from mac.solvers import GreedyEig`` and the
+reference's own ``from mac.solvers.greedy_eig import GreedyEig`` (``mac_amd/solvers/greedy_eig.py``, on the GPU).
+``mac.utils.cholesky`` (the reference's CHOLMOD wrapper) is not provided: importing it raises ImportError, as it does in the
+reference without its optional SuiteSparse dependency.
 """
 import importlib
 import sys
@@ -25,6 +26,7 @@ _ALIASES = {
     "mac.solvers": "mac_amd.solvers",
     "mac.solvers.mac": "mac_amd.solvers.mac",
     "mac.solvers.baseline": "mac_amd.solvers.baseline",
+    "mac.solvers.greedy_eig": "mac_amd.solvers.greedy_eig",
     "mac.utils": "mac_amd.utils",
     "mac.utils.graphs": "mac_amd.utils.graphs",
     "mac.utils.fiedler": "mac_amd.utils.fiedler",

@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define MACHIP_ABI_VERSION 7   /* 7: GreedyESP handle (machip_esp_*); 6: machip_solve_stats.drift, machip_panel_plan fills 12 entries; 5: per-handle option table (machip_set_option), machip_comm_drop_ipc; 4: inter-process communicator */
+#define MACHIP_ABI_VERSION 8   /* 8: GreedyEig handle (machip_eig_*); 7: GreedyESP handle (machip_esp_*); 6: machip_solve_stats.drift, machip_panel_plan fills 12 entries; 5: per-handle option table (machip_set_option), machip_comm_drop_ipc; 4: inter-process communicator */
 
 typedef enum machip_status {
     MACHIP_OK = 0,
@@ -372,6 +372,30 @@ int machip_esp_select(machip_esp* h, int nb, const int64_t* ks, int32_t* order_o
 int machip_esp_weighted_resistances(machip_esp* h, double* r_out);
 /* info4 = {form (0 chain, 1 dense inverse), leading dimension of Sigma, fold, updates pending since the last fold}; beta. */
 int machip_esp_info(machip_esp* h, int32_t* info4, double* beta);
+
+/* GreedyEig (mac/solvers/greedy_eig.py of the reference: the greedy k-edge selection by algebraic connectivity; mac_amd/csrc/eig.h).
+ * Every pick evaluates lambda_2(L_cur + w_e a_e a_e^T) for the unselected candidates whose supergradient bound
+ * u_e = lambda_2 + w_e (v_i - v_j)^2 is not below a value already established, in batches that share the dense inverse of the
+ * reduced Laplacian (the state of machip_esp), and takes the best by the reference's scan (candidate-index order, a candidate
+ * replaces the running best only if it exceeds it by more than 1e-8).  Every reported lambda_2 satisfies the stop rule
+ * ||L_e v - lambda v||_1 / ||L_e||_inf < 1e-8 (||v||_2 = 1), evaluated with the sparse Laplacian.  The fixed graph must be connected
+ * (MACHIP_DISCONNECTED otherwise); size limits and flags as machip_esp_create. */
+typedef struct machip_eig machip_eig;
+/* fold: as machip_esp_create (0 = 16); batch: columns solved together (1..4096; 0 = 512).  Builds Sigma0 and the fixed graph's Fiedler pair. */
+int machip_eig_create(int device, int64_t n, int64_t n_fixed, const int32_t* fi, const int32_t* fj, const double* fw,
+                      int64_t m, const int32_t* ci, const int32_t* cj, const double* cw, int fold, int batch, int flags, machip_eig** out);
+void machip_eig_destroy(machip_eig* h);
+/* One greedy run from the fixed graph, k picks (1 <= k <= m): order_out[k] = candidate indices in pick order, lambda2_out[k] =
+ * lambda_2 after each pick, t_ms_out[k] = wall time from the start of the run until each pick was made.  Any output may be NULL. */
+int machip_eig_select(machip_eig* h, int64_t k, int32_t* order_out, double* lambda2_out, double* t_ms_out);
+/* lambda_2(L_cur + e) of every candidate (m doubles; NaN for the selected), L_cur = the fixed graph plus the last run's picks. */
+int machip_eig_candidate_lambda2(machip_eig* h, double* out);
+/* the bounds u_e (m doubles; NaN for the selected) from the current Fiedler pair. */
+int machip_eig_candidate_bounds(machip_eig* h, double* out);
+/* info6 = {form (0 chain, 1 dense inverse), leading dimension of Sigma, fold, batch, pending updates, picks of the last run};
+ * beta_lambda2 = {beta (always 0), current lambda_2}; per pick of the last run (at most cap entries): candidates solved exactly and
+ * operator applications (summed over the columns). */
+int machip_eig_info(machip_eig* h, int32_t* info6, double* beta_lambda2, int64_t cap, int32_t* solved_out, int32_t* applies_out);
 
 #ifdef __cplusplus
 }

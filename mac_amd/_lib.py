@@ -106,6 +106,13 @@ SIGNATURES = {
     "machip_esp_select": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int64), _i32p, _f64p, _f64p]),
     "machip_esp_weighted_resistances": (C.c_int, [C.c_void_p, _f64p]),
     "machip_esp_info": (C.c_int, [C.c_void_p, _i32p, C.POINTER(C.c_double)]),
+    "machip_eig_create": (C.c_int, [C.c_int, C.c_int64, C.c_int64, _i32p, _i32p, _f64p, C.c_int64, _i32p, _i32p, _f64p,
+                                    C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+    "machip_eig_destroy": (None, [C.c_void_p]),
+    "machip_eig_select": (C.c_int, [C.c_void_p, C.c_int64, _i32p, _f64p, _f64p]),
+    "machip_eig_candidate_lambda2": (C.c_int, [C.c_void_p, _f64p]),
+    "machip_eig_candidate_bounds": (C.c_int, [C.c_void_p, _f64p]),
+    "machip_eig_info": (C.c_int, [C.c_void_p, _i32p, _f64p, C.c_int64, _i32p, _i32p]),
 }
 
 
@@ -508,6 +515,67 @@ class Esp:
         b = C.c_double()
         check(self._lib.machip_esp_info(self._h, p_i32(a), C.byref(b)))
         return dict(form="chain" if a[0] == 0 else "dense", ld=int(a[1]), fold=int(a[2]), pending=int(a[3]), beta=b.value)
+
+
+class Eig:
+    """Owns one ``machip_eig`` handle: GreedyEig's state on one GPU -- the dense inverse of the reduced Laplacian (shared with
+    GreedyESP's machinery) and the batched Fiedler solves against it (mac_amd/csrc/eig.h)."""
+
+    def __init__(self, n, fi, fj, fw, ci, cj, cw, fold=16, batch=512, dense_inverse=False, device=0):
+        lib = load()
+        require_device()
+        self.n = int(n)
+        fi, fj, fw = i32(fi), i32(fj), f64(fw)
+        ci, cj, cw = i32(ci), i32(cj), f64(cw)
+        self.m = int(len(cw))
+        h = C.c_void_p()
+        check(lib.machip_eig_create(int(device), self.n, len(fw), p_i32(fi), p_i32(fj), p_f64(fw), self.m,
+                                    p_i32(ci), p_i32(cj), p_f64(cw), int(fold), int(batch),
+                                    ESP_DENSE_INVERSE if dense_inverse else 0, C.byref(h)))
+        self._h = h
+        self._lib = lib
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.machip_eig_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def select(self, k):
+        """One greedy run of k picks: (order int32[k], lambda2 float64[k], t_ms float64[k])."""
+        k = int(k)
+        order = np.empty(max(k, 1), dtype=np.int32)
+        lam = np.empty(max(k, 1))
+        t = np.empty(max(k, 1))
+        check(self._lib.machip_eig_select(self._h, k, p_i32(order), p_f64(lam), p_f64(t)))
+        return order[:k], lam[:k], t[:k]
+
+    def candidate_lambda2(self):
+        out = np.empty(max(self.m, 1))
+        check(self._lib.machip_eig_candidate_lambda2(self._h, p_f64(out)))
+        return out[:self.m]
+
+    def candidate_bounds(self):
+        out = np.empty(max(self.m, 1))
+        check(self._lib.machip_eig_candidate_bounds(self._h, p_f64(out)))
+        return out[:self.m]
+
+    def info(self):
+        """dict(form, ld, fold, batch, pending, beta, lambda2, solved[picks], applications[picks])."""
+        a = np.zeros(6, dtype=np.int32)
+        b = np.zeros(2)
+        check(self._lib.machip_eig_info(self._h, p_i32(a), p_f64(b), 0, None, None))
+        k = int(a[5])
+        solved = np.zeros(max(k, 1), dtype=np.int32)
+        applies = np.zeros(max(k, 1), dtype=np.int32)
+        check(self._lib.machip_eig_info(self._h, p_i32(a), p_f64(b), k, p_i32(solved), p_i32(applies)))
+        return dict(form="chain" if a[0] == 0 else "dense", ld=int(a[1]), fold=int(a[2]), batch=int(a[3]), pending=int(a[4]),
+                    beta=float(b[0]), lambda2=float(b[1]), solved=solved[:k].copy(), applications=applies[:k].copy())
 
 
 class _stdout_to_stderr:

@@ -133,27 +133,32 @@ __global__ __launch_bounds__(kBlock) void k_esp_argmax(EspView V, int P) {
     }
 }
 
-// ---- z = Sigma a_{e*} = S[u,:] - S[v,:] - sum_{b<j} alpha_b Zb[:,b],  alpha_b = c_b (Zb[u,b] - Zb[v,b]);  into Zb[:,j].
-// grid = ceil(ld / 256) (rows n'..ld get 0: the fold reads whole tiles).  Workgroup 0 records the step. ----
+// ---- z = Sigma a_e = S[u,:] - S[v,:] - sum_{b<j} alpha_b Zb[:,b],  alpha_b = c_b (Zb[u,b] - Zb[v,b])  (shared with eig.h) ----
+// the alphas of the j pending columns into LDS (the caller synchronises before esp_z_entry)
+__device__ __forceinline__ void esp_z_alpha(const EspView& V, int u, int v, int j, double* alpha) {
+    for (int b = threadIdx.x; b < j; b += kBlock) {
+        const double* zc = V.Zb + (size_t)b * V.ld;
+        alpha[b] = V.cb[b] * ((u >= 0 ? zc[u] : 0.0) - (v >= 0 ? zc[v] : 0.0));
+    }
+}
+// entry i of z (0 for the padding rows n'..ld: the fold reads whole tiles)
+__device__ __forceinline__ double esp_z_entry(const EspView& V, const double* __restrict__ S, int u, int v, int j, const double* alpha, int i) {
+    if (i >= V.np) return 0.0;
+    const size_t ld = V.ld;
+    double z = (u >= 0 ? S[(size_t)u * ld + i] : 0.0) - (v >= 0 ? S[(size_t)v * ld + i] : 0.0);
+    for (int b = 0; b < j; ++b) z = __builtin_fma(-alpha[b], V.Zb[(size_t)b * ld + i], z);
+    return z;
+}
+
+// ---- the z of the step's winner into Zb[:,j].  grid = ceil(ld / 256).  Workgroup 0 records the step. ----
 __global__ __launch_bounds__(kBlock) void k_esp_z(EspView V, const double* __restrict__ S, int j, int k) {
     __shared__ double alpha[kEspMaxFold];
     const int e = V.best->idx;
     const int u = V.cu[e], v = V.cv[e];
-    const size_t ld = V.ld;
-    for (int b = threadIdx.x; b < j; b += kBlock) {
-        const double* zc = V.Zb + (size_t)b * ld;
-        alpha[b] = V.cb[b] * ((u >= 0 ? zc[u] : 0.0) - (v >= 0 ? zc[v] : 0.0));
-    }
+    esp_z_alpha(V, u, v, j, alpha);
     __syncthreads();
     const int i = blockIdx.x * kBlock + threadIdx.x;
-    if (i < V.ld) {
-        double z = 0.0;
-        if (i < V.np) {
-            z = (u >= 0 ? S[(size_t)u * ld + i] : 0.0) - (v >= 0 ? S[(size_t)v * ld + i] : 0.0);
-            for (int b = 0; b < j; ++b) z = __builtin_fma(-alpha[b], V.Zb[(size_t)b * ld + i], z);
-        }
-        V.Zb[(size_t)j * ld + i] = z;
-    }
+    if (i < V.ld) V.Zb[(size_t)j * V.ld + i] = esp_z_entry(V, S, u, v, j, alpha, i);
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         const double sstar = V.best->val;
         V.cb[j] = V.cw[e] / (1.0 + sstar);

@@ -17,6 +17,7 @@
 
 #include "solver.h"
 #include "esp.h"
+#include "eig.h"
 
 namespace machip {
 thread_local std::string g_err;
@@ -1779,6 +1780,93 @@ int machip_esp_weighted_resistances(machip_esp* h, double* r_out) {
         HIP_TRY(hipMemcpyAsync(r_out, h->s, sizeof(double) * (size_t)h->m, hipMemcpyDeviceToHost, h->stream));
     }
     HIP_TRY(hipStreamSynchronize(h->stream));
+    return MACHIP_OK;
+}
+
+// ---- GreedyEig (eig.h) ----
+
+int machip_eig_create(int device, int64_t n, int64_t n_fixed, const int32_t* fi, const int32_t* fj, const double* fw,
+                      int64_t m, const int32_t* ci, const int32_t* cj, const double* cw, int fold, int batch, int flags, machip_eig** out) {
+    if (!out) return fail(MACHIP_BAD_ARG, "out is NULL");
+    *out = nullptr;
+    if (fold == 0) fold = kEigDefaultFold;
+    if (batch == 0) batch = kEigDefaultBatch;
+    if (batch < 1 || batch > kEigMaxBatch) return fail(MACHIP_BAD_ARG, "batch must be in [1, 4096]");
+    machip_esp* base = nullptr;
+    ST_TRY(machip_esp_create(device, n, n_fixed, fi, fj, fw, m, ci, cj, cw, fold, flags, &base));
+    if (base->beta != 0.0) {
+        machip_esp_destroy(base);
+        return fail(MACHIP_DISCONNECTED, "GreedyEig needs a connected fixed graph (lambda_2 of the fixed graph is 0 otherwise)");
+    }
+    machip_eig* h = new machip_eig();
+    h->base = base; h->n = (int)n; h->m = (int)m; h->batch = batch;
+    h->ldq = (batch + kGjT - 1) / kGjT * kGjT;
+    h->ldv = ((int)n + kGjT - 1) / kGjT * kGjT;
+    h->adj0.assign((size_t)n, {}); h->hdeg0.assign((size_t)n, 0.0);
+    for (int64_t e = 0; e < n_fixed; ++e) {
+        if (fi[e] == fj[e]) continue;
+        h->adj0[(size_t)fi[e]].emplace_back(fj[e], fw[e]); h->adj0[(size_t)fj[e]].emplace_back(fi[e], fw[e]);
+        h->hdeg0[(size_t)fi[e]] += fw[e]; h->hdeg0[(size_t)fj[e]] += fw[e];
+    }
+    h->hci.assign(ci, ci + m); h->hcj.assign(cj, cj + m); h->hcw.assign(cw, cw + m);
+    h->sel.assign((size_t)m, 0);
+    auto body = [&]() -> int {
+        ST_TRY(h->alloc());
+        h->adj = h->adj0; h->hdeg = h->hdeg0;
+        ST_TRY(h->upload_graph());
+        HIP_TRY(hipMemcpyAsync(base->sig, base->sig0, sizeof(double) * (size_t)base->ld * (size_t)base->ld, hipMemcpyDeviceToDevice, base->stream));
+        base->pending = 0;
+        ST_TRY(h->first_pair());
+        return h->reset();
+    };
+    const int st = body();
+    if (st != MACHIP_OK) { machip_eig_destroy(h); return st; }
+    *out = h;
+    return MACHIP_OK;
+}
+
+void machip_eig_destroy(machip_eig* h) {
+    if (!h) return;
+    (void)hipSetDevice(h->base->device);
+    if (h->base->stream) (void)hipStreamSynchronize(h->base->stream);
+    h->release();
+    machip_esp_destroy(h->base);
+    delete h;
+}
+
+int machip_eig_select(machip_eig* h, int64_t k, int32_t* order_out, double* lambda2_out, double* t_ms_out) {
+    if (!h || k < 1) return fail(MACHIP_BAD_ARG, "NULL handle or k < 1");
+    if (k > h->m) return fail(MACHIP_BAD_ARG, "not enough candidate edges to satisfy the budget");
+    HIP_TRY(hipSetDevice(h->base->device));
+    return h->select((int)k, order_out, lambda2_out, t_ms_out);
+}
+
+int machip_eig_candidate_lambda2(machip_eig* h, double* out) {
+    if (!h || (!out && h->m)) return fail(MACHIP_BAD_ARG, "NULL handle or output");
+    HIP_TRY(hipSetDevice(h->base->device));
+    return h->all_lambda2(out);
+}
+
+int machip_eig_candidate_bounds(machip_eig* h, double* out) {
+    if (!h || (!out && h->m)) return fail(MACHIP_BAD_ARG, "NULL handle or output");
+    HIP_TRY(hipSetDevice(h->base->device));
+    std::vector<double> u;
+    ST_TRY(h->bounds(u));
+    for (int e = 0; e < h->m; ++e) out[e] = h->sel[(size_t)e] ? NAN : u[(size_t)e];
+    return MACHIP_OK;
+}
+
+int machip_eig_info(machip_eig* h, int32_t* info6, double* beta_lambda2, int64_t cap, int32_t* solved_out, int32_t* applies_out) {
+    if (!h) return fail(MACHIP_BAD_ARG, "NULL handle");
+    if (info6) {
+        info6[0] = h->base->form; info6[1] = h->base->ld; info6[2] = h->base->fold; info6[3] = h->batch; info6[4] = h->base->pending;
+        info6[5] = (int)h->solved.size();
+    }
+    if (beta_lambda2) { beta_lambda2[0] = h->base->beta; beta_lambda2[1] = h->lamcur; }
+    for (int64_t i = 0; i < cap && i < (int64_t)h->solved.size(); ++i) {
+        if (solved_out) solved_out[i] = h->solved[(size_t)i];
+        if (applies_out) applies_out[i] = h->applies[(size_t)i];
+    }
     return MACHIP_OK;
 }
 

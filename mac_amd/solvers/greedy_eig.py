@@ -1,0 +1,92 @@
+"""GreedyEig: greedy k-edge selection by algebraic connectivity, the third baseline MAC is compared against -- same public
+surface as the reference class (mac/solvers/greedy_eig.py), hot path on the MI355X (mac_amd/csrc/eig.h).
+
+Each of the k picks adds the candidate e that maximises lambda_2(L_cur + w_e a_e a_e^T).  A candidate whose supergradient bound
+u_e = lambda_2 + w_e (v_i - v_j)^2 (v the current unit Fiedler vector) is below a value already established in the pick cannot
+win and is not solved; the others are solved exactly (stop rule ||L_e v - lambda v||_1 / ||L_e||_inf < 1e-8), and the pick is the
+reference's scan over them: candidate-index order, a candidate replaces the running best only if it exceeds it by more than
+1e-8.  The reference re-factors by Cholesky up- and down-dates, one candidate after the other; here the dense inverse of the
+reduced Laplacian is resident on the GPU (the state GreedyESP keeps) and a batch of candidates is one dense fp64 matrix product
+per solver iteration.
+
+The fixed (odometry) graph must be connected: the reference factors L_odom with one diagonal entry pinned and no
+regularisation, which only means anything for a connected odometry graph; a disconnected one raises ``Disconnected`` here.
+Size limits as GreedyESP: 32 768 poses when the fixed edges are exactly the chain (i, i+1), 16 384 otherwise.
+"""
+from __future__ import annotations
+
+from typing import List, Optional, Tuple
+
+import numpy as np
+
+from mac_amd import _lib
+from mac_amd.utils import fiedler as _fiedler
+from mac_amd.utils.graphs import Edge, edges_to_arrays, weight_graph_lap_from_edge_list, weight_graph_lap_from_edges
+
+
+class GreedyEig:
+    def __init__(self, odom_measurements: List[Edge], lc_measurements: List[Edge], num_poses: int, *, device: int = 0,
+                 batch: int = 512, fold: int = 16, dense_inverse: bool = False):
+        """Arguments as mac/solvers/greedy_eig.py of the reference, plus keyword-only ``device`` (GPU ordinal), ``batch``
+        (candidates solved together, 1..4096), ``fold`` (picks kept as a low-rank block before they are folded into the
+        inverse, 1..256) and ``dense_inverse`` (build the inverse by dense Gauss-Jordan even for a chain: cross-checks).
+        Raises Disconnected when the fixed graph is not connected."""
+        self.L_odom = weight_graph_lap_from_edge_list(odom_measurements, num_poses)
+        self.num_poses = num_poses
+        self.odom_measurements = odom_measurements
+        self.lc_measurements = lc_measurements
+        ci, cj, cw = edges_to_arrays(lc_measurements)
+        self.weights = cw
+        self.edge_list = np.stack([ci, cj], axis=1).astype(np.int64).reshape(-1, 2)
+        fi, fj, fw = edges_to_arrays(odom_measurements)
+        self._dev = _lib.Eig(num_poses, fi, fj, fw, ci, cj, cw, fold=fold, batch=batch, dense_inverse=dense_inverse, device=device)
+        self.last_lambda2: Optional[np.ndarray] = None      # lambda_2 after every pick of the last run
+        self.last_times: Optional[np.ndarray] = None        # seconds from the start of the last run until each pick
+
+    # ---- the reference's helpers ----
+    def find_fiedler_pair(self, L, method="tracemin_lu", tol=1e-8):
+        """(lambda_2(L), v_2(L)) by mac_amd.utils.fiedler.find_fiedler_pair."""
+        lam, v, _ = _fiedler.find_fiedler_pair(L, method=method, tol=tol)
+        return lam, v
+
+    def combined_laplacian(self, w, tol=1e-10):
+        """L(w): the fixed edges plus the candidates weighted by w (entries of w not above ``tol`` are dropped)."""
+        w = np.asarray(w, dtype=np.float64)
+        idx = np.nonzero(w > tol)[0]
+        return self.L_odom + weight_graph_lap_from_edges(self.edge_list[idx], w[idx] * self.weights[idx], self.num_poses)
+
+    def grad_from_fiedler(self, fiedler_vec):
+        """Supergradient of lambda_2 with respect to w: w_e (v_i - v_j)^2 per candidate."""
+        v = np.asarray(fiedler_vec, dtype=np.float64)
+        d = v[self.edge_list[:, 0]] - v[self.edge_list[:, 1]]
+        return self.weights * d * d
+
+    # ---- selection ----
+    def subset(self, k: int, save_intermediate: bool = False) -> Tuple[np.ndarray, List[Edge]]:
+        """(solution 0/1 array of length m, the picked edges in pick order).  ``save_intermediate`` is accepted for the
+        reference's signature (the reference ignores it as well)."""
+        m = len(self.weights)
+        solution = np.zeros(m)
+        if k == 0:
+            self.last_lambda2 = np.zeros(0)
+            self.last_times = np.zeros(0)
+            return solution, []
+        assert 0 < k <= m, "not enough candidate edges to satisfy the budget"
+        order, lam, t_ms = self._dev.select(k)
+        self.last_lambda2 = lam
+        self.last_times = t_ms / 1e3
+        solution[order] = 1.0
+        return solution, [Edge(int(self.edge_list[e, 0]), int(self.edge_list[e, 1]), float(self.weights[e])) for e in order]
+
+    def candidate_lambda2(self) -> np.ndarray:
+        """lambda_2(L_cur + e) of every candidate (NaN for the selected), L_cur = the fixed graph plus the last run's picks."""
+        return self._dev.candidate_lambda2()
+
+    def candidate_bounds(self) -> np.ndarray:
+        """u_e = lambda_2 + w_e (v_i - v_j)^2 from the current Fiedler pair (NaN for the selected)."""
+        return self._dev.candidate_bounds()
+
+    def info(self) -> dict:
+        """form ("chain" / "dense"), ld, fold, batch, pending, beta, lambda2 (current), and per pick of the last run:
+        ``solved`` (candidates solved exactly) and ``applications`` (operator applications summed over the columns)."""
+        return self._dev.info()
