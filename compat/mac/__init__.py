@@ -16,6 +16,8 @@ name there would answer the reference's import line, which stays an ImportError 
 changes that one line (examples/g2o_experiment.py: ``from mac.solvers.greedy_esp import GreedyESP`` ->
 ``from mac.solvers import GreedyESP``).  GreedyEig is provided both ways, ``from mac.solvers import GreedyEig`` and the
 reference's own ``from mac.solvers.greedy_eig import GreedyEig`` (``mac_amd/solvers/greedy_eig.py``, on the GPU).
+ESPRelaxation (no counterpart in the reference: the convex relaxation GreedyESP's paper pairs the greedy with) is
+``from mac.solvers import ESPRelaxation`` (``mac_amd/solvers/esp_relax.py``).
 ``mac.utils.cholesky`` (the reference's CHOLMOD wrapper) is not provided: importing it raises ImportError, as it does in the
 reference without its optional SuiteSparse dependency.
 """
@@ -27,6 +29,7 @@ _ALIASES = {
     "mac.solvers.mac": "mac_amd.solvers.mac",
     "mac.solvers.baseline": "mac_amd.solvers.baseline",
     "mac.solvers.greedy_eig": "mac_amd.solvers.greedy_eig",
+    "mac.solvers.esp_relax": "mac_amd.solvers.esp_relax",
     "mac.utils": "mac_amd.utils",
     "mac.utils.graphs": "mac_amd.utils.graphs",
     "mac.utils.fiedler": "mac_amd.utils.fiedler",

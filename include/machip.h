@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define MACHIP_ABI_VERSION 8   /* 8: GreedyEig handle (machip_eig_*); 7: GreedyESP handle (machip_esp_*); 6: machip_solve_stats.drift, machip_panel_plan fills 12 entries; 5: per-handle option table (machip_set_option), machip_comm_drop_ipc; 4: inter-process communicator */
+#define MACHIP_ABI_VERSION 9   /* 9: the relaxation of GreedyESP's problem (machip_esp_relax_*); 8: GreedyEig handle (machip_eig_*); 7: GreedyESP handle (machip_esp_*); 6: machip_solve_stats.drift, machip_panel_plan fills 12 entries; 5: per-handle option table (machip_set_option), machip_comm_drop_ipc; 4: inter-process communicator */
 
 typedef enum machip_status {
     MACHIP_OK = 0,
@@ -372,6 +372,31 @@ int machip_esp_select(machip_esp* h, int nb, const int64_t* ks, int32_t* order_o
 int machip_esp_weighted_resistances(machip_esp* h, double* r_out);
 /* info4 = {form (0 chain, 1 dense inverse), leading dimension of Sigma, fold, updates pending since the last fold}; beta. */
 int machip_esp_info(machip_esp* h, int32_t* info4, double* beta);
+
+/* The convex relaxation of GreedyESP's problem on the same handle (mac_amd/csrc/esp_relax.h).  For x in [0, 1]^m:
+ *     M(x) = L_red + beta I + sum_e x_e w_e a_e a_e^T,   F(x) = log det M(x) - log det M(0)   (nats; F(0) = 0 exactly; for a 0/1 x
+ *     the sum of log(1 + gain) over its edges in machip_esp_select's convention),   dF/dx_e = w_e a_e^T M(x)^-1 a_e.
+ * F is concave: F(x) + dF(x).(s - x), s the top-k vertex of dF(x) (ties at the k-th value: lowest indices, as machip_lp_topk),
+ * is an upper bound on F over {x in [0, 1]^m, sum x <= k}, so on every k-edge selection.  Every evaluation assembles the dense
+ * M(x), inverts it by the blocked Gauss-Jordan elimination and takes log det from the same elimination's pivots; results are
+ * bit-identical from run to run.  The chain closed form does not apply to M(x): n <= 16384 whatever the fixed edges are,
+ * MACHIP_BAD_ARG beyond.  The first relaxation call on a handle allocates a third ld x ld buffer (Sigma0 stays untouched:
+ * machip_esp_select afterwards returns what it returns on a fresh handle) and evaluates log det M(0).  A relaxation call
+ * overwrites the working copy of the last selection run: machip_esp_weighted_resistances then refers to the fixed graph again.
+ * x outside [0, 1] or not finite, k <= 0, k > m: MACHIP_BAD_ARG (machip_last_error says which). */
+/* F(x) and, when grad_out is not NULL, the gradient (m doubles). */
+int machip_esp_relax_eval(machip_esp* h, const double* x, double* F_out, double* grad_out);
+/* Frank-Wolfe from x_inout with the open-loop step 2 / (2 + t), t = 0, 1, ...: per iteration F, the dual value F + g.(s - x)
+ * and |g|_2 (f_traj / dual_traj / gnorm_traj, max_iters entries each, any may be NULL); *upper_out = the smallest dual value
+ * seen.  Stops after the iteration at which |g|_2 < grad_tol or (upper - F) < gap_tol |F| (the iterate is then the one the test
+ * was evaluated at, not yet moved), or after max_iters.  x_inout returns the last iterate, *iters_out the iterations evaluated. */
+int machip_esp_relax_run(machip_esp* h, int64_t k, int max_iters, double gap_tol, double grad_tol, double* x_inout,
+                         double* f_traj, double* dual_traj, double* gnorm_traj, int* iters_out, double* upper_out);
+/* *out = sum_e a_e b_e (m doubles each, host), summed on the device in exactly the order machip_esp_relax_run sums g.(s - x): a
+ * Frank-Wolfe driver on the host that evaluates F and the gradient with machip_esp_relax_eval and forms the dual value as
+ * F + inner(g, s - x) reproduces machip_esp_relax_run's dual values, and with them its upper bound, bit for bit (a host dot
+ * product sums in another order and agrees to rounding only). */
+int machip_esp_relax_inner(machip_esp* h, const double* a, const double* b, double* out);
 
 /* GreedyEig (mac/solvers/greedy_eig.py of the reference: the greedy k-edge selection by algebraic connectivity; mac_amd/csrc/eig.h).
  * Every pick evaluates lambda_2(L_cur + w_e a_e a_e^T) for the unselected candidates whose supergradient bound

@@ -106,6 +106,10 @@ SIGNATURES = {
     "machip_esp_select": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int64), _i32p, _f64p, _f64p]),
     "machip_esp_weighted_resistances": (C.c_int, [C.c_void_p, _f64p]),
     "machip_esp_info": (C.c_int, [C.c_void_p, _i32p, C.POINTER(C.c_double)]),
+    "machip_esp_relax_eval": (C.c_int, [C.c_void_p, _f64p, C.POINTER(C.c_double), _f64p]),
+    "machip_esp_relax_run": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_double, C.c_double, _f64p, _f64p, _f64p, _f64p,
+                                       C.POINTER(C.c_int), C.POINTER(C.c_double)]),
+    "machip_esp_relax_inner": (C.c_int, [C.c_void_p, _f64p, _f64p, C.POINTER(C.c_double)]),
     "machip_eig_create": (C.c_int, [C.c_int, C.c_int64, C.c_int64, _i32p, _i32p, _f64p, C.c_int64, _i32p, _i32p, _f64p,
                                     C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "machip_eig_destroy": (None, [C.c_void_p]),
@@ -515,6 +519,35 @@ class Esp:
         b = C.c_double()
         check(self._lib.machip_esp_info(self._h, p_i32(a), C.byref(b)))
         return dict(form="chain" if a[0] == 0 else "dense", ld=int(a[1]), fold=int(a[2]), pending=int(a[3]), beta=b.value)
+
+    def relax_eval(self, x, want_grad=True):
+        """(F(x), gradient or None) of the relaxation: F = logdet M(x) - logdet M(0) (machip_esp_relax_eval)."""
+        x = f64(x)
+        assert len(x) == self.m, f"x has {len(x)} entries, the handle {self.m} candidates"
+        F = C.c_double()
+        g = np.empty(max(self.m, 1)) if want_grad else None
+        check(self._lib.machip_esp_relax_eval(self._h, p_f64(x), C.byref(F), p_f64(g) if want_grad else None))
+        return F.value, (g[:self.m] if want_grad else None)
+
+    def relax_run(self, k, x_init, max_iters=20, gap_tol=1e-4, grad_tol=1e-8):
+        """Frank-Wolfe on the relaxation from x_init (machip_esp_relax_run): dict(x, upper, iters, f, dual, gnorm)."""
+        x = np.array(x_init, dtype=np.float64)          # (a copy: the call writes the last iterate into it)
+        assert len(x) == self.m, f"x has {len(x)} entries, the handle {self.m} candidates"
+        n = max(int(max_iters), 1)
+        f, dual, gn = np.empty(n), np.empty(n), np.empty(n)
+        iters, upper = C.c_int(0), C.c_double(0.0)
+        check(self._lib.machip_esp_relax_run(self._h, int(k), int(max_iters), float(gap_tol), float(grad_tol), p_f64(x),
+                                             p_f64(f), p_f64(dual), p_f64(gn), C.byref(iters), C.byref(upper)))
+        i = iters.value
+        return dict(x=x, upper=upper.value, iters=i, f=f[:i], dual=dual[:i], gnorm=gn[:i])
+
+    def relax_inner(self, a, b):
+        """a . b summed on the device in the order relax_run sums g.(s - x) (machip_esp_relax_inner)."""
+        a, b = f64(a), f64(b)
+        assert len(a) == self.m and len(b) == self.m, f"vectors of {len(a)} and {len(b)} entries, the handle {self.m} candidates"
+        out = C.c_double()
+        check(self._lib.machip_esp_relax_inner(self._h, p_f64(a), p_f64(b), C.byref(out)))
+        return out.value
 
 
 class Eig:

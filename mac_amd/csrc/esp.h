@@ -226,6 +226,8 @@ __global__ __launch_bounds__(256) void k_esp_fold(double* __restrict__ S, const 
             for (int q = 0; q < 4; ++q) S[(size_t)(r0 + 16 * bi + lk + 4 * q) * ld + c0 + 16 * bj + li] = acc[bi][bj][q];
 }
 
+struct EspRelax;      // esp_relax.h: the state of the convex relaxation, made by the first relaxation call
+
 }  // namespace machip
 
 // ---- the handle (include/machip.h: machip_esp) ----
@@ -244,6 +246,9 @@ struct machip_esp {
     double *cw = nullptr, *s = nullptr, *Zb = nullptr, *cb = nullptr, *pv = nullptr, *gain = nullptr, *piv = nullptr;
     machip::EspBest* best = nullptr;
     std::vector<hipEvent_t> ev;
+    std::vector<int32_t> hfi, hfj, hci, hcj;      // the edge lists as given (host): esp_relax.h builds its incidence list from them
+    std::vector<double> hfw, hcw;
+    machip::EspRelax* rx = nullptr;
 
     machip::EspView view() const {
         machip::EspView V;
@@ -252,6 +257,23 @@ struct machip_esp {
         return V;
     }
     int grid_m() const { return std::max(1, std::min(machip::kEspGrid, (m + machip::kBlock - 1) / machip::kBlock)); }
+
+    // A^-1 of the ld x ld matrix in `src`: ld / 32 blocked Gauss-Jordan steps on the matrix cores, ping-pong between src and dst,
+    // look-ahead pivot blocks from 1 024 rows on -- exactly as solver.h inverts the capacitance matrix (woodbury.h).  The result
+    // is in `src` afterwards (the pointers are swapped per step); *bad <- 1 on a non-positive pivot.  LD: the pivot blocks'
+    // log-determinants into ldet[ld / 32] as well.
+    template <bool LD>
+    void gj_inverse(double*& src, double*& dst, double* ldet = nullptr) {
+        using namespace machip;
+        const int tiles = ld / kGjT;
+        const bool look = ld >= kEspGjLookMin;
+        for (int kb = 0, k = 0; kb < ld; kb += kGjB, ++k) {
+            if (look) k_gj_step<0, LD><<<dim3(tiles, tiles), 256, 0, stream>>>(src, dst, ld, kb, bad, k ? piv + (size_t)(k & 1) * kGjB * kGjB : nullptr,
+                                                                               piv + (size_t)((k + 1) & 1) * kGjB * kGjB, ldet);
+            else k_gj_step<0, LD><<<dim3(tiles, tiles), 256, 0, stream>>>(src, dst, ld, kb, bad, nullptr, nullptr, ldet);
+            std::swap(src, dst);
+        }
+    }
 
     // Sigma <- Sigma - Zb diag(c) Zb^T over the j pending columns
     void fold_into(double* S, int j) {

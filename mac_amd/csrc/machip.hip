@@ -17,6 +17,7 @@
 
 #include "solver.h"
 #include "esp.h"
+#include "esp_relax.h"
 #include "eig.h"
 
 namespace machip {
@@ -1610,6 +1611,8 @@ int machip_esp_create(int device, int64_t n, int64_t n_fixed, const int32_t* fi,
     machip_esp* h = new machip_esp();
     h->device = device; h->n = N; h->np = np; h->m = (int)m; h->fold = fold; h->beta = beta; h->form = chain ? 0 : 1;
     h->ld = (np + kGjT - 1) / kGjT * kGjT;
+    h->hfi.assign(fi, fi + n_fixed); h->hfj.assign(fj, fj + n_fixed); h->hfw.assign(fw, fw + n_fixed);
+    h->hci.assign(ci, ci + m); h->hcj.assign(cj, cj + m); h->hcw.assign(cw, cw + m);
     auto body = [&]() -> int {
         HIP_TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
         const size_t ld = (size_t)h->ld, ms = (size_t)std::max<int64_t>(m, 1);
@@ -1676,17 +1679,9 @@ int machip_esp_create(int device, int64_t n, int64_t n_fixed, const int32_t* fi,
         HIP_TRY(hipMemcpyAsync(dval, val.data(), sizeof(double) * val.size(), hipMemcpyHostToDevice, h->stream));
         const int cnt = (int)pos.size();
         k_esp_scatter<<<std::max(1, std::min(kMaxGrid, (cnt + kBlock - 1) / kBlock)), kBlock, 0, h->stream>>>(h->bufA, dpos, dval, cnt);
-        // (L_red + beta I)^-1: ld / 32 blocked Gauss-Jordan steps on the matrix cores, ping-pong between the two buffers, look-ahead
-        // pivot blocks from 1 024 rows on -- exactly as solver.h inverts the capacitance matrix (woodbury.h)
-        const int tiles = (int)ld / kGjT;
+        // (L_red + beta I)^-1 by the blocked Gauss-Jordan elimination (esp.h: gj_inverse)
         double *src = h->bufA, *dst = h->bufB;
-        const bool look = (int)ld >= kEspGjLookMin;
-        for (int kb = 0, k = 0; kb < (int)ld; kb += kGjB, ++k) {
-            if (look) k_gj_step<0><<<dim3(tiles, tiles), 256, 0, h->stream>>>(src, dst, (int)ld, kb, h->bad, k ? h->piv + (size_t)(k & 1) * kGjB * kGjB : nullptr,
-                                                                               h->piv + (size_t)((k + 1) & 1) * kGjB * kGjB);
-            else k_gj_step<0><<<dim3(tiles, tiles), 256, 0, h->stream>>>(src, dst, (int)ld, kb, h->bad);
-            std::swap(src, dst);
-        }
+        h->gj_inverse<false>(src, dst);
         HIP_TRY(hipGetLastError());
         int hbad = 0;
         HIP_TRY(hipMemcpyAsync(&hbad, h->bad, sizeof(int), hipMemcpyDeviceToHost, h->stream));
@@ -1707,6 +1702,7 @@ void machip_esp_destroy(machip_esp* h) {
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     for (hipEvent_t e : h->ev) (void)hipEventDestroy(e);
+    esp_relax_release(h);
     void* bufs[] = {h->bufA, h->bufB, h->cu, h->cv, h->sel, h->pi, h->order, h->bad, h->cw, h->s, h->Zb, h->cb, h->pv, h->gain, h->piv, h->best};
     for (void* q : bufs) if (q) (void)hipFree(q);
     if (h->stream) (void)hipStreamDestroy(h->stream);
@@ -1779,6 +1775,77 @@ int machip_esp_weighted_resistances(machip_esp* h, double* r_out) {
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpyAsync(r_out, h->s, sizeof(double) * (size_t)h->m, hipMemcpyDeviceToHost, h->stream));
     }
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    return MACHIP_OK;
+}
+
+// ---- the relaxation of GreedyESP's problem (esp_relax.h) ----
+
+int machip_esp_relax_eval(machip_esp* h, const double* x, double* F_out, double* grad_out) {
+    if (!h || !F_out) return fail(MACHIP_BAD_ARG, "NULL handle or F_out");
+    ST_TRY(esp_relax_check_x(h, x));
+    ST_TRY(esp_relax_prepare(h));
+    EspRelax* r = h->rx;
+    if (h->m) HIP_TRY(hipMemcpyAsync(r->xa, x, sizeof(double) * (size_t)h->m, hipMemcpyHostToDevice, h->stream));
+    ST_TRY(esp_relax_eval_on(h, r->xa, grad_out != nullptr));
+    if (grad_out && h->m) HIP_TRY(hipMemcpyAsync(grad_out, h->s, sizeof(double) * (size_t)h->m, hipMemcpyDeviceToHost, h->stream));
+    double s3[3];
+    ST_TRY(esp_relax_read(h, 0, s3));
+    *F_out = s3[0];
+    return MACHIP_OK;
+}
+
+int machip_esp_relax_run(machip_esp* h, int64_t k, int max_iters, double gap_tol, double grad_tol, double* x_inout,
+                         double* f_traj, double* dual_traj, double* gnorm_traj, int* iters_out, double* upper_out) {
+    if (!h || !iters_out || !upper_out || max_iters < 0) return fail(MACHIP_BAD_ARG, "NULL handle or output, or max_iters < 0");
+    *iters_out = 0;
+    *upper_out = INFINITY;
+    if (h->n > kEspDenseMaxN) return esp_relax_prepare(h);      // (the limit's message, nothing allocated)
+    if (k <= 0 || k > h->m) return fail(MACHIP_BAD_ARG, "k must be in [1, m] (m = " + std::to_string(h->m) + " candidates)");
+    ST_TRY(esp_relax_check_x(h, x_inout));
+    ST_TRY(esp_relax_prepare(h));
+    EspRelax* r = h->rx;
+    hipStream_t st = h->stream;
+    const size_t mb = sizeof(double) * (size_t)h->m;
+    const int grid = std::max(1, std::min(kMaxGrid, (h->m + kBlock - 1) / kBlock));
+    HIP_TRY(hipMemcpyAsync(r->xa, x_inout, mb, hipMemcpyHostToDevice, st));
+    double u = INFINITY;
+    for (int it = 0; it < max_iters; ++it) {
+        const double gamma = 2.0 / ((double)it + 2.0);
+        ST_TRY(esp_relax_eval_on(h, r->xa, true));
+        ST_TRY(esp_relax_select(h, (long)k));
+        k_fw_final<<<grid, kBlock, 0, st>>>(h->s, r->xa, h->m, r->st, gamma, r->xb, nullptr, r->part);
+        double s3[3];
+        ST_TRY(esp_relax_read(h, grid, s3));
+        u = std::min(u, s3[1]);
+        if (f_traj) f_traj[it] = s3[0];
+        if (dual_traj) dual_traj[it] = s3[1];
+        if (gnorm_traj) gnorm_traj[it] = s3[2];
+        *iters_out = it + 1;
+        *upper_out = u;
+        if (s3[2] < grad_tol) break;                                  // (x stays the iterate the test was evaluated at)
+        if ((u - s3[0]) < gap_tol * std::fabs(s3[0])) break;          // (F >= 0; at F = 0 the test cannot fire)
+        std::swap(r->xa, r->xb);
+    }
+    HIP_TRY(hipMemcpyAsync(x_inout, r->xa, mb, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return MACHIP_OK;
+}
+
+int machip_esp_relax_inner(machip_esp* h, const double* a, const double* b, double* out) {
+    if (!h || !out || (h->m && (!a || !b))) return fail(MACHIP_BAD_ARG, "NULL handle, vector or output");
+    ST_TRY(esp_relax_prepare(h));
+    EspRelax* r = h->rx;
+    const size_t mb = sizeof(double) * (size_t)h->m;
+    const int grid = std::max(1, std::min(kMaxGrid, (h->m + kBlock - 1) / kBlock));      // (the grid of k_fw_final in machip_esp_relax_run)
+    if (h->m) {
+        HIP_TRY(hipMemcpyAsync(r->xa, a, mb, hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(hipMemcpyAsync(r->xb, b, mb, hipMemcpyHostToDevice, h->stream));
+    }
+    k_relax_inner<<<grid, kBlock, 0, h->stream>>>(r->xa, r->xb, h->m, r->part);
+    k_relax_scalars<<<1, kBlock, 0, h->stream>>>(r->ldet, h->ld / kGjB, r->logdet0, r->part, grid, r->scal);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(out, r->scal + 3, sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     return MACHIP_OK;
 }

@@ -143,8 +143,12 @@ typedef double gj_d4 __attribute__((ext_vector_type(4)));
 // Per pivot p only row p and column p travel: their owners park them in LDS (rowp[32], colp[32]), every lane reads the 4 + 4 entries
 // its sub-block needs (a wave's LDS traffic is ordered: no barrier), 16 multiply-adds per lane.  (First build: all 256 threads on an LDS
 // copy, one barrier per pivot -- 0.53 us per pivot, 17 of the kernel's 28 us.)  Returns 1 on a non-positive pivot.
-__device__ __forceinline__ int gj_invert_block(double (&m)[4][4], double* rowp, double* colp, int br, int bc) {
+// LD: also *logdet = sum_p log(pivot_p), p = 0..31 in this order (every lane the same value) -- the log-determinant of the block,
+// since the scalar pivots of the elimination are the block's own Schur complements (esp_relax.h; LD = false keeps the code).
+template <bool LD = false>
+__device__ __forceinline__ int gj_invert_block(double (&m)[4][4], double* rowp, double* colp, int br, int bc, double* logdet = nullptr) {
     int bad = 0;
+    double lsum = 0.0;
     for (int pb = 0; pb < kGjB / 4; ++pb) {
 #pragma unroll
         for (int pj = 0; pj < 4; ++pj) {
@@ -167,6 +171,7 @@ __device__ __forceinline__ int gj_invert_block(double (&m)[4][4], double* rowp, 
 #pragma unroll
             for (int i = 0; i < 4; ++i) cp[i] = colp[4 * br + i];
             if (!(piv > 0.0) || !(piv < 1e300)) bad = 1;
+            if (LD) lsum += log(piv);
             double ip = __builtin_amdgcn_rcp(piv);     // hardware reciprocal + two Newton steps (no IEEE division on the chain)
             ip = ip * __builtin_fma(-piv, ip, 2.0);
             ip = ip * __builtin_fma(-piv, ip, 2.0);
@@ -194,12 +199,17 @@ __device__ __forceinline__ int gj_invert_block(double (&m)[4][4], double* rowp, 
             __builtin_amdgcn_wave_barrier();          // (everybody has read row / column p before the next pivot's owners overwrite them)
         }
     }
+    if (LD) *logdet = lsum;
     return bad;
 }
 
-template <int VAR = 0>     // (VAR != 0: timing builds of tools/ubench_gj.hip -- 1: no pivot-block inversion, 2: nor the products)
+// LD (esp_relax.h): the log-determinant of every pivot block the elimination inverts goes into ldet[block] (written once, by the
+// lane that owns it: workgroup (0, 0) for a block inverted in front of the products, the look-ahead workgroup for the next one);
+// their sum over the ld / 32 steps is log det A.  LD = false: `ldet` is not touched and the code is the one it was.
+template <int VAR = 0, bool LD = false>     // (VAR != 0: timing builds of tools/ubench_gj.hip -- 1: no pivot-block inversion, 2: nor the products)
 __global__ __launch_bounds__(256) void k_gj_step(const double* __restrict__ src, double* __restrict__ dst, int ld, int kb, int* bad,
-                                                 const double* __restrict__ pin = nullptr, double* __restrict__ pout = nullptr) {
+                                                 const double* __restrict__ pin = nullptr, double* __restrict__ pout = nullptr,
+                                                 double* __restrict__ ldet = nullptr) {
     __shared__ double sP[2][kGjB][kGjB + 1];
     __shared__ double sA[kGjT][kGjB + 1];      // A_iK: rows of the tile x pivot columns
     __shared__ double sT[kGjT][kGjB + 1];      // -(A_iK P); rows inside the pivot block: P
@@ -262,7 +272,9 @@ __global__ __launch_bounds__(256) void k_gj_step(const double* __restrict__ src,
     // their owners park them in LDS, every lane reads the 4 + 4 entries its sub-block needs (a wave's LDS traffic is ordered:
     // no barrier), 16 multiply-adds per lane. ----
     int isbad = 0;
-    if (wv == 0 && !VAR && !pin) isbad = gj_invert_block(m, &sP[1][0][0], &sP[1][0][0] + kGjB, br, bc);     // (scratch: sP[1] is otherwise unused)
+    double lsum = 0.0;
+    if (wv == 0 && !VAR && !pin) isbad = gj_invert_block<LD>(m, &sP[1][0][0], &sP[1][0][0] + kGjB, br, bc, &lsum);     // (scratch: sP[1] is otherwise unused)
+    if (LD && wv == 0 && !VAR && !pin && lane == 0 && blockIdx.x == 0 && blockIdx.y == 0) ldet[kb / kGjB] = lsum;
     if (wv == 0) {
 #pragma unroll
         for (int i = 0; i < 4; ++i)
@@ -334,7 +346,8 @@ __global__ __launch_bounds__(256) void k_gj_step(const double* __restrict__ src,
             for (int i = 0; i < 4; ++i)
 #pragma unroll
                 for (int j = 0; j < 4; ++j) m[i][j] = stage[4 * br + i][4 * bc + j];
-            if (gj_invert_block(m, &sP[1][0][0], &sP[1][0][0] + kGjB, br, bc) && lane == 0) *bad = 1;
+            if (gj_invert_block<LD>(m, &sP[1][0][0], &sP[1][0][0] + kGjB, br, bc, &lsum) && lane == 0) *bad = 1;
+            if (LD && lane == 0) ldet[kn / kGjB] = lsum;
 #pragma unroll
             for (int i = 0; i < 4; ++i)
 #pragma unroll

@@ -3,7 +3,9 @@
 Same call signature and semantics as the reference driver (mac/optimization/frankwolfe.py:10-79):
 ``problem(x) -> (value, supergradient)``, ``solve_lp(g) -> argmax_{s in C} <g, s>``, open-loop step
 2/(k+2) unless ``stepsize`` is given.  Both callables are plug-in points, so a device-resident
-problem slots in unchanged; ``MAC.solve`` itself runs the fused device loop (machip_fw_step),
+problem slots in unchanged; ``inner`` (extension, optional) replaces the NumPy dot product of the
+dual value <g, s - x> -- a device-resident problem that sums it in its own fixed order
+(``ESPRelaxation.inner``) then reproduces its own device loop bit for bit; ``MAC.solve`` itself runs the fused device loop (machip_fw_step),
 which applies exactly these rules.
 """
 import numpy as np
@@ -20,7 +22,7 @@ def _report(verbose, text):
 
 
 def frank_wolfe(initial, problem, solve_lp, stepsize=None, maxiter=50,
-                relative_duality_gap_tol=1e-5, grad_norm_tol=1e-10, verbose=False):
+                relative_duality_gap_tol=1e-5, grad_norm_tol=1e-10, verbose=False, inner=None):
     """Returns ``(x, upper)``: the last iterate and the tightest dual bound
     ``min_k f(x_k) + <g_k, s_k - x_k>`` seen.  When a stop test fires, the iterate returned is the
     one the test was evaluated at (not yet moved), as in the reference."""
@@ -29,7 +31,8 @@ def frank_wolfe(initial, problem, solve_lp, stepsize=None, maxiter=50,
     for it in range(maxiter):
         value, grad = problem(iterate)
         vertex = solve_lp(grad)
-        upper = min(upper, value + grad @ (vertex - iterate))      # bound from the pre-update point
+        gap = grad @ (vertex - iterate) if inner is None else inner(grad, vertex - iterate)
+        upper = min(upper, value + gap)                            # bound from the pre-update point
         if np.linalg.norm(grad) < grad_norm_tol:
             _report(verbose, f"frank_wolfe: |g| below {grad_norm_tol:g} at iteration {it}, stationary point")
             return iterate, upper

@@ -1,0 +1,78 @@
+"""ESPRelaxation: the convex relaxation of the k-edge tree-count problem GreedyESP is the greedy for (Khosoussi et al.,
+arXiv:1604.01116), solved by Frank-Wolfe on the MI355X (mac_amd/csrc/esp_relax.h).
+
+With node 0 pinned and x in [0, 1]^m, sum x <= k:
+
+    M(x) = L_red(fixed) + beta I + sum_e x_e w_e a_e a_e^T,     F(x) = logdet M(x) - logdet M(0)     (growth in nats)
+
+F is concave and dF/dx_e is the weighted effective resistance of e in the graph weighted by x, so the dual value
+F(x) + <dF(x), s - x> (s the top-k vertex of the gradient) bounds the growth of EVERY k-edge selection from above: what
+``MAC.solve`` returns for lambda_2, for the tree count.  ``evaluate_objective`` scores any solver's 0/1 selection under this
+objective (for a greedy selection it equals ``sum(log1p(GreedyESP.last_gains))``).  The reference has no such solver; the
+surface follows ``MAC``: ``solve`` returns the same triple and takes the same shortcut at k >= m.
+"""
+from __future__ import annotations
+
+from typing import List
+
+import numpy as np
+
+from mac_amd import _lib
+from mac_amd.utils.graphs import Edge, edges_to_arrays
+from mac_amd.utils.rounding import round_madow, round_nearest
+
+
+class ESPRelaxation:
+    def __init__(self, fixed_edges: List[Edge], candidate_edges: List[Edge], num_nodes: int, *, device: int = 0):
+        """Arguments as GreedyESP.  The fixed graph may be disconnected as long as every node other than 0 has a fixed edge
+        (beta = 1e-4 then, as in GreedyESP); num_nodes <= 16384 (the dense M(x) is inverted per evaluation)."""
+        self.fixed_edges = fixed_edges
+        self.all_candidate_edges = candidate_edges
+        self.num_nodes = num_nodes
+        fi, fj, fw = edges_to_arrays(fixed_edges)
+        ci, cj, cw = edges_to_arrays(candidate_edges)
+        self.weights = cw
+        self._dev = _lib.Esp(num_nodes, fi, fj, fw, ci, cj, cw, device=device)
+        self.trace = []          # [(F, running upper bound, ||g||_2)] per iteration of the last solve
+
+    def evaluate_objective(self, x) -> float:
+        """F(x): the growth of the log tree count over the fixed graph, in nats (F(0) = 0)."""
+        return self._dev.relax_eval(np.asarray(x, dtype=np.float64), want_grad=False)[0]
+
+    def problem(self, x):
+        """(F(x), gradient): the callable ``mac_amd.optimization.frankwolfe.frank_wolfe`` takes."""
+        return self._dev.relax_eval(np.asarray(x, dtype=np.float64), want_grad=True)
+
+    def inner(self, a, b) -> float:
+        """<a, b> summed on the device in the order ``solve`` sums <gradient, s - x>: passed to ``frank_wolfe`` as ``inner``,
+        the driver's dual values -- and its upper bound -- are those of ``solve`` bit for bit."""
+        return self._dev.relax_inner(np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64))
+
+    def solve(self, k, x_init, rounding="nearest", max_iters=20, relative_duality_gap_tol=1e-4, grad_norm_tol=1e-8,
+              random_rounding_max_iters=1, verbose=False):
+        """Frank-Wolfe (open-loop step 2 / (2 + t)) from ``x_init``, then rounding: ``(rounded, unrounded, upper)`` with
+        ``upper`` >= F of every k-edge selection.  The loop runs on the C side (machip_esp_relax_run)."""
+        m = len(self.weights)
+        if k >= m:
+            result = np.ones(m)
+            return result, result, self.evaluate_objective(result)
+        assert len(x_init) == m
+        r = self._dev.relax_run(k, x_init, max_iters=max_iters, gap_tol=relative_duality_gap_tol, grad_tol=grad_norm_tol)
+        self.trace, ub = [], float("inf")
+        for i in range(r["iters"]):
+            ub = min(ub, float(r["dual"][i]))
+            self.trace.append((float(r["f"][i]), ub, float(r["gnorm"][i])))
+            if verbose:
+                print(f"[mac_amd] it {i}: F={r['f'][i]:.12g} u={ub:.12g} |g|={r['gnorm'][i]:.3g}")
+        w = r["x"]
+        if rounding == "madow":
+            rounded = round_madow(w, k, value_fn=self.evaluate_objective, max_iters=random_rounding_max_iters)
+        else:
+            rounded = round_nearest(w, k, self.weights, 10)
+        return rounded, w, float(r["upper"])
+
+    def info(self) -> dict:
+        """The handle's description (GreedyESP.info) plus the iterations of the last solve."""
+        d = self._dev.info()
+        d["iterations"] = len(self.trace)
+        return d

@@ -1,0 +1,99 @@
+"""ESPRelaxation timing (mac_amd/csrc/esp_relax.h): one JSON line per case.
+
+    python tools/esp_relax_time.py [--no-check] [case ...]      cases: intel sphere2500 city10000 (default: all)
+
+K = 20 % of the candidates, naive start, 20 Frank-Wolfe iterations with the stop tests off.  run_ms = wall time of
+machip_esp_relax_run (the loop on the C side); python_ms = the same 20 iterations driven from Python: frank_wolfe over
+ESPRelaxation.problem (machip_esp_relax_eval per iteration, gradient to the host, LP vertex and update in NumPy).  first_ms =
+the first relaxation call on the handle (third buffer, incidence list, log det M(0)).  Unless --no-check: F of the final iterate
+against two CPU routes (dense LAPACK LU, sparse SuperLU), d = their disagreement.  The bytes model is DESIGN section 13's.
+Per kernel group: `rocprofv3 --kernel-trace --stats -d <dir> -o <name> -- python tools/esp_relax_time.py --no-check <case>`
+(k_relax_assemble, k_gj_step, k_esp_scores, k_sel_small, k_fw_final + k_relax_scalars: one launch each per iteration, ld / 32 of
+k_gj_step).
+"""
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import scipy.sparse as sp
+from scipy.sparse.linalg import splu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from mac_amd.optimization.frankwolfe import frank_wolfe  # noqa: E402
+from mac_amd.solvers import ESPRelaxation, NaiveGreedy  # noqa: E402
+from mac_amd.utils.graphs import Edge  # noqa: E402
+
+ITERS = 20
+
+
+def reduced(n, i, j, w):
+    keep = i != j
+    i, j, w = i[keep], j[keep], w[keep]
+    L = sp.coo_matrix((np.concatenate([w, w, -w, -w]), (np.concatenate([i, j, i, j]), np.concatenate([i, j, j, i]))), shape=(n, n))
+    return L.tocsc()[1:, 1:]
+
+
+def cpu_logdets(n, fi, fj, fw, ci, cj, cw, x, beta):
+    out = []
+    for xv in (x, np.zeros(len(x))):
+        M = (reduced(n, fi, fj, fw) + reduced(n, ci, cj, cw * xv) + beta * sp.identity(n - 1)).tocsc()
+        lu = splu(M, permc_spec="COLAMD", diag_pivot_thresh=0.0)
+        out.append((float(np.linalg.slogdet(M.toarray())[1]), float(np.sum(np.log(np.abs(lu.U.diagonal()))))))
+    return out
+
+
+def lp_vertex(g, k):
+    s = np.zeros(len(g))
+    s[np.lexsort((np.arange(len(g)), -g))[:k]] = 1.0
+    return s
+
+
+def run(case, check):
+    g = np.load(os.path.join(ROOT, "tests", "golden", f"g2o_{case}.npz"))
+    n, fi, fj, fw, ci, cj, cw = int(g["n"]), g["fi"], g["fj"], g["fw"].astype(np.float64), g["ci"], g["cj"], g["cw"].astype(np.float64)
+    fixed = [Edge(int(a), int(b), float(c)) for a, b, c in zip(fi, fj, fw)]
+    cand = [Edge(int(a), int(b), float(c)) for a, b, c in zip(ci, cj, cw)]
+    m = len(cw)
+    k = int(0.2 * m)
+    x0 = NaiveGreedy(cand).subset(k)
+    relax = ESPRelaxation(fixed, cand, n)
+    dev = relax._dev
+    t0 = time.perf_counter()
+    dev.relax_eval(np.zeros(m), want_grad=False)
+    first_ms = (time.perf_counter() - t0) * 1e3
+    dev.relax_run(k, x0, max_iters=2, gap_tol=0.0, grad_tol=0.0)          # (first launches of every kernel)
+    t0 = time.perf_counter()
+    r = dev.relax_run(k, x0, max_iters=ITERS, gap_tol=0.0, grad_tol=0.0)
+    run_ms = (time.perf_counter() - t0) * 1e3
+    t0 = time.perf_counter()
+    xp, up = frank_wolfe(x0, relax.problem, lambda gr: lp_vertex(gr, k), maxiter=ITERS, relative_duality_gap_tol=0.0, grad_norm_tol=0.0)
+    python_ms = (time.perf_counter() - t0) * 1e3
+    t0 = time.perf_counter()
+    F = relax.evaluate_objective(r["x"])
+    eval_ms = (time.perf_counter() - t0) * 1e3
+    info = relax.info()
+    ld = info["ld"]
+    out = dict(case=case, n=n, m=m, k=k, ld=ld, beta=info["beta"], iterations=int(r["iters"]), first_ms=round(first_ms, 2),
+               run_ms=round(run_ms, 2), ms_per_iteration=round(run_ms / ITERS, 3), python_ms=round(python_ms, 2),
+               python_ms_per_iteration=round(python_ms / ITERS, 3), eval_ms=round(eval_ms, 3),
+               bytes_assembly=8 * ld * ld, bytes_inverse=16 * ld * ld * (ld // 32), bytes_scores=52 * m,
+               model_tb_s=round((8 * ld * ld + 16 * ld * ld * (ld // 32) + 52 * m) / (run_ms / ITERS * 1e-3) / 1e12, 3),
+               F_last=float(r["f"][-1]), upper=float(r["upper"]), upper_python=float(up),
+               python_x_equal=bool(np.array_equal(xp, r["x"])))
+    if check:
+        (dx, sx), (d0, s0) = cpu_logdets(n, fi, fj, fw, ci, cj, cw, r["x"], info["beta"])
+        out.update(F_final_iterate=F, F_cpu_dense=dx - d0, F_cpu_sparse=sx - s0, logdet_Mx=dx, d=abs(dx - sx),
+                   device_error=abs(F - (dx - d0)), tolerance=10 * max(abs(dx - sx), 1e-13 * abs(dx)))
+    print(json.dumps(out), flush=True)
+
+
+if __name__ == "__main__":
+    args = sys.argv[1:]
+    check = "--no-check" not in args
+    ESPRelaxation([Edge(0, 1, 1.0), Edge(1, 2, 1.0)], [Edge(0, 2, 1.0)], 3).evaluate_objective([0.5])     # (HIP context and code objects)
+    for c in [a for a in args if not a.startswith("--")] or ["intel", "sphere2500", "city10000"]:
+        run(c, check)
