@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define MACHIP_ABI_VERSION 9   /* 9: the relaxation of GreedyESP's problem (machip_esp_relax_*); 8: GreedyEig handle (machip_eig_*); 7: GreedyESP handle (machip_esp_*); 6: machip_solve_stats.drift, machip_panel_plan fills 12 entries; 5: per-handle option table (machip_set_option), machip_comm_drop_ipc; 4: inter-process communicator */
+#define MACHIP_ABI_VERSION 10   /* 10: MACHIP_ESP_MATRIX_FREE (GreedyESP on a chain without a dense Sigma, option esp_free_split); 9: the relaxation of GreedyESP's problem (machip_esp_relax_*); 8: GreedyEig handle (machip_eig_*); 7: GreedyESP handle (machip_esp_*); 6: machip_solve_stats.drift, machip_panel_plan fills 12 entries; 5: per-handle option table (machip_set_option), machip_comm_drop_ipc; 4: inter-process communicator */
 
 typedef enum machip_status {
     MACHIP_OK = 0,
@@ -360,6 +360,17 @@ int machip_host_follow_records(const double* tri3, int J, int n, double e_target
  * exactly the chain (i, i+1) (closed-form Sigma), n <= 16384 otherwise (dense Gauss-Jordan inverse); beyond them MACHIP_BAD_ARG. */
 typedef struct machip_esp machip_esp;
 #define MACHIP_ESP_DENSE_INVERSE 1   /* flags: build Sigma by the dense inverse even for a chain (cross-checks) */
+/* flags: no Sigma at all (mac_amd/csrc/esp_free.h).  Only when the fixed edges are exactly the connected chain (i, i+1), parallel
+ * links summed (MACHIP_BAD_ARG otherwise, and together with MACHIP_ESP_DENSE_INVERSE): Sigma0's entries come from the chain's
+ * prefix resistances and every pick's rank-1 update stays in a history of ld x K doubles (ld = n - 1 rounded up to 64) that
+ * machip_esp_select allocates, or grows, for its largest budget; nothing of size ld x ld is ever allocated.  Nothing is ever folded:
+ * `fold` must be 0 with this flag (MACHIP_BAD_ARG otherwise -- an argument without a meaning is refused, not ignored).
+ * No limit on n but memory and int32 node ids; a K whose history does not fit in free device memory is MACHIP_BAD_ARG, decided
+ * before anything is allocated.  Pick j streams 8 ld j bytes (about 4 ld K^2 over a run): the route is for K << n.  Same rule, tie
+ * rule and per-entry arithmetic as the dense forms; the sums over the history run in a fixed order that depends on (ld, j, option
+ * esp_free_split) alone, so runs repeat bit for bit and agree with the dense chain form to rounding.  machip_esp_relax_* and
+ * machip_eig_create answer MACHIP_BAD_ARG on this route. */
+#define MACHIP_ESP_MATRIX_FREE 2
 /* fold: pending rank-1 updates folded into Sigma every `fold` steps (1..256; 0 = 64).  Builds Sigma0. */
 int machip_esp_create(int device, int64_t n, int64_t n_fixed, const int32_t* fi, const int32_t* fj, const double* fw,
                       int64_t m, const int32_t* ci, const int32_t* cj, const double* cw, int fold, int flags, machip_esp** out);
@@ -368,9 +379,11 @@ void machip_esp_destroy(machip_esp* h);
  * indices in selection order, gain_out[K] = the score s* of each pick (sum log(1 + gain) = logdet growth), t_ms_out[nb] = device
  * time from the call's start until budget ks[i] was reached.  Any output may be NULL. */
 int machip_esp_select(machip_esp* h, int nb, const int64_t* ks, int32_t* order_out, double* gain_out, double* t_ms_out);
-/* w_e r_e of every candidate (m doubles) in the current graph: F plus the last machip_esp_select's selections. */
+/* w_e r_e of every candidate (m doubles) in the current graph: F plus the last machip_esp_select's selections.  (Matrix-free
+ * route: every candidate is rescored from the chain and the history, m K gathered pairs.) */
 int machip_esp_weighted_resistances(machip_esp* h, double* r_out);
-/* info4 = {form (0 chain, 1 dense inverse), leading dimension of Sigma, fold, updates pending since the last fold}; beta. */
+/* info4 = {form (0 chain, 1 dense inverse, 2 chain without Sigma), leading dimension of Sigma, fold, updates pending since the
+ * last fold (form 2: the columns of the history)}; beta. */
 int machip_esp_info(machip_esp* h, int32_t* info4, double* beta);
 
 /* The convex relaxation of GreedyESP's problem on the same handle (mac_amd/csrc/esp_relax.h).  For x in [0, 1]^m:

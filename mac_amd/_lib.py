@@ -466,12 +466,16 @@ class Problem:
 
 
 ESP_DENSE_INVERSE = 1      # MACHIP_ESP_DENSE_INVERSE
+ESP_MATRIX_FREE = 2        # MACHIP_ESP_MATRIX_FREE
 
 
 class Esp:
     """Owns one ``machip_esp`` handle: GreedyESP's (L_red + beta I)^-1 resident on one GPU (mac_amd/csrc/esp.h)."""
 
-    def __init__(self, n, fi, fj, fw, ci, cj, cw, fold=64, dense_inverse=False, device=0):
+    def __init__(self, n, fi, fj, fw, ci, cj, cw, fold=64, dense_inverse=False, device=0, *, matrix_free=False):
+        """matrix_free: chain-fixed graphs only -- no dense inverse, the picks' updates stay in a history that ``select``
+        sizes for its largest budget (MACHIP_ESP_MATRIX_FREE; the slices of its sums: process option "esp_free_split").
+        Nothing is folded on that route: ``fold`` is not passed on (the C entry point wants 0 with the flag)."""
         lib = load()
         require_device()
         self.n = int(n)
@@ -479,9 +483,9 @@ class Esp:
         ci, cj, cw = i32(ci), i32(cj), f64(cw)
         self.m = int(len(cw))
         h = C.c_void_p()
+        flags = (ESP_DENSE_INVERSE if dense_inverse else 0) | (ESP_MATRIX_FREE if matrix_free else 0)
         check(lib.machip_esp_create(int(device), self.n, len(fw), p_i32(fi), p_i32(fj), p_f64(fw), self.m,
-                                    p_i32(ci), p_i32(cj), p_f64(cw), int(fold), ESP_DENSE_INVERSE if dense_inverse else 0,
-                                    C.byref(h)))
+                                    p_i32(ci), p_i32(cj), p_f64(cw), 0 if matrix_free else int(fold), flags, C.byref(h)))
         self._h = h
         self._lib = lib
 
@@ -514,11 +518,11 @@ class Esp:
         return r[:self.m]
 
     def info(self):
-        """dict(form = "chain" | "dense", ld, fold, pending, beta)."""
+        """dict(form = "chain" | "dense" | "chain_free", ld, fold, pending, beta)."""
         a = np.zeros(4, dtype=np.int32)
         b = C.c_double()
         check(self._lib.machip_esp_info(self._h, p_i32(a), C.byref(b)))
-        return dict(form="chain" if a[0] == 0 else "dense", ld=int(a[1]), fold=int(a[2]), pending=int(a[3]), beta=b.value)
+        return dict(form=("chain", "dense", "chain_free")[a[0]], ld=int(a[1]), fold=int(a[2]), pending=int(a[3]), beta=b.value)
 
     def relax_eval(self, x, want_grad=True):
         """(F(x), gradient or None) of the relaxation: F = logdet M(x) - logdet M(0) (machip_esp_relax_eval)."""

@@ -28,6 +28,7 @@ namespace machip {
 
 constexpr int kEspChainMaxN = 32768;   // chain form: 2 x 8.6 GB of Sigma at the limit
 constexpr int kEspDenseMaxN = 16384;   // general form: 512 Gauss-Jordan launches over 2 x 2.1 GB (k_gj_step indexes with int: ld^2 < 2^31)
+constexpr int kEspFormFree = 2;        // machip_esp::form of MACHIP_ESP_MATRIX_FREE: no Sigma at all, no n limit (esp_free.h)
 constexpr int kEspMaxFold = 256;
 constexpr int kEspDefaultFold = 64;
 constexpr int kEspGrid = 256;          // workgroups of the score / update pass (= partials of the argmax)
@@ -150,6 +151,15 @@ __device__ __forceinline__ double esp_z_entry(const EspView& V, const double* __
     return z;
 }
 
+// the step's record, by one thread: winner e is pick k and column j of the low-rank block (shared with esp_free.h)
+__device__ __forceinline__ void esp_record_step(const EspView& V, int e, int j, int k) {
+    const double sstar = V.best->val;
+    V.cb[j] = V.cw[e] / (1.0 + sstar);
+    V.order[k] = e;
+    V.gain[k] = sstar;
+    V.sel[e] = 1;
+}
+
 // ---- the z of the step's winner into Zb[:,j].  grid = ceil(ld / 256).  Workgroup 0 records the step. ----
 __global__ __launch_bounds__(kBlock) void k_esp_z(EspView V, const double* __restrict__ S, int j, int k) {
     __shared__ double alpha[kEspMaxFold];
@@ -159,13 +169,7 @@ __global__ __launch_bounds__(kBlock) void k_esp_z(EspView V, const double* __res
     __syncthreads();
     const int i = blockIdx.x * kBlock + threadIdx.x;
     if (i < V.ld) V.Zb[(size_t)j * V.ld + i] = esp_z_entry(V, S, u, v, j, alpha, i);
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        const double sstar = V.best->val;
-        V.cb[j] = V.cw[e] / (1.0 + sstar);
-        V.order[k] = e;
-        V.gain[k] = sstar;
-        V.sel[e] = 1;
-    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) esp_record_step(V, e, j, k);
 }
 
 // ---- s_e <- s_e - w_e c (z_u - z_v)^2 for all m, z = Zb[:,j]; partials of the argmax over the unselected ----
@@ -235,13 +239,16 @@ struct machip_esp {
     int device = 0;
     hipStream_t stream = nullptr;
     int n = 0, np = 0, ld = 0, m = 0, fold = machip::kEspDefaultFold;
-    int form = 0;                 // 0 chain, 1 general (dense Gauss-Jordan inverse)
+    int form = 0;                 // 0 chain, 1 general (dense Gauss-Jordan inverse), 2 chain without Sigma (esp_free.h)
     double beta = 0.0;
+    double *R = nullptr, *part = nullptr;      // form 2: the chain's prefix resistances (n'), the column slices' partial sums
+    size_t zcap = 0;              // form 2: columns Zb / cb are allocated for (the history of the largest budget so far)
+    int free_split = 0;           // form 2: option esp_free_split when the handle was made (0 = automatic)
     double *bufA = nullptr, *bufB = nullptr;
     double* sig0 = nullptr;       // pristine Sigma0 (one of bufA / bufB)
     double* sig = nullptr;        // working copy (the other one)
     bool live = false;            // sig holds the state after the last selection run
-    int pending = 0;              // columns of Zb not yet folded into sig
+    int pending = 0;              // columns of Zb not yet folded into sig (form 2: the picks of the last run, never folded)
     int *cu = nullptr, *cv = nullptr, *sel = nullptr, *pi = nullptr, *order = nullptr, *bad = nullptr;
     double *cw = nullptr, *s = nullptr, *Zb = nullptr, *cb = nullptr, *pv = nullptr, *gain = nullptr, *piv = nullptr;
     machip::EspBest* best = nullptr;

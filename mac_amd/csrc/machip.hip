@@ -17,6 +17,7 @@
 
 #include "solver.h"
 #include "esp.h"
+#include "esp_free.h"
 #include "esp_relax.h"
 #include "eig.h"
 
@@ -1568,10 +1569,17 @@ int machip_esp_create(int device, int64_t n, int64_t n_fixed, const int32_t* fi,
     if (n < 2) return fail(MACHIP_BAD_ARG, "num_nodes must be at least 2");
     if (n_fixed < 0 || m < 0 || m > 2000000000ll) return fail(MACHIP_BAD_ARG, "bad edge counts");
     if ((n_fixed && (!fi || !fj || !fw)) || (m && (!ci || !cj || !cw))) return fail(MACHIP_BAD_ARG, "NULL edge array");
+    const int fold_given = fold;
     if (fold == 0) fold = kEspDefaultFold;
     if (fold < 1 || fold > kEspMaxFold) return fail(MACHIP_BAD_ARG, "fold must be in [1, 256]");
-    if (flags & ~MACHIP_ESP_DENSE_INVERSE) return fail(MACHIP_BAD_ARG, "unknown flags");
-    if (n > kEspChainMaxN) return fail(MACHIP_BAD_ARG, "GreedyESP keeps (L_red + beta I)^-1 dense: num_nodes must be <= 32768 (chain-fixed graphs), <= 16384 otherwise");
+    if (flags & ~(MACHIP_ESP_DENSE_INVERSE | MACHIP_ESP_MATRIX_FREE)) return fail(MACHIP_BAD_ARG, "unknown flags");
+    const bool mfree = (flags & MACHIP_ESP_MATRIX_FREE) != 0;
+    if (mfree && fold_given != 0)      // (an argument that would be ignored is refused, not dropped: nothing is ever folded here)
+        return fail(MACHIP_BAD_ARG, "MACHIP_ESP_MATRIX_FREE never folds: fold has no meaning on this route and must be 0");
+    if (mfree && (flags & MACHIP_ESP_DENSE_INVERSE))
+        return fail(MACHIP_BAD_ARG, "MACHIP_ESP_MATRIX_FREE keeps no Sigma: it cannot be combined with MACHIP_ESP_DENSE_INVERSE");
+    if (mfree && n > (int64_t)INT_MAX - kGjT) return fail(MACHIP_BAD_ARG, "node ids are int32: num_nodes is too large");
+    if (!mfree && n > kEspChainMaxN) return fail(MACHIP_BAD_ARG, "GreedyESP keeps (L_red + beta I)^-1 dense: num_nodes must be <= 32768 (chain-fixed graphs), <= 16384 otherwise");
     for (int64_t e = 0; e < n_fixed; ++e)
         if (fi[e] < 0 || fi[e] >= n || fj[e] < 0 || fj[e] >= n || !std::isfinite(fw[e])) return fail(MACHIP_BAD_ARG, "fixed edge out of range or weight not finite");
     for (int64_t e = 0; e < m; ++e)
@@ -1604,26 +1612,31 @@ int machip_esp_create(int device, int64_t n, int64_t n_fixed, const int32_t* fi,
         else link[(size_t)a] += fw[e];
     }
     for (int i = 0; chain && i < np; ++i) if (!(link[(size_t)i] > 0.0)) chain = false;
+    if (mfree && !chain)
+        return fail(MACHIP_BAD_ARG, "the matrix-free route needs a chain: the fixed edges must be exactly the connected path (i, i+1), i = 0..n-2 (parallel links summed)");
     if (!chain && n > kEspDenseMaxN)
         return fail(MACHIP_BAD_ARG, "GreedyESP inverts L_red + beta I densely when the fixed edges are not exactly the chain (i, i+1): num_nodes must be <= 16384");
     if (machip_device_count() <= 0) return fail(MACHIP_NO_DEVICE, "no HIP device visible");
     HIP_TRY(hipSetDevice(device));
     machip_esp* h = new machip_esp();
-    h->device = device; h->n = N; h->np = np; h->m = (int)m; h->fold = fold; h->beta = beta; h->form = chain ? 0 : 1;
+    h->device = device; h->n = N; h->np = np; h->m = (int)m; h->fold = mfree ? 0 : fold; h->beta = beta; h->form = mfree ? kEspFormFree : chain ? 0 : 1;
+    h->free_split = (int)std::max(0l, std::min<long>(default_options().get(kOpt_esp_free_split, 0), kEspFreeMaxSplit));
     h->ld = (np + kGjT - 1) / kGjT * kGjT;
     h->hfi.assign(fi, fi + n_fixed); h->hfj.assign(fj, fj + n_fixed); h->hfw.assign(fw, fw + n_fixed);
     h->hci.assign(ci, ci + m); h->hcj.assign(cj, cj + m); h->hcw.assign(cw, cw + m);
     auto body = [&]() -> int {
         HIP_TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
         const size_t ld = (size_t)h->ld, ms = (size_t)std::max<int64_t>(m, 1);
-        ST_TRY(dev_alloc(&h->bufA, ld * ld)); ST_TRY(dev_alloc(&h->bufB, ld * ld));
+        if (!mfree) { ST_TRY(dev_alloc(&h->bufA, ld * ld)); ST_TRY(dev_alloc(&h->bufB, ld * ld)); }
         ST_TRY(dev_alloc(&h->cu, ms)); ST_TRY(dev_alloc(&h->cv, ms)); ST_TRY(dev_alloc(&h->cw, ms)); ST_TRY(dev_alloc(&h->s, ms));
         ST_TRY(dev_alloc(&h->sel, ms)); ST_TRY(dev_alloc(&h->order, ms)); ST_TRY(dev_alloc(&h->gain, ms));
-        ST_TRY(dev_alloc(&h->Zb, ld * (size_t)fold)); ST_TRY(dev_alloc(&h->cb, (size_t)fold));
+        if (!mfree) { ST_TRY(dev_alloc(&h->Zb, ld * (size_t)fold)); ST_TRY(dev_alloc(&h->cb, (size_t)fold)); }      // (matrix-free: machip_esp_select sizes the history)
         ST_TRY(dev_alloc(&h->pv, (size_t)kEspGrid)); ST_TRY(dev_alloc(&h->pi, (size_t)kEspGrid)); ST_TRY(dev_alloc(&h->best, 1));
         ST_TRY(dev_alloc(&h->bad, 1)); ST_TRY(dev_alloc(&h->piv, (size_t)2 * kGjB * kGjB));
-        HIP_TRY(hipMemsetAsync(h->Zb, 0, sizeof(double) * ld * (size_t)fold, h->stream));
-        HIP_TRY(hipMemsetAsync(h->cb, 0, sizeof(double) * (size_t)fold, h->stream));
+        if (!mfree) {
+            HIP_TRY(hipMemsetAsync(h->Zb, 0, sizeof(double) * ld * (size_t)fold, h->stream));
+            HIP_TRY(hipMemsetAsync(h->cb, 0, sizeof(double) * (size_t)fold, h->stream));
+        }
         HIP_TRY(hipMemsetAsync(h->bad, 0, sizeof(int), h->stream));
         if (m) {
             std::vector<int> u((size_t)m), v((size_t)m);
@@ -1640,6 +1653,11 @@ int machip_esp_create(int device, int64_t n, int64_t n_fixed, const int32_t* fi,
             double* dR = nullptr;
             ST_TRY(dev_alloc(&dR, (size_t)np));
             HIP_TRY(hipMemcpyAsync(dR, R.data(), sizeof(double) * (size_t)np, hipMemcpyHostToDevice, h->stream));
+            if (mfree) {                                  // R is all of Sigma0 this route keeps
+                h->R = dR;
+                HIP_TRY(hipStreamSynchronize(h->stream));
+                return MACHIP_OK;
+            }
             k_esp_chain_fill<<<dim3((unsigned)((ld + kBlock - 1) / kBlock), (unsigned)ld), kBlock, 0, h->stream>>>(h->bufA, dR, np, (int)ld);
             HIP_TRY(hipGetLastError());
             HIP_TRY(hipStreamSynchronize(h->stream));
@@ -1703,7 +1721,7 @@ void machip_esp_destroy(machip_esp* h) {
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     for (hipEvent_t e : h->ev) (void)hipEventDestroy(e);
     esp_relax_release(h);
-    void* bufs[] = {h->bufA, h->bufB, h->cu, h->cv, h->sel, h->pi, h->order, h->bad, h->cw, h->s, h->Zb, h->cb, h->pv, h->gain, h->piv, h->best};
+    void* bufs[] = {h->bufA, h->bufB, h->cu, h->cv, h->sel, h->pi, h->order, h->bad, h->cw, h->s, h->Zb, h->cb, h->pv, h->gain, h->piv, h->best, h->R, h->part};
     for (void* q : bufs) if (q) (void)hipFree(q);
     if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
@@ -1715,6 +1733,8 @@ int machip_esp_info(machip_esp* h, int32_t* info4, double* beta) {
     if (beta) *beta = h->beta;
     return MACHIP_OK;
 }
+
+static int esp_select_finish(machip_esp* h, int nb, int K, int32_t* order_out, double* gain_out, double* t_ms_out);
 
 int machip_esp_select(machip_esp* h, int nb, const int64_t* ks, int32_t* order_out, double* gain_out, double* t_ms_out) {
     if (!h || nb < 1 || !ks) return fail(MACHIP_BAD_ARG, "NULL handle, no budgets or ks is NULL");
@@ -1728,8 +1748,12 @@ int machip_esp_select(machip_esp* h, int nb, const int64_t* ks, int32_t* order_o
         h->ev.push_back(e);
     }
     const int K = (int)ks[nb - 1], B = h->fold, P = h->grid_m(), zg = (h->ld + kBlock - 1) / kBlock;
-    const EspView V = h->view();
     hipStream_t st = h->stream;
+    if (h->form == kEspFormFree) {
+        ST_TRY(esp_free_select(h, nb, ks));
+        return esp_select_finish(h, nb, K, order_out, gain_out, t_ms_out);
+    }
+    const EspView V = h->view();
     h->live = false;
     HIP_TRY(hipEventRecord(h->ev[0], st));
     HIP_TRY(hipMemcpyAsync(h->sig, h->sig0, sizeof(double) * (size_t)h->ld * (size_t)h->ld, hipMemcpyDeviceToDevice, st));
@@ -1749,6 +1773,12 @@ int machip_esp_select(machip_esp* h, int nb, const int64_t* ks, int32_t* order_o
     }
     HIP_TRY(hipGetLastError());
     h->pending = K % B;
+    return esp_select_finish(h, nb, K, order_out, gain_out, t_ms_out);
+}
+
+// the end of a selection run, either route: the results and the budgets' times to the host
+static int esp_select_finish(machip_esp* h, int nb, int K, int32_t* order_out, double* gain_out, double* t_ms_out) {
+    hipStream_t st = h->stream;
     int hbad = 0;
     if (order_out) HIP_TRY(hipMemcpyAsync(order_out, h->order, sizeof(int) * (size_t)K, hipMemcpyDeviceToHost, st));
     if (gain_out) HIP_TRY(hipMemcpyAsync(gain_out, h->gain, sizeof(double) * (size_t)K, hipMemcpyDeviceToHost, st));
@@ -1769,9 +1799,11 @@ int machip_esp_weighted_resistances(machip_esp* h, double* r_out) {
     if (!h || (!r_out && h->m)) return fail(MACHIP_BAD_ARG, "NULL handle or output");
     HIP_TRY(hipSetDevice(h->device));
     double* S = h->live ? h->sig : h->sig0;
-    if (h->live && h->pending) { h->fold_into(S, h->pending); h->pending = 0; }
+    if (h->form != kEspFormFree && h->live && h->pending) { h->fold_into(S, h->pending); h->pending = 0; }
     if (h->m) {
-        k_esp_scores<<<h->grid_m(), kBlock, 0, h->stream>>>(h->view(), S, 0);
+        if (h->form != kEspFormFree) k_esp_scores<<<h->grid_m(), kBlock, 0, h->stream>>>(h->view(), S, 0);
+        else if (h->live) k_esp_free_resist<<<h->grid_m(), kBlock, 0, h->stream>>>(h->view(), h->R, h->pending);
+        else k_esp_free_scores<<<h->grid_m(), kBlock, 0, h->stream>>>(h->view(), h->R, 0);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpyAsync(r_out, h->s, sizeof(double) * (size_t)h->m, hipMemcpyDeviceToHost, h->stream));
     }
@@ -1859,6 +1891,8 @@ int machip_eig_create(int device, int64_t n, int64_t n_fixed, const int32_t* fi,
     if (fold == 0) fold = kEigDefaultFold;
     if (batch == 0) batch = kEigDefaultBatch;
     if (batch < 1 || batch > kEigMaxBatch) return fail(MACHIP_BAD_ARG, "batch must be in [1, 4096]");
+    if (flags & MACHIP_ESP_MATRIX_FREE)
+        return fail(MACHIP_BAD_ARG, "GreedyEig solves against the dense inverse: MACHIP_ESP_MATRIX_FREE is not available here");
     machip_esp* base = nullptr;
     ST_TRY(machip_esp_create(device, n, n_fixed, fi, fj, fw, m, ci, cj, cw, fold, flags, &base));
     if (base->beta != 0.0) {

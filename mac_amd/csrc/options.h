@@ -32,7 +32,9 @@ namespace machip {
     X(lob_patience) X(lob_small_s) X(lob_fuse)                                                                                     \
     /* select / assembly / lanes / communicators (the handle-creation ones are read when the handle, or its first lane, is made) */ \
     X(sel_small) X(sel_fuse) X(asm_g) X(asm_maxgrid) X(vbudget_mb) X(vcap) X(lanes) X(lane_vbudget_mb) X(lane_queues) X(shard_eig) X(ipc_panel) \
-    X(rccl_timeout_s)
+    X(rccl_timeout_s)                                                                                                              \
+    /* GreedyESP, matrix-free route (read when the handle is made): slices of the history's columns per pick, 1..32 */           \
+    X(esp_free_split)
 
 enum OptId {
 #define X(n) kOpt_##n,

@@ -23,11 +23,13 @@ from mac_amd.utils.graphs import Edge, edges_to_arrays, weight_reduced_graph_lap
 
 class GreedyESP:
     def __init__(self, fixed_edges: List[Edge], candidate_edges: List[Edge], num_nodes: int, lazy: bool = False, *,
-                 device: int = 0, fold: int = 64, dense_inverse: bool = False):
+                 device: int = 0, fold: int = 64, dense_inverse: bool = False, matrix_free: bool = False):
         """Arguments as mac/solvers/greedy_esp.py of the reference, plus keyword-only ``device`` (GPU ordinal), ``fold``
         (pending rank-1 updates folded into the inverse every ``fold`` picks, 1..256) and ``dense_inverse`` (build the
-        inverse by dense Gauss-Jordan even when the fixed edges are a chain: cross-checks).  Raises Disconnected when the
-        fixed graph is disconnected and a node other than 0 has no fixed edge (the reference re-raises CHOLMOD's error)."""
+        inverse by dense Gauss-Jordan even when the fixed edges are a chain: cross-checks) and ``matrix_free`` (chain-fixed
+        graphs only: no dense inverse, no folds (``fold`` is not used) and no limit on num_nodes; the picks' updates are kept as a history of num_nodes x k
+        doubles, so the route is for k << num_nodes -- DESIGN section 14).  Raises Disconnected when the fixed graph is
+        disconnected and a node other than 0 has no fixed edge (the reference re-raises CHOLMOD's error)."""
         if num_nodes == 0:
             assert len(fixed_edges) == len(candidate_edges) == 0
         self.L_fixed = weight_reduced_graph_lap_from_edge_list(fixed_edges, num_nodes)
@@ -38,7 +40,8 @@ class GreedyESP:
         self.lazy = lazy
         fi, fj, fw = edges_to_arrays(fixed_edges)
         ci, cj, cw = edges_to_arrays(candidate_edges)
-        self._dev = _lib.Esp(num_nodes, fi, fj, fw, ci, cj, cw, fold=fold, dense_inverse=dense_inverse, device=device)
+        self._dev = _lib.Esp(num_nodes, fi, fj, fw, ci, cj, cw, fold=fold, dense_inverse=dense_inverse, device=device,
+                             matrix_free=matrix_free)
         self.last_gains: Optional[np.ndarray] = None      # s* of every pick of the last run (sum log(1 + gain) = logdet growth)
 
     def _run(self, ks):
@@ -83,5 +86,5 @@ class GreedyESP:
         return self._dev.weighted_resistances()
 
     def info(self) -> dict:
-        """How the inverse was built: form ("chain" / "dense"), leading dimension, fold, pending updates, beta."""
+        """How the inverse was built: form ("chain" / "dense" / "chain_free"), leading dimension, fold, pending updates, beta."""
         return self._dev.info()

@@ -6,6 +6,13 @@ Pose graphs: a full sweep (K = all candidates).  er10k: n = 10 000, chain-fixed,
 build_ms = wall time of the constructor (host arrays + Sigma0 on the device), select_ms = device time of one run from its start
 to the last pick (events on the handle's stream).  The bytes model counts HBM traffic per step (two rows of Sigma, the pending
 block, the z column, the score pass over the candidates), per fold (Sigma read + written) and for Sigma0.
+
+    python tools/esp_time.py --matrix-free [case ...]      cases: city10000 er10k chain100k:2000 chain100k:10000 (default: all)
+
+The matrix-free route (mac_amd/csrc/esp_free.h; chain-fixed graphs, no Sigma).  chain100k:K: n = 100 000, chain-fixed, 2 M random
+candidate pairs, K picks -- beyond the dense limit.  One run with eight budgets: per segment of picks the mean history length j,
+us per pick, and the rate in the model "pick j streams 8 ld j bytes" (the history only: the score pass is not counted);
+history_bytes = 8 ld K.
 """
 import json
 import os
@@ -65,7 +72,47 @@ def run(case):
                           select_bytes_model=int(model), model_tb_s=round(model / (float(t_ms[-1]) * 1e-3) / 1e12, 3))), flush=True)
 
 
+def chain100k(K, n=100000, m=2000000, seed=0):
+    rng = np.random.default_rng(seed)
+    fi = np.arange(n - 1)
+    return n, fi, fi + 1, rng.uniform(0.5, 2.0, n - 1), rng.integers(0, n, m), rng.integers(0, n, m), rng.uniform(0.5, 2.0, m), K
+
+
+def run_free(case):
+    from mac_amd import _lib
+    if case.startswith("chain100k"):
+        n, fi, fj, fw, ci, cj, cw, K = chain100k(int(case.split(":")[1]))
+    else:
+        n, fi, fj, fw, ci, cj, cw, K = er10k() if case == "er10k" else pose_graph(case)
+    t0 = time.perf_counter()
+    dev = _lib.Esp(n, fi, fj, fw, ci, cj, cw, matrix_free=True)
+    build_ms = (time.perf_counter() - t0) * 1e3
+    info = dev.info()
+    ld, m = info["ld"], len(cw)
+    ks = sorted({max(1, K * q // 8) for q in range(1, 9)})
+    dev.select([min(K, 64)])                     # (first launches of every kernel; the history is allocated before the timed events)
+    t0 = time.perf_counter()
+    order, gain, t_ms = dev.select(ks)
+    wall_ms = (time.perf_counter() - t0) * 1e3
+    segs, k0, t_prev = [], 0, 0.0
+    for k1, t1 in zip(ks, t_ms):                 # picks k0 .. k1 - 1: pick j has j columns behind it
+        us = (float(t1) - t_prev) * 1e3 / (k1 - k0)
+        j = (k0 + k1 - 1) / 2
+        segs.append([round(j, 1), round(us, 3), round(8 * ld * j / (us * 1e-6) / 1e12, 3)])
+        k0, t_prev = k1, float(t1)
+    stream = 4 * ld * K * (K - 1)
+    print(json.dumps(dict(case=case, route="matrix_free", n=n, m=m, steps=K, form=info["form"], ld=ld, build_ms=round(build_ms, 2),
+                          select_ms=round(float(t_ms[-1]), 3), select_wall_ms=round(wall_ms, 2),
+                          us_per_step=round(float(t_ms[-1]) * 1e3 / K, 3), history_bytes=8 * ld * K, stream_bytes_model=stream,
+                          stream_tb_s=round(stream / (float(t_ms[-1]) * 1e-3) / 1e12, 3), j_us_tbs=segs)), flush=True)
+
+
 if __name__ == "__main__":
     GreedyESP([Edge(0, 1, 1.0), Edge(1, 2, 1.0)], [Edge(0, 2, 1.0)], 3).subset(1)      # (HIP context and code objects: not build_ms)
-    for c in sys.argv[1:] or ["intel", "sphere2500", "city10000", "ais2klinik", "er10k"]:
-        run(c)
+    args = [a for a in sys.argv[1:] if a != "--matrix-free"]
+    if "--matrix-free" in sys.argv[1:]:
+        for c in args or ["city10000", "er10k", "chain100k:2000", "chain100k:10000"]:
+            run_free(c)
+    else:
+        for c in args or ["intel", "sphere2500", "city10000", "ais2klinik", "er10k"]:
+            run(c)
