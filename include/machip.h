@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define MACHIP_ABI_VERSION 10   /* 10: MACHIP_ESP_MATRIX_FREE (GreedyESP on a chain without a dense Sigma, option esp_free_split); 9: the relaxation of GreedyESP's problem (machip_esp_relax_*); 8: GreedyEig handle (machip_eig_*); 7: GreedyESP handle (machip_esp_*); 6: machip_solve_stats.drift, machip_panel_plan fills 12 entries; 5: per-handle option table (machip_set_option), machip_comm_drop_ipc; 4: inter-process communicator */
+#define MACHIP_ABI_VERSION 11   /* 11: MACHIP_ESP_SPANNING_TREE (the matrix-free route of GreedyESP for any connected fixed graph; machip_esp_tree_plan, machip_esp_seeds); 10: MACHIP_ESP_MATRIX_FREE (GreedyESP on a chain without a dense Sigma, option esp_free_split); 9: the relaxation of GreedyESP's problem (machip_esp_relax_*); 8: GreedyEig handle (machip_eig_*); 7: GreedyESP handle (machip_esp_*); 6: machip_solve_stats.drift, machip_panel_plan fills 12 entries; 5: per-handle option table (machip_set_option), machip_comm_drop_ipc; 4: inter-process communicator */
 
 typedef enum machip_status {
     MACHIP_OK = 0,
@@ -371,6 +371,16 @@ typedef struct machip_esp machip_esp;
  * esp_free_split) alone, so runs repeat bit for bit and agree with the dense chain form to rounding.  machip_esp_relax_* and
  * machip_eig_create answer MACHIP_BAD_ARG on this route. */
 #define MACHIP_ESP_MATRIX_FREE 2
+/* flags, valid only together with MACHIP_ESP_MATRIX_FREE (MACHIP_BAD_ARG alone, with MACHIP_ESP_DENSE_INVERSE or with fold != 0):
+ * the matrix-free route for ANY connected fixed graph (mac_amd/csrc/esp_tree.h).  Sigma0 is that of the spanning tree T that
+ * machip_esp_tree_plan builds -- Sigma0(T)_ab = R[lca(a, b)], R the resistance from node 0 along T -- and each of the r fixed links
+ * not in T ("seeds") is a rank-1 update kept as one of the first r columns of the history, before the first pick; the seeds make
+ * no entry in order_out / gain_out.  The history holds r + K columns (8 ld (r + K) bytes): the route is for r << n, K << n.  A fixed
+ * graph that is not connected is MACHIP_BAD_ARG (the route has no beta), as are fixed links whose summed weight is not positive;
+ * all argument errors are decided on the host before a device is touched.  Exact for any connected fixed graph; on a chain it
+ * feeds the history's sums the doubles MACHIP_ESP_MATRIX_FREE alone feeds them and returns the same bits.  machip_esp_relax_* and
+ * machip_eig_create answer MACHIP_BAD_ARG on this route. */
+#define MACHIP_ESP_SPANNING_TREE 8
 /* fold: pending rank-1 updates folded into Sigma every `fold` steps (1..256; 0 = 64).  Builds Sigma0. */
 int machip_esp_create(int device, int64_t n, int64_t n_fixed, const int32_t* fi, const int32_t* fj, const double* fw,
                       int64_t m, const int32_t* ci, const int32_t* cj, const double* cw, int fold, int flags, machip_esp** out);
@@ -382,9 +392,20 @@ int machip_esp_select(machip_esp* h, int nb, const int64_t* ks, int32_t* order_o
 /* w_e r_e of every candidate (m doubles) in the current graph: F plus the last machip_esp_select's selections.  (Matrix-free
  * route: every candidate is rescored from the chain and the history, m K gathered pairs.) */
 int machip_esp_weighted_resistances(machip_esp* h, double* r_out);
-/* info4 = {form (0 chain, 1 dense inverse, 2 chain without Sigma), leading dimension of Sigma, fold, updates pending since the
- * last fold (form 2: the columns of the history)}; beta. */
+/* info4 = {form (0 chain, 1 dense inverse, 2 chain without Sigma, 3 spanning tree without Sigma), leading dimension of Sigma, fold,
+ * updates pending since the last fold (form 2: the columns of the history; form 3: the picks in it, seeds not counted)}; beta. */
 int machip_esp_info(machip_esp* h, int32_t* info4, double* beta);
+/* The host side of MACHIP_ESP_SPANNING_TREE, no device needed.  Parallel fixed edges are summed in list order ((a, b) and (b, a)
+ * are one link), self-loops dropped.  T = the BFS tree from node 0, the neighbours of a node visited in order of first appearance
+ * in the fixed list.  Outputs by node (n entries each): parent (-1 for node 0), R[v] = R[parent] + 1 / w (R[0] = 0; on a chain
+ * the prefix sums, same order of additions), pre = preorder number (children in the order BFS attached them), end = the last
+ * preorder number of v's subtree (a is an ancestor of b iff pre[a] <= pre[b] <= end[a]).  The links not in T, in order of first
+ * appearance and oriented as first given, are the seeds: *n_seeds of them into su, sv, sw (room for n_fixed entries each).
+ * MACHIP_BAD_ARG when the fixed graph is not connected or a link's summed weight is not positive. */
+int machip_esp_tree_plan(int64_t n, int64_t n_fixed, const int32_t* fi, const int32_t* fj, const double* fw, int32_t* parent,
+                         double* R, int32_t* pre, int32_t* end, int64_t* n_seeds, int32_t* su, int32_t* sv, double* sw);
+/* *seeds_out = the seeds of a MACHIP_ESP_SPANNING_TREE handle (distinct fixed links - (n - 1)); 0 on every other handle. */
+int machip_esp_seeds(machip_esp* h, int64_t* seeds_out);
 
 /* The convex relaxation of GreedyESP's problem on the same handle (mac_amd/csrc/esp_relax.h).  For x in [0, 1]^m:
  *     M(x) = L_red + beta I + sum_e x_e w_e a_e a_e^T,   F(x) = log det M(x) - log det M(0)   (nats; F(0) = 0 exactly; for a 0/1 x

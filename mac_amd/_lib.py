@@ -106,6 +106,9 @@ SIGNATURES = {
     "machip_esp_select": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int64), _i32p, _f64p, _f64p]),
     "machip_esp_weighted_resistances": (C.c_int, [C.c_void_p, _f64p]),
     "machip_esp_info": (C.c_int, [C.c_void_p, _i32p, C.POINTER(C.c_double)]),
+    "machip_esp_tree_plan": (C.c_int, [C.c_int64, C.c_int64, _i32p, _i32p, _f64p, _i32p, _f64p, _i32p, _i32p, C.POINTER(C.c_int64),
+                                       _i32p, _i32p, _f64p]),
+    "machip_esp_seeds": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     "machip_esp_relax_eval": (C.c_int, [C.c_void_p, _f64p, C.POINTER(C.c_double), _f64p]),
     "machip_esp_relax_run": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_double, C.c_double, _f64p, _f64p, _f64p, _f64p,
                                        C.POINTER(C.c_int), C.POINTER(C.c_double)]),
@@ -467,15 +470,35 @@ class Problem:
 
 ESP_DENSE_INVERSE = 1      # MACHIP_ESP_DENSE_INVERSE
 ESP_MATRIX_FREE = 2        # MACHIP_ESP_MATRIX_FREE
+ESP_SPANNING_TREE = 8      # MACHIP_ESP_SPANNING_TREE (only together with ESP_MATRIX_FREE)
+
+
+def host_esp_tree(n, fi, fj, fw):
+    """The spanning tree and the seeds the matrix_free="tree" route works from (machip_esp_tree_plan; host only, no device):
+    dict(parent, R, pre, end) by node and seeds = (u, v, w) arrays of the fixed links outside the tree."""
+    fi, fj, fw = i32(fi), i32(fj), f64(fw)
+    n, nf = int(n), len(fw)
+    parent, pre, end = (np.zeros(max(n, 1), dtype=np.int32) for _ in range(3))
+    R = np.zeros(max(n, 1))
+    su, sv, sw = np.zeros(max(nf, 1), dtype=np.int32), np.zeros(max(nf, 1), dtype=np.int32), np.zeros(max(nf, 1))
+    r = C.c_int64(0)
+    check(load().machip_esp_tree_plan(n, nf, p_i32(fi), p_i32(fj), p_f64(fw), p_i32(parent), p_f64(R), p_i32(pre), p_i32(end),
+                                      C.byref(r), p_i32(su), p_i32(sv), p_f64(sw)))
+    r = r.value
+    return dict(parent=parent[:n], R=R[:n], pre=pre[:n], end=end[:n], seeds=(su[:r].copy(), sv[:r].copy(), sw[:r].copy()))
 
 
 class Esp:
     """Owns one ``machip_esp`` handle: GreedyESP's (L_red + beta I)^-1 resident on one GPU (mac_amd/csrc/esp.h)."""
 
     def __init__(self, n, fi, fj, fw, ci, cj, cw, fold=64, dense_inverse=False, device=0, *, matrix_free=False):
-        """matrix_free: chain-fixed graphs only -- no dense inverse, the picks' updates stay in a history that ``select``
+        """matrix_free="tree": any connected fixed graph -- a spanning tree's closed form plus one seeded history column per fixed
+        link outside it (MACHIP_ESP_MATRIX_FREE | MACHIP_ESP_SPANNING_TREE, mac_amd/csrc/esp_tree.h).
+        matrix_free=True: chain-fixed graphs only -- no dense inverse, the picks' updates stay in a history that ``select``
         sizes for its largest budget (MACHIP_ESP_MATRIX_FREE; the slices of its sums: process option "esp_free_split").
         Nothing is folded on that route: ``fold`` is not passed on (the C entry point wants 0 with the flag)."""
+        if not isinstance(matrix_free, (bool, np.bool_)) and matrix_free != "tree":
+            raise ValueError(f'matrix_free must be False, True or "tree", not {matrix_free!r}')
         lib = load()
         require_device()
         self.n = int(n)
@@ -484,6 +507,8 @@ class Esp:
         self.m = int(len(cw))
         h = C.c_void_p()
         flags = (ESP_DENSE_INVERSE if dense_inverse else 0) | (ESP_MATRIX_FREE if matrix_free else 0)
+        if isinstance(matrix_free, str):
+            flags |= ESP_SPANNING_TREE
         check(lib.machip_esp_create(int(device), self.n, len(fw), p_i32(fi), p_i32(fj), p_f64(fw), self.m,
                                     p_i32(ci), p_i32(cj), p_f64(cw), 0 if matrix_free else int(fold), flags, C.byref(h)))
         self._h = h
@@ -518,11 +543,14 @@ class Esp:
         return r[:self.m]
 
     def info(self):
-        """dict(form = "chain" | "dense" | "chain_free", ld, fold, pending, beta)."""
+        """dict(form = "chain" | "dense" | "chain_free" | "tree_free", ld, fold, pending, beta, seeds)."""
         a = np.zeros(4, dtype=np.int32)
         b = C.c_double()
+        r = C.c_int64(0)
         check(self._lib.machip_esp_info(self._h, p_i32(a), C.byref(b)))
-        return dict(form=("chain", "dense", "chain_free")[a[0]], ld=int(a[1]), fold=int(a[2]), pending=int(a[3]), beta=b.value)
+        check(self._lib.machip_esp_seeds(self._h, C.byref(r)))
+        return dict(form=("chain", "dense", "chain_free", "tree_free")[a[0]], ld=int(a[1]), fold=int(a[2]), pending=int(a[3]),
+                    beta=b.value, seeds=int(r.value))
 
     def relax_eval(self, x, want_grad=True):
         """(F(x), gradient or None) of the relaxation: F = logdet M(x) - logdet M(0) (machip_esp_relax_eval)."""

@@ -231,6 +231,7 @@ __global__ __launch_bounds__(256) void k_esp_fold(double* __restrict__ S, const 
 }
 
 struct EspRelax;      // esp_relax.h: the state of the convex relaxation, made by the first relaxation call
+struct EspTreeState;  // esp_tree.h: the spanning tree's tables and the seeds of a MACHIP_ESP_SPANNING_TREE handle
 
 }  // namespace machip
 
@@ -239,11 +240,11 @@ struct machip_esp {
     int device = 0;
     hipStream_t stream = nullptr;
     int n = 0, np = 0, ld = 0, m = 0, fold = machip::kEspDefaultFold;
-    int form = 0;                 // 0 chain, 1 general (dense Gauss-Jordan inverse), 2 chain without Sigma (esp_free.h)
+    int form = 0;                 // 0 chain, 1 general (dense Gauss-Jordan inverse), 2 chain without Sigma (esp_free.h), 3 spanning tree without Sigma (esp_tree.h)
     double beta = 0.0;
-    double *R = nullptr, *part = nullptr;      // form 2: the chain's prefix resistances (n'), the column slices' partial sums
-    size_t zcap = 0;              // form 2: columns Zb / cb are allocated for (the history of the largest budget so far)
-    int free_split = 0;           // form 2: option esp_free_split when the handle was made (0 = automatic)
+    double *R = nullptr, *part = nullptr;      // form 2: the chain's prefix resistances (n'); forms 2, 3: the column slices' partial sums
+    size_t zcap = 0;              // forms 2, 3: columns Zb / cb are allocated for (the history of the largest budget so far; form 3: seeds included)
+    int free_split = 0;           // forms 2, 3: option esp_free_split when the handle was made (0 = automatic)
     double *bufA = nullptr, *bufB = nullptr;
     double* sig0 = nullptr;       // pristine Sigma0 (one of bufA / bufB)
     double* sig = nullptr;        // working copy (the other one)
@@ -256,6 +257,7 @@ struct machip_esp {
     std::vector<int32_t> hfi, hfj, hci, hcj;      // the edge lists as given (host): esp_relax.h builds its incidence list from them
     std::vector<double> hfw, hcw;
     machip::EspRelax* rx = nullptr;
+    machip::EspTreeState* tr = nullptr;
 
     machip::EspView view() const {
         machip::EspView V;

@@ -79,8 +79,9 @@ __global__ __launch_bounds__(kBlock) void k_esp_free_resist(EspView V, const dou
 
 // ---- the z of the step's winner.  grid = (ceil(ld / 512), S); slice s = blockIdx.y owns the columns [s per, (s + 1) per) of the j
 // in the history.  SPLIT = false (S = 1): z into Zb[:, j], workgroup 0 records the step.  SPLIT = true: the slice's partial sum
-// into part[s ld ..]; k_esp_free_zsum finishes. ----
-template <bool SPLIT>
+// into part[s ld ..]; k_esp_free_zsum finishes.  LOADED (esp_tree.h): `R` is not the chain's prefix sums but the Sigma0 row
+// difference itself (ld doubles, written by k_esp_tree_row) and slice 0 starts its chain from that value; nothing else differs. ----
+template <bool SPLIT, bool LOADED = false>
 __global__ __launch_bounds__(kBlock) void k_esp_free_z(EspView V, const double* __restrict__ R, double* __restrict__ part, int j, int k,
                                                        int per) {
     __shared__ double alpha[kEspFreeChunk];
@@ -92,7 +93,13 @@ __global__ __launch_bounds__(kBlock) void k_esp_free_z(EspView V, const double* 
     const int i = 2 * (blockIdx.x * kBlock + threadIdx.x);      // rows i, i + 1 (ld is a multiple of 64)
     const bool in = i < V.ld;
     double z0 = 0.0, z1 = 0.0;
-    if (s == 0 && in) {
+    if (LOADED) {
+        if (s == 0 && in) {
+            const double2 x = *reinterpret_cast<const double2*>(R + i);
+            z0 = x.x;
+            z1 = x.y;
+        }
+    } else if (s == 0 && in) {
         if (i < V.np) z0 = esp_free_sig0(R, u, i) - esp_free_sig0(R, v, i);
         if (i + 1 < V.np) z1 = esp_free_sig0(R, u, i + 1) - esp_free_sig0(R, v, i + 1);
     }

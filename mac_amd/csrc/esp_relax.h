@@ -192,7 +192,7 @@ inline int esp_relax_read(machip_esp* h, int np, double* out3) {
 
 // First relaxation call on a handle: the third buffer, the incidence list, log det M(0).
 inline int esp_relax_prepare(machip_esp* h) {
-    if (h->form == kEspFormFree)
+    if (h->form == kEspFormFree || h->tr)      // (tr: a MACHIP_ESP_MATRIX_FREE | MACHIP_ESP_SPANNING_TREE handle, esp_tree.h)
         return fail(MACHIP_BAD_ARG, "the relaxation inverts the dense M(x): not available on a MACHIP_ESP_MATRIX_FREE handle");
     if (h->n > kEspDenseMaxN)
         return fail(MACHIP_BAD_ARG, "the relaxation inverts the dense M(x) (no chain closed form): num_nodes must be <= 16384");

@@ -18,6 +18,7 @@
 #include "solver.h"
 #include "esp.h"
 #include "esp_free.h"
+#include "esp_tree.h"
 #include "esp_relax.h"
 #include "eig.h"
 
@@ -1572,8 +1573,10 @@ int machip_esp_create(int device, int64_t n, int64_t n_fixed, const int32_t* fi,
     const int fold_given = fold;
     if (fold == 0) fold = kEspDefaultFold;
     if (fold < 1 || fold > kEspMaxFold) return fail(MACHIP_BAD_ARG, "fold must be in [1, 256]");
-    if (flags & ~(MACHIP_ESP_DENSE_INVERSE | MACHIP_ESP_MATRIX_FREE)) return fail(MACHIP_BAD_ARG, "unknown flags");
-    const bool mfree = (flags & MACHIP_ESP_MATRIX_FREE) != 0;
+    if (flags & ~(MACHIP_ESP_DENSE_INVERSE | MACHIP_ESP_MATRIX_FREE | MACHIP_ESP_SPANNING_TREE)) return fail(MACHIP_BAD_ARG, "unknown flags");
+    const bool mfree = (flags & MACHIP_ESP_MATRIX_FREE) != 0, tree = (flags & MACHIP_ESP_SPANNING_TREE) != 0;
+    if (tree && !mfree)
+        return fail(MACHIP_BAD_ARG, "MACHIP_ESP_SPANNING_TREE selects the spanning tree of the matrix-free route: it is valid only together with MACHIP_ESP_MATRIX_FREE");
     if (mfree && fold_given != 0)      // (an argument that would be ignored is refused, not dropped: nothing is ever folded here)
         return fail(MACHIP_BAD_ARG, "MACHIP_ESP_MATRIX_FREE never folds: fold has no meaning on this route and must be 0");
     if (mfree && (flags & MACHIP_ESP_DENSE_INVERSE))
@@ -1597,6 +1600,8 @@ int machip_esp_create(int device, int64_t n, int64_t n_fixed, const int32_t* fi,
         const int a = root(fi[e]), b = root(fj[e]);
         if (a != b) { par[a] = b; --comps; }
     }
+    if (tree && comps > 1)
+        return fail(MACHIP_BAD_ARG, "the spanning-tree route needs a connected fixed graph: the fixed edges leave " + std::to_string(comps) + " components");
     double beta = 0.0;
     if (comps > 1) {
         for (int i = 1; i < N; ++i)
@@ -1605,21 +1610,23 @@ int machip_esp_create(int device, int64_t n, int64_t n_fixed, const int32_t* fi,
     }
     // chain form: F is exactly the path (i, i+1), parallel links summed
     std::vector<double> link((size_t)np, 0.0);
-    bool chain = !(flags & MACHIP_ESP_DENSE_INVERSE) && comps == 1;
+    bool chain = !(flags & MACHIP_ESP_DENSE_INVERSE) && comps == 1 && !tree;
     for (int64_t e = 0; chain && e < n_fixed; ++e) {
         const int a = std::min(fi[e], fj[e]), b = std::max(fi[e], fj[e]);
         if (b != a + 1) chain = false;
         else link[(size_t)a] += fw[e];
     }
     for (int i = 0; chain && i < np; ++i) if (!(link[(size_t)i] > 0.0)) chain = false;
-    if (mfree && !chain)
+    EspTreePlan tplan;
+    if (tree) ST_TRY(esp_tree_plan(n, n_fixed, fi, fj, fw, tplan));
+    if (mfree && !tree && !chain)
         return fail(MACHIP_BAD_ARG, "the matrix-free route needs a chain: the fixed edges must be exactly the connected path (i, i+1), i = 0..n-2 (parallel links summed)");
-    if (!chain && n > kEspDenseMaxN)
+    if (!chain && !tree && n > kEspDenseMaxN)
         return fail(MACHIP_BAD_ARG, "GreedyESP inverts L_red + beta I densely when the fixed edges are not exactly the chain (i, i+1): num_nodes must be <= 16384");
     if (machip_device_count() <= 0) return fail(MACHIP_NO_DEVICE, "no HIP device visible");
     HIP_TRY(hipSetDevice(device));
     machip_esp* h = new machip_esp();
-    h->device = device; h->n = N; h->np = np; h->m = (int)m; h->fold = mfree ? 0 : fold; h->beta = beta; h->form = mfree ? kEspFormFree : chain ? 0 : 1;
+    h->device = device; h->n = N; h->np = np; h->m = (int)m; h->fold = mfree ? 0 : fold; h->beta = beta; h->form = tree ? kEspFormTree : mfree ? kEspFormFree : chain ? 0 : 1;
     h->free_split = (int)std::max(0l, std::min<long>(default_options().get(kOpt_esp_free_split, 0), kEspFreeMaxSplit));
     h->ld = (np + kGjT - 1) / kGjT * kGjT;
     h->hfi.assign(fi, fi + n_fixed); h->hfj.assign(fj, fj + n_fixed); h->hfw.assign(fw, fw + n_fixed);
@@ -1646,6 +1653,7 @@ int machip_esp_create(int device, int64_t n, int64_t n_fixed, const int32_t* fi,
             HIP_TRY(hipMemcpyAsync(h->cw, cw, sizeof(double) * (size_t)m, hipMemcpyHostToDevice, h->stream));
             HIP_TRY(hipStreamSynchronize(h->stream));     // (host staging goes out of scope)
         }
+        if (tree) return esp_tree_upload(h, tplan);      // the tables are all of Sigma0 this route keeps; the seeds run at the first use
         if (chain) {
             std::vector<double> R((size_t)np);
             double acc = 0.0;
@@ -1721,10 +1729,33 @@ void machip_esp_destroy(machip_esp* h) {
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     for (hipEvent_t e : h->ev) (void)hipEventDestroy(e);
     esp_relax_release(h);
+    esp_tree_release(h);
     void* bufs[] = {h->bufA, h->bufB, h->cu, h->cv, h->sel, h->pi, h->order, h->bad, h->cw, h->s, h->Zb, h->cb, h->pv, h->gain, h->piv, h->best, h->R, h->part};
     for (void* q : bufs) if (q) (void)hipFree(q);
     if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
+}
+
+int machip_esp_tree_plan(int64_t n, int64_t n_fixed, const int32_t* fi, const int32_t* fj, const double* fw, int32_t* parent,
+                         double* R, int32_t* pre, int32_t* end, int64_t* n_seeds, int32_t* su, int32_t* sv, double* sw) {
+    if (!parent || !R || !pre || !end || !n_seeds || (n_fixed > 0 && (!su || !sv || !sw))) return fail(MACHIP_BAD_ARG, "NULL output");
+    EspTreePlan P;
+    ST_TRY(esp_tree_plan(n, n_fixed, fi, fj, fw, P));
+    std::copy(P.parent.begin(), P.parent.end(), parent);
+    std::copy(P.R.begin(), P.R.end(), R);
+    std::copy(P.pre.begin(), P.pre.end(), pre);
+    std::copy(P.end.begin(), P.end.end(), end);
+    *n_seeds = (int64_t)P.sw.size();
+    std::copy(P.su.begin(), P.su.end(), su);
+    std::copy(P.sv.begin(), P.sv.end(), sv);
+    std::copy(P.sw.begin(), P.sw.end(), sw);
+    return MACHIP_OK;
+}
+
+int machip_esp_seeds(machip_esp* h, int64_t* seeds_out) {
+    if (!h || !seeds_out) return fail(MACHIP_BAD_ARG, "NULL handle or output");
+    *seeds_out = h->tr ? h->tr->seeds : 0;
+    return MACHIP_OK;
 }
 
 int machip_esp_info(machip_esp* h, int32_t* info4, double* beta) {
@@ -1749,8 +1780,8 @@ int machip_esp_select(machip_esp* h, int nb, const int64_t* ks, int32_t* order_o
     }
     const int K = (int)ks[nb - 1], B = h->fold, P = h->grid_m(), zg = (h->ld + kBlock - 1) / kBlock;
     hipStream_t st = h->stream;
-    if (h->form == kEspFormFree) {
-        ST_TRY(esp_free_select(h, nb, ks));
+    if (h->form == kEspFormFree || h->form == kEspFormTree) {
+        ST_TRY(h->form == kEspFormTree ? esp_tree_select(h, nb, ks) : esp_free_select(h, nb, ks));
         return esp_select_finish(h, nb, K, order_out, gain_out, t_ms_out);
     }
     const EspView V = h->view();
@@ -1798,6 +1829,13 @@ static int esp_select_finish(machip_esp* h, int nb, int K, int32_t* order_out, d
 int machip_esp_weighted_resistances(machip_esp* h, double* r_out) {
     if (!h || (!r_out && h->m)) return fail(MACHIP_BAD_ARG, "NULL handle or output");
     HIP_TRY(hipSetDevice(h->device));
+    if (h->form == kEspFormTree) {
+        ST_TRY(esp_tree_resist(h));
+        HIP_TRY(hipGetLastError());
+        if (h->m) HIP_TRY(hipMemcpyAsync(r_out, h->s, sizeof(double) * (size_t)h->m, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        return MACHIP_OK;
+    }
     double* S = h->live ? h->sig : h->sig0;
     if (h->form != kEspFormFree && h->live && h->pending) { h->fold_into(S, h->pending); h->pending = 0; }
     if (h->m) {
@@ -1893,6 +1931,8 @@ int machip_eig_create(int device, int64_t n, int64_t n_fixed, const int32_t* fi,
     if (batch < 1 || batch > kEigMaxBatch) return fail(MACHIP_BAD_ARG, "batch must be in [1, 4096]");
     if (flags & MACHIP_ESP_MATRIX_FREE)
         return fail(MACHIP_BAD_ARG, "GreedyEig solves against the dense inverse: MACHIP_ESP_MATRIX_FREE is not available here");
+    if (flags & MACHIP_ESP_SPANNING_TREE)
+        return fail(MACHIP_BAD_ARG, "GreedyEig solves against the dense inverse: MACHIP_ESP_SPANNING_TREE is not available here");
     machip_esp* base = nullptr;
     ST_TRY(machip_esp_create(device, n, n_fixed, fi, fj, fw, m, ci, cj, cw, fold, flags, &base));
     if (base->beta != 0.0) {

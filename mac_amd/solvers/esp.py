@@ -23,12 +23,14 @@ from mac_amd.utils.graphs import Edge, edges_to_arrays, weight_reduced_graph_lap
 
 class GreedyESP:
     def __init__(self, fixed_edges: List[Edge], candidate_edges: List[Edge], num_nodes: int, lazy: bool = False, *,
-                 device: int = 0, fold: int = 64, dense_inverse: bool = False, matrix_free: bool = False):
+                 device: int = 0, fold: int = 64, dense_inverse: bool = False, matrix_free=False):
         """Arguments as mac/solvers/greedy_esp.py of the reference, plus keyword-only ``device`` (GPU ordinal), ``fold``
         (pending rank-1 updates folded into the inverse every ``fold`` picks, 1..256) and ``dense_inverse`` (build the
         inverse by dense Gauss-Jordan even when the fixed edges are a chain: cross-checks) and ``matrix_free`` (chain-fixed
         graphs only: no dense inverse, no folds (``fold`` is not used) and no limit on num_nodes; the picks' updates are kept as a history of num_nodes x k
-        doubles, so the route is for k << num_nodes -- DESIGN section 14).  Raises Disconnected when the fixed graph is
+        doubles, so the route is for k << num_nodes -- DESIGN section 14; ``matrix_free="tree"``: the same route for any
+        connected fixed graph, from a spanning tree of it plus one history column per fixed link outside the tree -- DESIGN
+        section 15).  Raises Disconnected when the fixed graph is
         disconnected and a node other than 0 has no fixed edge (the reference re-raises CHOLMOD's error)."""
         if num_nodes == 0:
             assert len(fixed_edges) == len(candidate_edges) == 0
@@ -86,5 +88,5 @@ class GreedyESP:
         return self._dev.weighted_resistances()
 
     def info(self) -> dict:
-        """How the inverse was built: form ("chain" / "dense" / "chain_free"), leading dimension, fold, pending updates, beta."""
+        """How the inverse was built: form ("chain" / "dense" / "chain_free" / "tree_free"), leading dimension, fold, pending updates, beta, seeds."""
         return self._dev.info()
