@@ -17,7 +17,8 @@ changes that one line (examples/g2o_experiment.py: ``from mac.solvers.greedy_esp
 ``from mac.solvers import GreedyESP``).  GreedyEig is provided both ways, ``from mac.solvers import GreedyEig`` and the
 reference's own ``from mac.solvers.greedy_eig import GreedyEig`` (``mac_amd/solvers/greedy_eig.py``, on the GPU).
 ESPRelaxation (no counterpart in the reference: the convex relaxation GreedyESP's paper pairs the greedy with) is
-``from mac.solvers import ESPRelaxation`` (``mac_amd/solvers/esp_relax.py``).
+``from mac.solvers import ESPRelaxation`` (``mac_amd/solvers/esp_relax.py``); ``ESPRelaxation(..., edge_space=True)`` is its
+candidate-space form for chain-fixed graphs of any length.
 ``mac.utils.cholesky`` (the reference's CHOLMOD wrapper) is not provided: importing it raises ImportError, as it does in the
 reference without its optional SuiteSparse dependency.
 """

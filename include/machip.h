@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define MACHIP_ABI_VERSION 11   /* 11: MACHIP_ESP_SPANNING_TREE (the matrix-free route of GreedyESP for any connected fixed graph; machip_esp_tree_plan, machip_esp_seeds); 10: MACHIP_ESP_MATRIX_FREE (GreedyESP on a chain without a dense Sigma, option esp_free_split); 9: the relaxation of GreedyESP's problem (machip_esp_relax_*); 8: GreedyEig handle (machip_eig_*); 7: GreedyESP handle (machip_esp_*); 6: machip_solve_stats.drift, machip_panel_plan fills 12 entries; 5: per-handle option table (machip_set_option), machip_comm_drop_ipc; 4: inter-process communicator */
+#define MACHIP_ABI_VERSION 12   /* 12: MACHIP_ESP_EDGE_RELAX (the relaxation in the candidates' space on a chain-fixed graph; machip_esp_relax_info); 11: MACHIP_ESP_SPANNING_TREE (the matrix-free route of GreedyESP for any connected fixed graph; machip_esp_tree_plan, machip_esp_seeds); 10: MACHIP_ESP_MATRIX_FREE (GreedyESP on a chain without a dense Sigma, option esp_free_split); 9: the relaxation of GreedyESP's problem (machip_esp_relax_*); 8: GreedyEig handle (machip_eig_*); 7: GreedyESP handle (machip_esp_*); 6: machip_solve_stats.drift, machip_panel_plan fills 12 entries; 5: per-handle option table (machip_set_option), machip_comm_drop_ipc; 4: inter-process communicator */
 
 typedef enum machip_status {
     MACHIP_OK = 0,
@@ -368,8 +368,8 @@ typedef struct machip_esp machip_esp;
  * No limit on n but memory and int32 node ids; a K whose history does not fit in free device memory is MACHIP_BAD_ARG, decided
  * before anything is allocated.  Pick j streams 8 ld j bytes (about 4 ld K^2 over a run): the route is for K << n.  Same rule, tie
  * rule and per-entry arithmetic as the dense forms; the sums over the history run in a fixed order that depends on (ld, j, option
- * esp_free_split) alone, so runs repeat bit for bit and agree with the dense chain form to rounding.  machip_esp_relax_* and
- * machip_eig_create answer MACHIP_BAD_ARG on this route. */
+ * esp_free_split) alone, so runs repeat bit for bit and agree with the dense chain form to rounding.  machip_esp_relax_* (unless
+ * the handle was made with MACHIP_ESP_EDGE_RELAX as well) and machip_eig_create answer MACHIP_BAD_ARG on this route. */
 #define MACHIP_ESP_MATRIX_FREE 2
 /* flags, valid only together with MACHIP_ESP_MATRIX_FREE (MACHIP_BAD_ARG alone, with MACHIP_ESP_DENSE_INVERSE or with fold != 0):
  * the matrix-free route for ANY connected fixed graph (mac_amd/csrc/esp_tree.h).  Sigma0 is that of the spanning tree T that
@@ -381,6 +381,11 @@ typedef struct machip_esp machip_esp;
  * feeds the history's sums the doubles MACHIP_ESP_MATRIX_FREE alone feeds them and returns the same bits.  machip_esp_relax_* and
  * machip_eig_create answer MACHIP_BAD_ARG on this route. */
 #define MACHIP_ESP_SPANNING_TREE 8
+/* flags, valid only together with MACHIP_ESP_MATRIX_FREE (MACHIP_BAD_ARG alone, with MACHIP_ESP_DENSE_INVERSE, with
+ * MACHIP_ESP_SPANNING_TREE, or on a fixed graph that is not the connected chain): the handle is a MACHIP_ESP_MATRIX_FREE handle
+ * -- machip_esp_select and machip_esp_weighted_resistances work exactly as without this flag -- on which machip_esp_relax_* run in
+ * the space of the m candidates instead of the n - 1 nodes (mac_amd/csrc/esp_relax_edge.h; the text above machip_esp_relax_eval). */
+#define MACHIP_ESP_EDGE_RELAX 16
 /* fold: pending rank-1 updates folded into Sigma every `fold` steps (1..256; 0 = 64).  Builds Sigma0. */
 int machip_esp_create(int device, int64_t n, int64_t n_fixed, const int32_t* fi, const int32_t* fj, const double* fw,
                       int64_t m, const int32_t* ci, const int32_t* cj, const double* cw, int fold, int flags, machip_esp** out);
@@ -417,7 +422,18 @@ int machip_esp_seeds(machip_esp* h, int64_t* seeds_out);
  * MACHIP_BAD_ARG beyond.  The first relaxation call on a handle allocates a third ld x ld buffer (Sigma0 stays untouched:
  * machip_esp_select afterwards returns what it returns on a fresh handle) and evaluates log det M(0).  A relaxation call
  * overwrites the working copy of the last selection run: machip_esp_weighted_resistances then refers to the fixed graph again.
- * x outside [0, 1] or not finite, k <= 0, k > m: MACHIP_BAD_ARG (machip_last_error says which). */
+ * x outside [0, 1] or not finite, k <= 0, k > m: MACHIP_BAD_ARG (machip_last_error says which).
+ *
+ * On a handle made with MACHIP_ESP_EDGE_RELAX the same three entry points work in edge space.  With R[v] the chain's resistance
+ * from node 0 to v, candidate e oriented lo_e <= hi_e, G_ef = max(0, R[min(hi_e, hi_f)] - R[max(lo_e, lo_f)]) (the resistance of
+ * the overlap of two chain intervals), D = diag(w_e x_e) and N(x) = I + G D (m x m, not symmetric, leading principal minors
+ * positive on all of [0, 1]^m):
+ *     F(x) = log det N(x)   (the matrix determinant lemma; F(0) = log 1 = 0 exactly),   dF/dx_e = w_e [N(x)^-1 G]_ee.
+ * Every evaluation assembles N(x) (leading dimension m rounded up to 64, identity beyond m), inverts it by the same blocked
+ * Gauss-Jordan elimination and takes F from its pivots; the LP vertex, the step, the stop rules, the tie rule, the argument
+ * checks and the outputs are those above, and runs repeat bit for bit.  Limit: m <= 16384 (MACHIP_BAD_ARG at the first relaxation
+ * call, before anything is allocated); none on n.  The first call allocates two ld x ld buffers; nothing of size n is allocated and
+ * nothing the greedy keeps (its history, what machip_esp_weighted_resistances reports) is touched. */
 /* F(x) and, when grad_out is not NULL, the gradient (m doubles). */
 int machip_esp_relax_eval(machip_esp* h, const double* x, double* F_out, double* grad_out);
 /* Frank-Wolfe from x_inout with the open-loop step 2 / (2 + t), t = 0, 1, ...: per iteration F, the dual value F + g.(s - x)
@@ -431,6 +447,9 @@ int machip_esp_relax_run(machip_esp* h, int64_t k, int max_iters, double gap_tol
  * F + inner(g, s - x) reproduces machip_esp_relax_run's dual values, and with them its upper bound, bit for bit (a host dot
  * product sums in another order and agrees to rounding only). */
 int machip_esp_relax_inner(machip_esp* h, const double* a, const double* b, double* out);
+/* info2 = {the space the relaxation of this handle works in (0: nodes, M(x); 1: candidates, N(x), MACHIP_ESP_EDGE_RELAX), the
+ * leading dimension of the matrix it inverts (0 before the first relaxation call on a node-space handle)}. */
+int machip_esp_relax_info(machip_esp* h, int32_t* info2);
 
 /* GreedyEig (mac/solvers/greedy_eig.py of the reference: the greedy k-edge selection by algebraic connectivity; mac_amd/csrc/eig.h).
  * Every pick evaluates lambda_2(L_cur + w_e a_e a_e^T) for the unselected candidates whose supergradient bound

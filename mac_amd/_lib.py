@@ -113,6 +113,7 @@ SIGNATURES = {
     "machip_esp_relax_run": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_double, C.c_double, _f64p, _f64p, _f64p, _f64p,
                                        C.POINTER(C.c_int), C.POINTER(C.c_double)]),
     "machip_esp_relax_inner": (C.c_int, [C.c_void_p, _f64p, _f64p, C.POINTER(C.c_double)]),
+    "machip_esp_relax_info": (C.c_int, [C.c_void_p, _i32p]),
     "machip_eig_create": (C.c_int, [C.c_int, C.c_int64, C.c_int64, _i32p, _i32p, _f64p, C.c_int64, _i32p, _i32p, _f64p,
                                     C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "machip_eig_destroy": (None, [C.c_void_p]),
@@ -471,6 +472,7 @@ class Problem:
 ESP_DENSE_INVERSE = 1      # MACHIP_ESP_DENSE_INVERSE
 ESP_MATRIX_FREE = 2        # MACHIP_ESP_MATRIX_FREE
 ESP_SPANNING_TREE = 8      # MACHIP_ESP_SPANNING_TREE (only together with ESP_MATRIX_FREE)
+ESP_EDGE_RELAX = 16        # MACHIP_ESP_EDGE_RELAX (only together with ESP_MATRIX_FREE alone: the chain)
 
 
 def host_esp_tree(n, fi, fj, fw):
@@ -491,14 +493,19 @@ def host_esp_tree(n, fi, fj, fw):
 class Esp:
     """Owns one ``machip_esp`` handle: GreedyESP's (L_red + beta I)^-1 resident on one GPU (mac_amd/csrc/esp.h)."""
 
-    def __init__(self, n, fi, fj, fw, ci, cj, cw, fold=64, dense_inverse=False, device=0, *, matrix_free=False):
+    def __init__(self, n, fi, fj, fw, ci, cj, cw, fold=64, dense_inverse=False, device=0, *, matrix_free=False, edge_relax=False):
         """matrix_free="tree": any connected fixed graph -- a spanning tree's closed form plus one seeded history column per fixed
         link outside it (MACHIP_ESP_MATRIX_FREE | MACHIP_ESP_SPANNING_TREE, mac_amd/csrc/esp_tree.h).
         matrix_free=True: chain-fixed graphs only -- no dense inverse, the picks' updates stay in a history that ``select``
         sizes for its largest budget (MACHIP_ESP_MATRIX_FREE; the slices of its sums: process option "esp_free_split").
-        Nothing is folded on that route: ``fold`` is not passed on (the C entry point wants 0 with the flag)."""
+        Nothing is folded on that route: ``fold`` is not passed on (the C entry point wants 0 with the flag).
+        edge_relax=True (with matrix_free=True only): ``relax_eval`` / ``relax_run`` / ``relax_inner`` work in the space of the
+        m candidates instead of the n - 1 nodes (MACHIP_ESP_EDGE_RELAX, mac_amd/csrc/esp_relax_edge.h): m <= 16384, any n."""
         if not isinstance(matrix_free, (bool, np.bool_)) and matrix_free != "tree":
             raise ValueError(f'matrix_free must be False, True or "tree", not {matrix_free!r}')
+        if edge_relax and (isinstance(matrix_free, str) or not matrix_free or dense_inverse):
+            raise ValueError("edge_relax=True runs the relaxation on the chain-free handle: it needs matrix_free=True "
+                             f"(not {matrix_free!r}) and dense_inverse=False")
         lib = load()
         require_device()
         self.n = int(n)
@@ -509,6 +516,8 @@ class Esp:
         flags = (ESP_DENSE_INVERSE if dense_inverse else 0) | (ESP_MATRIX_FREE if matrix_free else 0)
         if isinstance(matrix_free, str):
             flags |= ESP_SPANNING_TREE
+        if edge_relax:
+            flags |= ESP_EDGE_RELAX
         check(lib.machip_esp_create(int(device), self.n, len(fw), p_i32(fi), p_i32(fj), p_f64(fw), self.m,
                                     p_i32(ci), p_i32(cj), p_f64(cw), 0 if matrix_free else int(fold), flags, C.byref(h)))
         self._h = h
@@ -551,6 +560,13 @@ class Esp:
         check(self._lib.machip_esp_seeds(self._h, C.byref(r)))
         return dict(form=("chain", "dense", "chain_free", "tree_free")[a[0]], ld=int(a[1]), fold=int(a[2]), pending=int(a[3]),
                     beta=b.value, seeds=int(r.value))
+
+    def relax_info(self):
+        """dict(form = "node" | "edge", ld): the space the relaxation works in and the leading dimension of the matrix it inverts
+        (0 before the first relaxation call on a node-space handle)."""
+        a = np.zeros(2, dtype=np.int32)
+        check(self._lib.machip_esp_relax_info(self._h, p_i32(a)))
+        return dict(form=("node", "edge")[a[0]], ld=int(a[1]))
 
     def relax_eval(self, x, want_grad=True):
         """(F(x), gradient or None) of the relaxation: F = logdet M(x) - logdet M(0) (machip_esp_relax_eval)."""

@@ -240,6 +240,7 @@ struct machip_esp {
     int device = 0;
     hipStream_t stream = nullptr;
     int n = 0, np = 0, ld = 0, m = 0, fold = machip::kEspDefaultFold;
+    bool edge_relax = false;      // MACHIP_ESP_EDGE_RELAX (form 2 only): the relaxation runs in the candidates' space (esp_relax_edge.h)
     int form = 0;                 // 0 chain, 1 general (dense Gauss-Jordan inverse), 2 chain without Sigma (esp_free.h), 3 spanning tree without Sigma (esp_tree.h)
     double beta = 0.0;
     double *R = nullptr, *part = nullptr;      // form 2: the chain's prefix resistances (n'); forms 2, 3: the column slices' partial sums
@@ -272,14 +273,19 @@ struct machip_esp {
     // is in `src` afterwards (the pointers are swapped per step); *bad <- 1 on a non-positive pivot.  LD: the pivot blocks'
     // log-determinants into ldet[ld / 32] as well.
     template <bool LD>
-    void gj_inverse(double*& src, double*& dst, double* ldet = nullptr) {
+    void gj_inverse(double*& src, double*& dst, double* ldet = nullptr) { gj_inverse_of<LD>(src, dst, ld, piv, ldet); }
+
+    // The same for a matrix of leading dimension `ldm` (a multiple of 64) with the look-ahead pivot buffer `pv2` (2 x 32 x 32
+    // doubles): the handle's own (ld, piv) above, the edge-space relaxation's (esp_relax_edge.h).
+    template <bool LD>
+    void gj_inverse_of(double*& src, double*& dst, int ldm, double* pv2, double* ldet) {
         using namespace machip;
-        const int tiles = ld / kGjT;
-        const bool look = ld >= kEspGjLookMin;
-        for (int kb = 0, k = 0; kb < ld; kb += kGjB, ++k) {
-            if (look) k_gj_step<0, LD><<<dim3(tiles, tiles), 256, 0, stream>>>(src, dst, ld, kb, bad, k ? piv + (size_t)(k & 1) * kGjB * kGjB : nullptr,
-                                                                               piv + (size_t)((k + 1) & 1) * kGjB * kGjB, ldet);
-            else k_gj_step<0, LD><<<dim3(tiles, tiles), 256, 0, stream>>>(src, dst, ld, kb, bad, nullptr, nullptr, ldet);
+        const int tiles = ldm / kGjT;
+        const bool look = ldm >= kEspGjLookMin;
+        for (int kb = 0, k = 0; kb < ldm; kb += kGjB, ++k) {
+            if (look) k_gj_step<0, LD><<<dim3(tiles, tiles), 256, 0, stream>>>(src, dst, ldm, kb, bad, k ? pv2 + (size_t)(k & 1) * kGjB * kGjB : nullptr,
+                                                                               pv2 + (size_t)((k + 1) & 1) * kGjB * kGjB, ldet);
+            else k_gj_step<0, LD><<<dim3(tiles, tiles), 256, 0, stream>>>(src, dst, ldm, kb, bad, nullptr, nullptr, ldet);
             std::swap(src, dst);
         }
     }

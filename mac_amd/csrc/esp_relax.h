@@ -18,12 +18,16 @@
 //      machip_lp_topk: ties at the k-th value go to the lowest indices);
 //   6. k_fw_final (partials of g.(s - x) and g.g, x_next = x + gamma (s - x)) and k_relax_scalars (F, dual, |g|).
 // The host reads three scalars and the pivot flag per iteration (the stop tests), nothing else.
+//
+// On a MACHIP_ESP_EDGE_RELAX handle steps 1-4 are those of esp_relax_edge.h instead -- N(x) = I + G D in the candidates' space,
+// its inverse and the gradient from it -- and steps 5-6, the reading of the scalars and the loop are the ones here.
 #pragma once
 #include <algorithm>
 #include <cmath>
 #include <vector>
 
 #include "esp.h"
+#include "esp_relax_edge.h"
 #include "kernels.h"
 
 namespace machip {
@@ -37,6 +41,8 @@ struct EspRelax {
     SelState* st = nullptr;
     unsigned int* hist = nullptr;
     double logdet0 = 0.0;                    // log det M(0), by the same kernels in the same order (F(0) = 0 exactly)
+    int ld = 0;                              // leading dimension of the matrix an evaluation inverts (node space: the handle's)
+    EspEdge* ed = nullptr;                   // edge space (esp_relax_edge.h): N(x) instead of M(x); bufC .. tw above stay unused
 };
 
 // Row i of M(x): zeros, then entry q in [rowptr[i], rowptr[i + 1]) at column ecol[q] = sum over its terms t in
@@ -100,6 +106,7 @@ inline void esp_relax_release(machip_esp* h) {
     if (!r) return;
     void* bufs[] = {r->bufC, r->rowptr, r->ecol, r->tptr, r->tx, r->tw, r->xa, r->xb, r->part, r->ldet, r->scal, r->st, r->hist};
     for (void* q : bufs) if (q) (void)hipFree(q);
+    esp_edge_release(r->ed);
     delete r;
     h->rx = nullptr;
 }
@@ -148,6 +155,7 @@ inline int esp_relax_build_lists(machip_esp* h, EspRelax* r) {
 // gone, Sigma0 is not touched), the blocks' log-determinants in ldet[], the gradient in h->s (want_grad).
 inline int esp_relax_eval_on(machip_esp* h, const double* x, bool want_grad) {
     EspRelax* r = h->rx;
+    if (r->ed) return esp_edge_eval_on(h, r->ed, x, r->ldet, want_grad);
     hipStream_t st = h->stream;
     h->live = false;
     h->pending = 0;
@@ -167,6 +175,7 @@ inline int esp_relax_select(machip_esp* h, long k) {
     if (m <= kSelSmallMax) {
         k_sel_small<<<1, 1024, 0, h->stream>>>(h->s, m, (long long)k, r->st, 0);
     } else {
+        if (!r->hist) return fail(MACHIP_BAD_ARG, "the multi-launch select has no histogram on this handle (edge space allocates none: m <= 16384 must stay below kSelSmallMax)");
         constexpr int B = 1024, U = 4;
         const int grid = (int)std::max<long>(1, std::min<long>(128, (m + (long)B * U - 1) / ((long)B * U)));
         k_sel_init<<<1, 1024, 0, h->stream>>>(r->st, (long long)k, r->hist, 6 * kBins);
@@ -181,31 +190,56 @@ inline int esp_relax_select(machip_esp* h, long k) {
 inline int esp_relax_read(machip_esp* h, int np, double* out3) {
     EspRelax* r = h->rx;
     int hbad = 0;
-    k_relax_scalars<<<1, kBlock, 0, h->stream>>>(r->ldet, h->ld / kGjB, r->logdet0, r->part, np, r->scal);
+    k_relax_scalars<<<1, kBlock, 0, h->stream>>>(r->ldet, r->ld / kGjB, r->logdet0, r->part, np, r->scal);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(out3, r->scal, sizeof(double) * 3, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipMemcpyAsync(&hbad, h->bad, sizeof(int), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
+    if (hbad && r->ed) return fail(MACHIP_NOT_CONVERGED, "N(x) = I + G D has a non-positive Gauss-Jordan pivot (its leading minors are positive: lost numerically)");
     if (hbad) return fail(MACHIP_NOT_CONVERGED, "M(x) is not positive definite numerically (a non-positive Gauss-Jordan pivot)");
     return MACHIP_OK;
 }
 
-// First relaxation call on a handle: the third buffer, the incidence list, log det M(0).
-inline int esp_relax_prepare(machip_esp* h) {
+// What the relaxation cannot do on this handle, decided from the handle alone (nothing is allocated before it is asked).
+inline int esp_relax_limits(const machip_esp* h) {
+    if (h->edge_relax) {
+        if (h->m > kEspDenseMaxN)
+            return fail(MACHIP_BAD_ARG, "MACHIP_ESP_EDGE_RELAX inverts the dense m x m N(x): the number of candidates must be <= 16384 (m = " +
+                                            std::to_string(h->m) + ")");
+        return MACHIP_OK;
+    }
     if (h->form == kEspFormFree || h->tr)      // (tr: a MACHIP_ESP_MATRIX_FREE | MACHIP_ESP_SPANNING_TREE handle, esp_tree.h)
         return fail(MACHIP_BAD_ARG, "the relaxation inverts the dense M(x): not available on a MACHIP_ESP_MATRIX_FREE handle");
     if (h->n > kEspDenseMaxN)
         return fail(MACHIP_BAD_ARG, "the relaxation inverts the dense M(x) (no chain closed form): num_nodes must be <= 16384");
+    return MACHIP_OK;
+}
+
+// First relaxation call on a handle.  Node space: the third buffer, the incidence list, log det M(0).  Edge space: the state of
+// esp_relax_edge.h (log det N(0) = log det I = 0: nothing to evaluate).
+inline int esp_relax_prepare(machip_esp* h) {
+    ST_TRY(esp_relax_limits(h));
     HIP_TRY(hipSetDevice(h->device));
     if (h->rx) return MACHIP_OK;
     EspRelax* r = new EspRelax();
     h->rx = r;
     auto body = [&]() -> int {
-        const size_t ld = (size_t)h->ld, ms = (size_t)std::max(h->m, 1);
-        ST_TRY(dev_alloc(&r->bufC, ld * ld));
+        if (h->edge_relax) {
+            r->ed = new EspEdge();
+            ST_TRY(esp_edge_prepare(h, r->ed));
+        }
+        r->ld = r->ed ? r->ed->ld : h->ld;
+        const size_t ld = (size_t)r->ld, ms = (size_t)std::max(h->m, 1);
+        if (!r->ed) ST_TRY(dev_alloc(&r->bufC, ld * ld));
         ST_TRY(dev_alloc(&r->xa, ms)); ST_TRY(dev_alloc(&r->xb, ms));
         ST_TRY(dev_alloc(&r->part, (size_t)2 * kMaxGrid)); ST_TRY(dev_alloc(&r->ldet, ld / kGjB)); ST_TRY(dev_alloc(&r->scal, 4));
-        ST_TRY(dev_alloc(&r->st, 1)); ST_TRY(dev_alloc(&r->hist, (size_t)6 * kBins));
+        ST_TRY(dev_alloc(&r->st, 1));
+        if (r->ed) {                             // (m <= 16 384 is below kSelSmallMax: the multi-launch select's histogram is never used)
+            // log det N(0) = 0 in every block: what k_relax_scalars sums when machip_esp_relax_inner is the handle's first call
+            HIP_TRY(hipMemsetAsync(r->ldet, 0, sizeof(double) * (ld / kGjB), h->stream));
+            return MACHIP_OK;
+        }
+        ST_TRY(dev_alloc(&r->hist, (size_t)6 * kBins));
         ST_TRY(esp_relax_build_lists(h, r));
         HIP_TRY(hipMemsetAsync(r->xa, 0, sizeof(double) * ms, h->stream));
         ST_TRY(esp_relax_eval_on(h, r->xa, false));

@@ -1573,8 +1573,15 @@ int machip_esp_create(int device, int64_t n, int64_t n_fixed, const int32_t* fi,
     const int fold_given = fold;
     if (fold == 0) fold = kEspDefaultFold;
     if (fold < 1 || fold > kEspMaxFold) return fail(MACHIP_BAD_ARG, "fold must be in [1, 256]");
-    if (flags & ~(MACHIP_ESP_DENSE_INVERSE | MACHIP_ESP_MATRIX_FREE | MACHIP_ESP_SPANNING_TREE)) return fail(MACHIP_BAD_ARG, "unknown flags");
+    if (flags & ~(MACHIP_ESP_DENSE_INVERSE | MACHIP_ESP_MATRIX_FREE | MACHIP_ESP_SPANNING_TREE | MACHIP_ESP_EDGE_RELAX)) return fail(MACHIP_BAD_ARG, "unknown flags");
     const bool mfree = (flags & MACHIP_ESP_MATRIX_FREE) != 0, tree = (flags & MACHIP_ESP_SPANNING_TREE) != 0;
+    const bool edge = (flags & MACHIP_ESP_EDGE_RELAX) != 0;
+    if (edge && !mfree)      // (alone the bit was an unknown flag before the route existed, and stays one: the message keeps saying so)
+        return fail(MACHIP_BAD_ARG, "unknown flags: MACHIP_ESP_EDGE_RELAX puts the relaxation on the chain-free handle and is valid only together with MACHIP_ESP_MATRIX_FREE");
+    if (edge && (flags & MACHIP_ESP_DENSE_INVERSE))
+        return fail(MACHIP_BAD_ARG, "MACHIP_ESP_EDGE_RELAX takes Sigma0 from the chain's closed form: it cannot be combined with MACHIP_ESP_DENSE_INVERSE");
+    if (edge && tree)
+        return fail(MACHIP_BAD_ARG, "MACHIP_ESP_EDGE_RELAX has the chain's closed form only: it cannot be combined with MACHIP_ESP_SPANNING_TREE");
     if (tree && !mfree)
         return fail(MACHIP_BAD_ARG, "MACHIP_ESP_SPANNING_TREE selects the spanning tree of the matrix-free route: it is valid only together with MACHIP_ESP_MATRIX_FREE");
     if (mfree && fold_given != 0)      // (an argument that would be ignored is refused, not dropped: nothing is ever folded here)
@@ -1620,13 +1627,15 @@ int machip_esp_create(int device, int64_t n, int64_t n_fixed, const int32_t* fi,
     EspTreePlan tplan;
     if (tree) ST_TRY(esp_tree_plan(n, n_fixed, fi, fj, fw, tplan));
     if (mfree && !tree && !chain)
-        return fail(MACHIP_BAD_ARG, "the matrix-free route needs a chain: the fixed edges must be exactly the connected path (i, i+1), i = 0..n-2 (parallel links summed)");
+        return fail(MACHIP_BAD_ARG, std::string("the matrix-free route needs a chain: the fixed edges must be exactly the connected path (i, i+1), i = 0..n-2 (parallel links summed)") +
+                                        (edge ? "; MACHIP_ESP_EDGE_RELAX builds the candidates' Gram matrix from that chain's resistances" : ""));
     if (!chain && !tree && n > kEspDenseMaxN)
         return fail(MACHIP_BAD_ARG, "GreedyESP inverts L_red + beta I densely when the fixed edges are not exactly the chain (i, i+1): num_nodes must be <= 16384");
     if (machip_device_count() <= 0) return fail(MACHIP_NO_DEVICE, "no HIP device visible");
     HIP_TRY(hipSetDevice(device));
     machip_esp* h = new machip_esp();
     h->device = device; h->n = N; h->np = np; h->m = (int)m; h->fold = mfree ? 0 : fold; h->beta = beta; h->form = tree ? kEspFormTree : mfree ? kEspFormFree : chain ? 0 : 1;
+    h->edge_relax = edge;
     h->free_split = (int)std::max(0l, std::min<long>(default_options().get(kOpt_esp_free_split, 0), kEspFreeMaxSplit));
     h->ld = (np + kGjT - 1) / kGjT * kGjT;
     h->hfi.assign(fi, fi + n_fixed); h->hfj.assign(fj, fj + n_fixed); h->hfw.assign(fw, fw + n_fixed);
@@ -1870,7 +1879,7 @@ int machip_esp_relax_run(machip_esp* h, int64_t k, int max_iters, double gap_tol
     if (!h || !iters_out || !upper_out || max_iters < 0) return fail(MACHIP_BAD_ARG, "NULL handle or output, or max_iters < 0");
     *iters_out = 0;
     *upper_out = INFINITY;
-    if (h->n > kEspDenseMaxN) return esp_relax_prepare(h);      // (the limit's message, nothing allocated)
+    if (h->edge_relax ? h->m > kEspDenseMaxN : h->n > kEspDenseMaxN) return esp_relax_prepare(h);      // (the limit's message, nothing allocated)
     if (k <= 0 || k > h->m) return fail(MACHIP_BAD_ARG, "k must be in [1, m] (m = " + std::to_string(h->m) + " candidates)");
     ST_TRY(esp_relax_check_x(h, x_inout));
     ST_TRY(esp_relax_prepare(h));
@@ -1913,10 +1922,17 @@ int machip_esp_relax_inner(machip_esp* h, const double* a, const double* b, doub
         HIP_TRY(hipMemcpyAsync(r->xb, b, mb, hipMemcpyHostToDevice, h->stream));
     }
     k_relax_inner<<<grid, kBlock, 0, h->stream>>>(r->xa, r->xb, h->m, r->part);
-    k_relax_scalars<<<1, kBlock, 0, h->stream>>>(r->ldet, h->ld / kGjB, r->logdet0, r->part, grid, r->scal);
+    k_relax_scalars<<<1, kBlock, 0, h->stream>>>(r->ldet, r->ld / kGjB, r->logdet0, r->part, grid, r->scal);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(out, r->scal + 3, sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
+    return MACHIP_OK;
+}
+
+int machip_esp_relax_info(machip_esp* h, int32_t* info2) {
+    if (!h || !info2) return fail(MACHIP_BAD_ARG, "NULL handle or output");
+    info2[0] = h->edge_relax ? 1 : 0;
+    info2[1] = h->rx ? h->rx->ld : h->edge_relax ? (std::max(h->m, 1) + kGjT - 1) / kGjT * kGjT : 0;
     return MACHIP_OK;
 }
 

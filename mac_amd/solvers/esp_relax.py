@@ -23,16 +23,26 @@ from mac_amd.utils.rounding import round_madow, round_nearest
 
 
 class ESPRelaxation:
-    def __init__(self, fixed_edges: List[Edge], candidate_edges: List[Edge], num_nodes: int, *, device: int = 0):
+    def __init__(self, fixed_edges: List[Edge], candidate_edges: List[Edge], num_nodes: int, *, device: int = 0,
+                 edge_space: bool = False):
         """Arguments as GreedyESP.  The fixed graph may be disconnected as long as every node other than 0 has a fixed edge
-        (beta = 1e-4 then, as in GreedyESP); num_nodes <= 16384 (the dense M(x) is inverted per evaluation)."""
+        (beta = 1e-4 then, as in GreedyESP); num_nodes <= 16384 (the dense M(x) is inverted per evaluation).
+
+        edge_space=True: the same relaxation carried out in the space of the candidates (mac_amd/csrc/esp_relax_edge.h).  With G
+        the candidates' Gram matrix under the chain's resistances and D = diag(w x), F(x) = logdet(I + G D) and the gradient is
+        w_e [(I + G D)^-1 G]_ee: an m x m inverse per evaluation instead of an (n - 1) x (n - 1) one.  Regime: the fixed edges are
+        exactly the connected chain (i, i+1) (parallel links summed), at most 16384 candidates, any num_nodes.  Same results to
+        rounding, not the same bits: the default stays node space."""
         self.fixed_edges = fixed_edges
         self.all_candidate_edges = candidate_edges
         self.num_nodes = num_nodes
         fi, fj, fw = edges_to_arrays(fixed_edges)
         ci, cj, cw = edges_to_arrays(candidate_edges)
         self.weights = cw
-        self._dev = _lib.Esp(num_nodes, fi, fj, fw, ci, cj, cw, device=device)
+        if edge_space:
+            self._dev = _lib.Esp(num_nodes, fi, fj, fw, ci, cj, cw, device=device, matrix_free=True, edge_relax=True)
+        else:
+            self._dev = _lib.Esp(num_nodes, fi, fj, fw, ci, cj, cw, device=device)
         self.trace = []          # [(F, running upper bound, ||g||_2)] per iteration of the last solve
 
     def evaluate_objective(self, x) -> float:
@@ -72,7 +82,10 @@ class ESPRelaxation:
         return rounded, w, float(r["upper"])
 
     def info(self) -> dict:
-        """The handle's description (GreedyESP.info) plus the iterations of the last solve."""
+        """The handle's description (GreedyESP.info), the space the relaxation works in (relax_form = "node" | "edge") with the
+        leading dimension it inverts (relax_ld), and the iterations of the last solve."""
         d = self._dev.info()
+        ri = self._dev.relax_info()
+        d["relax_form"], d["relax_ld"] = ri["form"], ri["ld"]
         d["iterations"] = len(self.trace)
         return d

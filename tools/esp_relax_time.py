@@ -1,6 +1,12 @@
-"""ESPRelaxation timing (mac_amd/csrc/esp_relax.h): one JSON line per case.
+"""ESPRelaxation timing (mac_amd/csrc/esp_relax.h, esp_relax_edge.h): one JSON line per case.
 
-    python tools/esp_relax_time.py [--no-check] [case ...]      cases: intel sphere2500 city10000 (default: all)
+    python tools/esp_relax_time.py [--no-check] [--edge-space] [--no-python] [case ...]
+    cases: intel sphere2500 ais2klinik city10000 (default: intel sphere2500 city10000), and chain100k (a chain of 100 000 nodes,
+    weights U(0.5, 2), 4 000 seeded random candidates: --edge-space only, never checked on the CPU)
+
+--edge-space: ESPRelaxation(edge_space=True) -- N(x) = I + G D in the candidates' space; a fixed graph the
+route refuses (not the connected chain) gives a line with "refused", and so does chain100k without --edge-space.  --no-python:
+skip the Python-driven loop and leave its keys out of the line.
 
 K = 20 % of the candidates, naive start, 20 Frank-Wolfe iterations with the stop tests off.  run_ms = wall time of
 machip_esp_relax_run (the loop on the C side); python_ms = the same 20 iterations driven from Python: frank_wolfe over
@@ -52,15 +58,32 @@ def lp_vertex(g, k):
     return s
 
 
-def run(case, check):
-    g = np.load(os.path.join(ROOT, "tests", "golden", f"g2o_{case}.npz"))
-    n, fi, fj, fw, ci, cj, cw = int(g["n"]), g["fi"], g["fj"], g["fw"].astype(np.float64), g["ci"], g["cj"], g["cw"].astype(np.float64)
+def chain100k(n=100000, cands=4000, seed=100):
+    rng = np.random.default_rng(seed)
+    fi = np.arange(n - 1)
+    return n, fi, fi + 1, rng.uniform(0.5, 2.0, n - 1), rng.integers(0, n, cands), rng.integers(0, n, cands), rng.uniform(0.5, 2.0, cands)
+
+
+def run(case, check, edge_space=False, python_loop=True):
+    if case == "chain100k":
+        n, fi, fj, fw, ci, cj, cw = chain100k()
+        check = False
+        if not edge_space:                      # (n is beyond the node form's 16 384: there is nothing to time)
+            print(json.dumps(dict(case=case, n=n, m=len(cw), form="node", refused="chain100k is --edge-space only")), flush=True)
+            return
+    else:
+        g = np.load(os.path.join(ROOT, "tests", "golden", f"g2o_{case}.npz"))
+        n, fi, fj, fw, ci, cj, cw = int(g["n"]), g["fi"], g["fj"], g["fw"].astype(np.float64), g["ci"], g["cj"], g["cw"].astype(np.float64)
     fixed = [Edge(int(a), int(b), float(c)) for a, b, c in zip(fi, fj, fw)]
     cand = [Edge(int(a), int(b), float(c)) for a, b, c in zip(ci, cj, cw)]
     m = len(cw)
     k = int(0.2 * m)
     x0 = NaiveGreedy(cand).subset(k)
-    relax = ESPRelaxation(fixed, cand, n)
+    try:
+        relax = ESPRelaxation(fixed, cand, n, edge_space=edge_space)
+    except AssertionError as e:
+        print(json.dumps(dict(case=case, n=n, m=m, form="edge" if edge_space else "node", refused=str(e))), flush=True)
+        return
     dev = relax._dev
     t0 = time.perf_counter()
     dev.relax_eval(np.zeros(m), want_grad=False)
@@ -69,21 +92,24 @@ def run(case, check):
     t0 = time.perf_counter()
     r = dev.relax_run(k, x0, max_iters=ITERS, gap_tol=0.0, grad_tol=0.0)
     run_ms = (time.perf_counter() - t0) * 1e3
-    t0 = time.perf_counter()
-    xp, up = frank_wolfe(x0, relax.problem, lambda gr: lp_vertex(gr, k), maxiter=ITERS, relative_duality_gap_tol=0.0, grad_norm_tol=0.0)
-    python_ms = (time.perf_counter() - t0) * 1e3
+    py = {}
+    if python_loop:
+        t0 = time.perf_counter()
+        xp, up = frank_wolfe(x0, relax.problem, lambda gr: lp_vertex(gr, k), maxiter=ITERS, relative_duality_gap_tol=0.0, grad_norm_tol=0.0)
+        python_ms = (time.perf_counter() - t0) * 1e3
+        py = dict(python_ms=round(python_ms, 2), python_ms_per_iteration=round(python_ms / ITERS, 3), upper_python=float(up),
+                  python_x_equal=bool(np.array_equal(xp, r["x"])))
     t0 = time.perf_counter()
     F = relax.evaluate_objective(r["x"])
     eval_ms = (time.perf_counter() - t0) * 1e3
     info = relax.info()
-    ld = info["ld"]
-    out = dict(case=case, n=n, m=m, k=k, ld=ld, beta=info["beta"], iterations=int(r["iters"]), first_ms=round(first_ms, 2),
-               run_ms=round(run_ms, 2), ms_per_iteration=round(run_ms / ITERS, 3), python_ms=round(python_ms, 2),
-               python_ms_per_iteration=round(python_ms / ITERS, 3), eval_ms=round(eval_ms, 3),
-               bytes_assembly=8 * ld * ld, bytes_inverse=16 * ld * ld * (ld // 32), bytes_scores=52 * m,
-               model_tb_s=round((8 * ld * ld + 16 * ld * ld * (ld // 32) + 52 * m) / (run_ms / ITERS * 1e-3) / 1e12, 3),
-               F_last=float(r["f"][-1]), upper=float(r["upper"]), upper_python=float(up),
-               python_x_equal=bool(np.array_equal(xp, r["x"])))
+    ld = info["relax_ld"]                       # node space: n - 1 rounded up to 64; edge space: m rounded up to 64
+    # (edge space: the assembly writes 8 ld^2 bytes as well, and the gradient reads 8 ld m instead of the scores' 52 m)
+    out = dict(case=case, form=info["relax_form"], n=n, m=m, k=k, ld=ld, beta=info["beta"], iterations=int(r["iters"]), first_ms=round(first_ms, 2),
+               run_ms=round(run_ms, 2), ms_per_iteration=round(run_ms / ITERS, 3), eval_ms=round(eval_ms, 3),
+               bytes_assembly=8 * ld * ld, bytes_inverse=16 * ld * ld * (ld // 32), bytes_scores=8 * ld * m if edge_space else 52 * m,
+               model_tb_s=round((8 * ld * ld + 16 * ld * ld * (ld // 32) + (8 * ld * m if edge_space else 52 * m)) / (run_ms / ITERS * 1e-3) / 1e12, 3),
+               F_last=float(r["f"][-1]), upper=float(r["upper"]), **py)
     if check:
         (dx, sx), (d0, s0) = cpu_logdets(n, fi, fj, fw, ci, cj, cw, r["x"], info["beta"])
         out.update(F_final_iterate=F, F_cpu_dense=dx - d0, F_cpu_sparse=sx - s0, logdet_Mx=dx, d=abs(dx - sx),
@@ -96,4 +122,4 @@ if __name__ == "__main__":
     check = "--no-check" not in args
     ESPRelaxation([Edge(0, 1, 1.0), Edge(1, 2, 1.0)], [Edge(0, 2, 1.0)], 3).evaluate_objective([0.5])     # (HIP context and code objects)
     for c in [a for a in args if not a.startswith("--")] or ["intel", "sphere2500", "city10000"]:
-        run(c, check)
+        run(c, check, edge_space="--edge-space" in args, python_loop="--no-python" not in args)
