@@ -378,14 +378,20 @@ typedef struct machip_esp machip_esp;
  * no entry in order_out / gain_out.  The history holds r + K columns (8 ld (r + K) bytes): the route is for r << n, K << n.  A fixed
  * graph that is not connected is MACHIP_BAD_ARG (the route has no beta), as are fixed links whose summed weight is not positive;
  * all argument errors are decided on the host before a device is touched.  Exact for any connected fixed graph; on a chain it
- * feeds the history's sums the doubles MACHIP_ESP_MATRIX_FREE alone feeds them and returns the same bits.  machip_esp_relax_* and
- * machip_eig_create answer MACHIP_BAD_ARG on this route. */
+ * feeds the history's sums the doubles MACHIP_ESP_MATRIX_FREE alone feeds them and returns the same bits.  machip_esp_relax_* (unless
+ * the handle was made with MACHIP_ESP_EDGE_RELAX_TREE as well) and machip_eig_create answer MACHIP_BAD_ARG on this route. */
 #define MACHIP_ESP_SPANNING_TREE 8
 /* flags, valid only together with MACHIP_ESP_MATRIX_FREE (MACHIP_BAD_ARG alone, with MACHIP_ESP_DENSE_INVERSE, with
  * MACHIP_ESP_SPANNING_TREE, or on a fixed graph that is not the connected chain): the handle is a MACHIP_ESP_MATRIX_FREE handle
  * -- machip_esp_select and machip_esp_weighted_resistances work exactly as without this flag -- on which machip_esp_relax_* run in
  * the space of the m candidates instead of the n - 1 nodes (mac_amd/csrc/esp_relax_edge.h; the text above machip_esp_relax_eval). */
 #define MACHIP_ESP_EDGE_RELAX 16
+/* flags, valid only as MACHIP_ESP_MATRIX_FREE | MACHIP_ESP_SPANNING_TREE | MACHIP_ESP_EDGE_RELAX_TREE (without both partners
+ * MACHIP_BAD_ARG "unknown flags ..."; with MACHIP_ESP_EDGE_RELAX or MACHIP_ESP_DENSE_INVERSE MACHIP_BAD_ARG naming the pair; all
+ * decided on the host before a device is touched): the handle is a spanning-tree handle -- machip_esp_select and
+ * machip_esp_weighted_resistances work exactly as without this flag -- on which machip_esp_relax_* run in the space of the m
+ * candidates and the r seeds (mac_amd/csrc/esp_relax_edge_tree.h; the text above machip_esp_relax_eval).  Bit 4 stays unknown. */
+#define MACHIP_ESP_EDGE_RELAX_TREE 32
 /* fold: pending rank-1 updates folded into Sigma every `fold` steps (1..256; 0 = 64).  Builds Sigma0. */
 int machip_esp_create(int device, int64_t n, int64_t n_fixed, const int32_t* fi, const int32_t* fj, const double* fw,
                       int64_t m, const int32_t* ci, const int32_t* cj, const double* cw, int fold, int flags, machip_esp** out);
@@ -433,7 +439,21 @@ int machip_esp_seeds(machip_esp* h, int64_t* seeds_out);
  * Gauss-Jordan elimination and takes F from its pivots; the LP vertex, the step, the stop rules, the tie rule, the argument
  * checks and the outputs are those above, and runs repeat bit for bit.  Limit: m <= 16384 (MACHIP_BAD_ARG at the first relaxation
  * call, before anything is allocated); none on n.  The first call allocates two ld x ld buffers; nothing of size n is allocated and
- * nothing the greedy keeps (its history, what machip_esp_weighted_resistances reports) is touched. */
+ * nothing the greedy keeps (its history, what machip_esp_weighted_resistances reports) is touched.
+ *
+ * On a handle made with MACHIP_ESP_EDGE_RELAX_TREE they work in edge space over the spanning tree T of machip_esp_tree_plan, for
+ * any connected fixed graph.  M = m + r columns: [0, m) the candidates, [m, M) the r seeds in the plan's order.  With Rt the root
+ * resistances along T,
+ *     G_ef = (Rt[lca(u_e, u_f)] + Rt[lca(v_e, v_f)]) - (Rt[lca(u_e, v_f)] + Rt[lca(v_e, u_f)])      (this association; G_ef = G_fe
+ *     to the bit, a self-loop's row and column exact zeros),   d_j = w_j x_j (j < m), w_seed (j >= m),   N(x) = I + G diag(d),
+ *     F(x) = log det N(x) - log det N(0)   (N(0): the seeds alone, evaluated once per handle by the same kernels: F(0) = 0 exactly),
+ *     dF/dx_e = w_e sum_{j < M} N(x)^-1[e, j] G[j, e]   (e < m).
+ * G is built once, at the first relaxation call, and kept (ld x ld, ld = M rounded up to 64); every evaluation assembles N(x) from
+ * it, inverts it by the same elimination and takes the gradient from rows of N^-1 and G.  The LP vertex, the step, the stop rules,
+ * the tie rule, the argument checks and the outputs range over the m candidates and are those above; runs repeat bit for bit.
+ * Limit: m + r <= 16384 (MACHIP_BAD_ARG naming m and r at the first relaxation call, before anything is allocated; the handle's
+ * greedy keeps working); none on n.  The first call allocates three ld x ld buffers (24 ld^2 bytes); nothing of size n is allocated
+ * beyond the tree's tables and nothing the greedy keeps is written -- the seeds need not have been run. */
 /* F(x) and, when grad_out is not NULL, the gradient (m doubles). */
 int machip_esp_relax_eval(machip_esp* h, const double* x, double* F_out, double* grad_out);
 /* Frank-Wolfe from x_inout with the open-loop step 2 / (2 + t), t = 0, 1, ...: per iteration F, the dual value F + g.(s - x)
@@ -447,9 +467,13 @@ int machip_esp_relax_run(machip_esp* h, int64_t k, int max_iters, double gap_tol
  * F + inner(g, s - x) reproduces machip_esp_relax_run's dual values, and with them its upper bound, bit for bit (a host dot
  * product sums in another order and agrees to rounding only). */
 int machip_esp_relax_inner(machip_esp* h, const double* a, const double* b, double* out);
-/* info2 = {the space the relaxation of this handle works in (0: nodes, M(x); 1: candidates, N(x), MACHIP_ESP_EDGE_RELAX), the
- * leading dimension of the matrix it inverts (0 before the first relaxation call on a node-space handle)}. */
+/* info2 = {the space the relaxation of this handle works in (0: nodes, M(x); 1: candidates, N(x), MACHIP_ESP_EDGE_RELAX;
+ * 2: candidates and seeds over the spanning tree, MACHIP_ESP_EDGE_RELAX_TREE), the leading dimension of the matrix it inverts
+ * (0 before the first relaxation call on a node-space handle)}. */
 int machip_esp_relax_info(machip_esp* h, int32_t* info2);
+/* The stored Gram matrix of a MACHIP_ESP_EDGE_RELAX_TREE handle, M x M row-major into G_out (M = m + r, built if no relaxation
+ * call has built it yet).  MACHIP_BAD_ARG on every other kind of handle and when M is not m + r. */
+int machip_esp_relax_gram(machip_esp* h, double* G_out, int64_t M);
 
 /* GreedyEig (mac/solvers/greedy_eig.py of the reference: the greedy k-edge selection by algebraic connectivity; mac_amd/csrc/eig.h).
  * Every pick evaluates lambda_2(L_cur + w_e a_e a_e^T) for the unselected candidates whose supergradient bound

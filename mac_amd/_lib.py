@@ -114,6 +114,7 @@ SIGNATURES = {
                                        C.POINTER(C.c_int), C.POINTER(C.c_double)]),
     "machip_esp_relax_inner": (C.c_int, [C.c_void_p, _f64p, _f64p, C.POINTER(C.c_double)]),
     "machip_esp_relax_info": (C.c_int, [C.c_void_p, _i32p]),
+    "machip_esp_relax_gram": (C.c_int, [C.c_void_p, _f64p, C.c_int64]),
     "machip_eig_create": (C.c_int, [C.c_int, C.c_int64, C.c_int64, _i32p, _i32p, _f64p, C.c_int64, _i32p, _i32p, _f64p,
                                     C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "machip_eig_destroy": (None, [C.c_void_p]),
@@ -473,6 +474,7 @@ ESP_DENSE_INVERSE = 1      # MACHIP_ESP_DENSE_INVERSE
 ESP_MATRIX_FREE = 2        # MACHIP_ESP_MATRIX_FREE
 ESP_SPANNING_TREE = 8      # MACHIP_ESP_SPANNING_TREE (only together with ESP_MATRIX_FREE)
 ESP_EDGE_RELAX = 16        # MACHIP_ESP_EDGE_RELAX (only together with ESP_MATRIX_FREE alone: the chain)
+ESP_EDGE_RELAX_TREE = 32   # MACHIP_ESP_EDGE_RELAX_TREE (only as ESP_MATRIX_FREE | ESP_SPANNING_TREE | ESP_EDGE_RELAX_TREE)
 
 
 def host_esp_tree(n, fi, fj, fw):
@@ -500,10 +502,18 @@ class Esp:
         sizes for its largest budget (MACHIP_ESP_MATRIX_FREE; the slices of its sums: process option "esp_free_split").
         Nothing is folded on that route: ``fold`` is not passed on (the C entry point wants 0 with the flag).
         edge_relax=True (with matrix_free=True only): ``relax_eval`` / ``relax_run`` / ``relax_inner`` work in the space of the
-        m candidates instead of the n - 1 nodes (MACHIP_ESP_EDGE_RELAX, mac_amd/csrc/esp_relax_edge.h): m <= 16384, any n."""
+        m candidates instead of the n - 1 nodes (MACHIP_ESP_EDGE_RELAX, mac_amd/csrc/esp_relax_edge.h): m <= 16384, any n.
+        edge_relax="tree" (with matrix_free="tree" only): the same over the spanning tree, the r seeds as r more columns
+        (MACHIP_ESP_EDGE_RELAX_TREE, mac_amd/csrc/esp_relax_edge_tree.h): any connected fixed graph, m + r <= 16384, any n."""
         if not isinstance(matrix_free, (bool, np.bool_)) and matrix_free != "tree":
             raise ValueError(f'matrix_free must be False, True or "tree", not {matrix_free!r}')
-        if edge_relax and (isinstance(matrix_free, str) or not matrix_free or dense_inverse):
+        if not isinstance(edge_relax, (bool, np.bool_)):
+            if edge_relax != "tree":
+                raise ValueError(f'edge_relax must be False, True or "tree", not {edge_relax!r}')
+            if not isinstance(matrix_free, str) or dense_inverse:
+                raise ValueError('edge_relax="tree" runs the relaxation on the spanning-tree handle: it needs matrix_free="tree" '
+                                 f"(not {matrix_free!r}) and dense_inverse=False")
+        elif edge_relax and (isinstance(matrix_free, str) or not matrix_free or dense_inverse):
             raise ValueError("edge_relax=True runs the relaxation on the chain-free handle: it needs matrix_free=True "
                              f"(not {matrix_free!r}) and dense_inverse=False")
         lib = load()
@@ -517,7 +527,7 @@ class Esp:
         if isinstance(matrix_free, str):
             flags |= ESP_SPANNING_TREE
         if edge_relax:
-            flags |= ESP_EDGE_RELAX
+            flags |= ESP_EDGE_RELAX_TREE if isinstance(edge_relax, str) else ESP_EDGE_RELAX
         check(lib.machip_esp_create(int(device), self.n, len(fw), p_i32(fi), p_i32(fj), p_f64(fw), self.m,
                                     p_i32(ci), p_i32(cj), p_f64(cw), 0 if matrix_free else int(fold), flags, C.byref(h)))
         self._h = h
@@ -562,11 +572,21 @@ class Esp:
                     beta=b.value, seeds=int(r.value))
 
     def relax_info(self):
-        """dict(form = "node" | "edge", ld): the space the relaxation works in and the leading dimension of the matrix it inverts
-        (0 before the first relaxation call on a node-space handle)."""
+        """dict(form = "node" | "edge" | "edge_tree", ld): the space the relaxation works in and the leading dimension of the matrix
+        it inverts (0 before the first relaxation call on a node-space handle)."""
         a = np.zeros(2, dtype=np.int32)
         check(self._lib.machip_esp_relax_info(self._h, p_i32(a)))
-        return dict(form=("node", "edge")[a[0]], ld=int(a[1]))
+        return dict(form=("node", "edge", "edge_tree")[a[0]], ld=int(a[1]))
+
+    def relax_gram(self):
+        """The stored (m + r) x (m + r) Gram matrix of an edge_relax="tree" handle: the candidates' columns, then the seeds' in the
+        plan's order (machip_esp_relax_gram; built if no relaxation call has built it yet)."""
+        r = C.c_int64(0)
+        check(self._lib.machip_esp_seeds(self._h, C.byref(r)))
+        M = self.m + int(r.value)
+        G = np.empty((max(M, 1), max(M, 1)))
+        check(self._lib.machip_esp_relax_gram(self._h, p_f64(G), M))
+        return G[:M, :M]
 
     def relax_eval(self, x, want_grad=True):
         """(F(x), gradient or None) of the relaxation: F = logdet M(x) - logdet M(0) (machip_esp_relax_eval)."""

@@ -241,6 +241,7 @@ struct machip_esp {
     hipStream_t stream = nullptr;
     int n = 0, np = 0, ld = 0, m = 0, fold = machip::kEspDefaultFold;
     bool edge_relax = false;      // MACHIP_ESP_EDGE_RELAX (form 2 only): the relaxation runs in the candidates' space (esp_relax_edge.h)
+    bool edge_tree = false;       // MACHIP_ESP_EDGE_RELAX_TREE (form 3 only): the same over the spanning tree's columns (esp_relax_edge_tree.h)
     int form = 0;                 // 0 chain, 1 general (dense Gauss-Jordan inverse), 2 chain without Sigma (esp_free.h), 3 spanning tree without Sigma (esp_tree.h)
     double beta = 0.0;
     double *R = nullptr, *part = nullptr;      // form 2: the chain's prefix resistances (n'); forms 2, 3: the column slices' partial sums

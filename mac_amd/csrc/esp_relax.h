@@ -20,7 +20,9 @@
 // The host reads three scalars and the pivot flag per iteration (the stop tests), nothing else.
 //
 // On a MACHIP_ESP_EDGE_RELAX handle steps 1-4 are those of esp_relax_edge.h instead -- N(x) = I + G D in the candidates' space,
-// its inverse and the gradient from it -- and steps 5-6, the reading of the scalars and the loop are the ones here.
+// its inverse and the gradient from it -- and steps 5-6, the reading of the scalars and the loop are the ones here.  On a
+// MACHIP_ESP_EDGE_RELAX_TREE handle they are those of esp_relax_edge_tree.h: the same N(x) over the candidates and the seeds of a
+// spanning tree, its Gram matrix stored, log det N(0) subtracted.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -28,6 +30,7 @@
 
 #include "esp.h"
 #include "esp_relax_edge.h"
+#include "esp_relax_edge_tree.h"
 #include "kernels.h"
 
 namespace machip {
@@ -43,6 +46,7 @@ struct EspRelax {
     double logdet0 = 0.0;                    // log det M(0), by the same kernels in the same order (F(0) = 0 exactly)
     int ld = 0;                              // leading dimension of the matrix an evaluation inverts (node space: the handle's)
     EspEdge* ed = nullptr;                   // edge space (esp_relax_edge.h): N(x) instead of M(x); bufC .. tw above stay unused
+    EspEdgeTree* et = nullptr;               // edge space over a spanning tree (esp_relax_edge_tree.h): likewise
 };
 
 // Row i of M(x): zeros, then entry q in [rowptr[i], rowptr[i + 1]) at column ecol[q] = sum over its terms t in
@@ -107,6 +111,7 @@ inline void esp_relax_release(machip_esp* h) {
     void* bufs[] = {r->bufC, r->rowptr, r->ecol, r->tptr, r->tx, r->tw, r->xa, r->xb, r->part, r->ldet, r->scal, r->st, r->hist};
     for (void* q : bufs) if (q) (void)hipFree(q);
     esp_edge_release(r->ed);
+    esp_edge_tree_release(r->et);
     delete r;
     h->rx = nullptr;
 }
@@ -156,6 +161,7 @@ inline int esp_relax_build_lists(machip_esp* h, EspRelax* r) {
 inline int esp_relax_eval_on(machip_esp* h, const double* x, bool want_grad) {
     EspRelax* r = h->rx;
     if (r->ed) return esp_edge_eval_on(h, r->ed, x, r->ldet, want_grad);
+    if (r->et) return esp_edge_tree_eval_on(h, r->et, x, r->ldet, want_grad);
     hipStream_t st = h->stream;
     h->live = false;
     h->pending = 0;
@@ -195,13 +201,20 @@ inline int esp_relax_read(machip_esp* h, int np, double* out3) {
     HIP_TRY(hipMemcpyAsync(out3, r->scal, sizeof(double) * 3, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipMemcpyAsync(&hbad, h->bad, sizeof(int), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
-    if (hbad && r->ed) return fail(MACHIP_NOT_CONVERGED, "N(x) = I + G D has a non-positive Gauss-Jordan pivot (its leading minors are positive: lost numerically)");
+    if (hbad && (r->ed || r->et)) return fail(MACHIP_NOT_CONVERGED, "N(x) = I + G D has a non-positive Gauss-Jordan pivot (its leading minors are positive: lost numerically)");
     if (hbad) return fail(MACHIP_NOT_CONVERGED, "M(x) is not positive definite numerically (a non-positive Gauss-Jordan pivot)");
     return MACHIP_OK;
 }
 
 // What the relaxation cannot do on this handle, decided from the handle alone (nothing is allocated before it is asked).
 inline int esp_relax_limits(const machip_esp* h) {
+    if (h->edge_tree) {
+        const int64_t m = h->m, sd = h->tr->seeds;
+        if (m + sd > kEspDenseMaxN)
+            return fail(MACHIP_BAD_ARG, "MACHIP_ESP_EDGE_RELAX_TREE inverts the dense (m + r) x (m + r) N(x): candidates plus seeds must be <= 16384 (m = " +
+                                            std::to_string(m) + ", r = " + std::to_string(sd) + ")");
+        return MACHIP_OK;
+    }
     if (h->edge_relax) {
         if (h->m > kEspDenseMaxN)
             return fail(MACHIP_BAD_ARG, "MACHIP_ESP_EDGE_RELAX inverts the dense m x m N(x): the number of candidates must be <= 16384 (m = " +
@@ -216,7 +229,8 @@ inline int esp_relax_limits(const machip_esp* h) {
 }
 
 // First relaxation call on a handle.  Node space: the third buffer, the incidence list, log det M(0).  Edge space: the state of
-// esp_relax_edge.h (log det N(0) = log det I = 0: nothing to evaluate).
+// esp_relax_edge.h (log det N(0) = log det I = 0: nothing to evaluate).  Edge space over a spanning tree: the state of
+// esp_relax_edge_tree.h with its Gram matrix, and log det N(0) -- the seeds' -- by one evaluation at x = 0.
 inline int esp_relax_prepare(machip_esp* h) {
     ST_TRY(esp_relax_limits(h));
     HIP_TRY(hipSetDevice(h->device));
@@ -228,9 +242,13 @@ inline int esp_relax_prepare(machip_esp* h) {
             r->ed = new EspEdge();
             ST_TRY(esp_edge_prepare(h, r->ed));
         }
-        r->ld = r->ed ? r->ed->ld : h->ld;
+        if (h->edge_tree) {
+            r->et = new EspEdgeTree();
+            ST_TRY(esp_edge_tree_prepare(h, r->et));
+        }
+        r->ld = r->ed ? r->ed->ld : r->et ? r->et->ld : h->ld;
         const size_t ld = (size_t)r->ld, ms = (size_t)std::max(h->m, 1);
-        if (!r->ed) ST_TRY(dev_alloc(&r->bufC, ld * ld));
+        if (!r->ed && !r->et) ST_TRY(dev_alloc(&r->bufC, ld * ld));
         ST_TRY(dev_alloc(&r->xa, ms)); ST_TRY(dev_alloc(&r->xb, ms));
         ST_TRY(dev_alloc(&r->part, (size_t)2 * kMaxGrid)); ST_TRY(dev_alloc(&r->ldet, ld / kGjB)); ST_TRY(dev_alloc(&r->scal, 4));
         ST_TRY(dev_alloc(&r->st, 1));
@@ -239,8 +257,10 @@ inline int esp_relax_prepare(machip_esp* h) {
             HIP_TRY(hipMemsetAsync(r->ldet, 0, sizeof(double) * (ld / kGjB), h->stream));
             return MACHIP_OK;
         }
-        ST_TRY(dev_alloc(&r->hist, (size_t)6 * kBins));
-        ST_TRY(esp_relax_build_lists(h, r));
+        if (!r->et) {                            // (edge space over a tree: m <= 16 384 as above, no incidence list)
+            ST_TRY(dev_alloc(&r->hist, (size_t)6 * kBins));
+            ST_TRY(esp_relax_build_lists(h, r));
+        }
         HIP_TRY(hipMemsetAsync(r->xa, 0, sizeof(double) * ms, h->stream));
         ST_TRY(esp_relax_eval_on(h, r->xa, false));
         double s3[3];

@@ -132,15 +132,23 @@ struct EspTreeView {
     const double* Rt;        // preorder number -> resistance from the root
 };
 
+// One lifting step at level k towards the preorder number px: x moves to its 2^k-th ancestor unless that ancestor is an ancestor
+// of px as well.  One dependent 8-byte gather.  The one statement of the lifting rule: every chain below is made of these.
+__device__ __forceinline__ int esp_tree_lift(const EspTreeView& T, int k, int x, int px) {
+    const int2 a = T.up[(size_t)k * T.n + x];
+    return (a.x <= px && px <= a.y) ? x : a.x;
+}
+
+// The end of a chain that started at u = (pu, eu) and stands at x: u itself when u is an ancestor of px, else the parent of x.
+__device__ __forceinline__ int esp_tree_lift_end(const EspTreeView& T, int pu, int eu, int x, int px) {
+    return (pu <= px && px <= eu) ? pu : T.up[x].x;
+}
+
 // preorder number of lca(u, x) for u = (pu, eu) and the preorder number px: `levels` dependent gathers
 __device__ __forceinline__ int esp_tree_lca(const EspTreeView& T, int pu, int eu, int px) {
     int x = pu;
-    for (int k = T.levels - 1; k >= 0; --k) {
-        const int2 a = T.up[(size_t)k * T.n + x];
-        if (!(a.x <= px && px <= a.y)) x = a.x;
-    }
-    const int par = T.up[x].x;
-    return (pu <= px && px <= eu) ? pu : par;
+    for (int k = T.levels - 1; k >= 0; --k) x = esp_tree_lift(T, k, x, px);
+    return esp_tree_lift_end(T, pu, eu, x, px);
 }
 
 // esp_free_score with R[min(u, v)] replaced by Rt[lca(u, v)]: the same three-term sum (u, v reduced: node - 1)
@@ -206,13 +214,11 @@ __global__ __launch_bounds__(kBlock) void k_esp_tree_row(EspView V, EspTreeView 
     const int eu = T.tend[pu], ev = T.tend[pv];
     int xu = pu, xv = pv;
     for (int k = T.levels - 1; k >= 0; --k) {            // the two chains side by side: 2 gathers in flight per lane
-        const int2 a = T.up[(size_t)k * T.n + xu];
-        const int2 b = T.up[(size_t)k * T.n + xv];
-        if (!(a.x <= px && px <= a.y)) xu = a.x;
-        if (!(b.x <= px && px <= b.y)) xv = b.x;
+        xu = esp_tree_lift(T, k, xu, px);
+        xv = esp_tree_lift(T, k, xv, px);
     }
-    const int lu = (pu <= px && px <= eu) ? pu : T.up[xu].x;
-    const int lv = (pv <= px && px <= ev) ? pv : T.up[xv].x;
+    const int lu = esp_tree_lift_end(T, pu, eu, xu, px);
+    const int lv = esp_tree_lift_end(T, pv, ev, xv, px);
     zrow[i] = T.Rt[lu] - T.Rt[lv];
 }
 

@@ -1573,9 +1573,16 @@ int machip_esp_create(int device, int64_t n, int64_t n_fixed, const int32_t* fi,
     const int fold_given = fold;
     if (fold == 0) fold = kEspDefaultFold;
     if (fold < 1 || fold > kEspMaxFold) return fail(MACHIP_BAD_ARG, "fold must be in [1, 256]");
-    if (flags & ~(MACHIP_ESP_DENSE_INVERSE | MACHIP_ESP_MATRIX_FREE | MACHIP_ESP_SPANNING_TREE | MACHIP_ESP_EDGE_RELAX)) return fail(MACHIP_BAD_ARG, "unknown flags");
+    if (flags & ~(MACHIP_ESP_DENSE_INVERSE | MACHIP_ESP_MATRIX_FREE | MACHIP_ESP_SPANNING_TREE | MACHIP_ESP_EDGE_RELAX | MACHIP_ESP_EDGE_RELAX_TREE))
+        return fail(MACHIP_BAD_ARG, "unknown flags");
     const bool mfree = (flags & MACHIP_ESP_MATRIX_FREE) != 0, tree = (flags & MACHIP_ESP_SPANNING_TREE) != 0;
-    const bool edge = (flags & MACHIP_ESP_EDGE_RELAX) != 0;
+    const bool edge = (flags & MACHIP_ESP_EDGE_RELAX) != 0, etree = (flags & MACHIP_ESP_EDGE_RELAX_TREE) != 0;
+    if (etree && edge)
+        return fail(MACHIP_BAD_ARG, "MACHIP_ESP_EDGE_RELAX_TREE builds the Gram matrix from the spanning tree, MACHIP_ESP_EDGE_RELAX from the chain: the two cannot be combined");
+    if (etree && (flags & MACHIP_ESP_DENSE_INVERSE))
+        return fail(MACHIP_BAD_ARG, "MACHIP_ESP_EDGE_RELAX_TREE takes Sigma0 from the spanning tree's closed form: it cannot be combined with MACHIP_ESP_DENSE_INVERSE");
+    if (etree && !(mfree && tree))      // (without its partners the bit was an unknown flag before the route existed, and stays one)
+        return fail(MACHIP_BAD_ARG, "unknown flags: MACHIP_ESP_EDGE_RELAX_TREE puts the relaxation on the spanning-tree handle and is valid only together with MACHIP_ESP_MATRIX_FREE | MACHIP_ESP_SPANNING_TREE");
     if (edge && !mfree)      // (alone the bit was an unknown flag before the route existed, and stays one: the message keeps saying so)
         return fail(MACHIP_BAD_ARG, "unknown flags: MACHIP_ESP_EDGE_RELAX puts the relaxation on the chain-free handle and is valid only together with MACHIP_ESP_MATRIX_FREE");
     if (edge && (flags & MACHIP_ESP_DENSE_INVERSE))
@@ -1636,6 +1643,7 @@ int machip_esp_create(int device, int64_t n, int64_t n_fixed, const int32_t* fi,
     machip_esp* h = new machip_esp();
     h->device = device; h->n = N; h->np = np; h->m = (int)m; h->fold = mfree ? 0 : fold; h->beta = beta; h->form = tree ? kEspFormTree : mfree ? kEspFormFree : chain ? 0 : 1;
     h->edge_relax = edge;
+    h->edge_tree = etree;
     h->free_split = (int)std::max(0l, std::min<long>(default_options().get(kOpt_esp_free_split, 0), kEspFreeMaxSplit));
     h->ld = (np + kGjT - 1) / kGjT * kGjT;
     h->hfi.assign(fi, fi + n_fixed); h->hfj.assign(fj, fj + n_fixed); h->hfw.assign(fw, fw + n_fixed);
@@ -1879,7 +1887,8 @@ int machip_esp_relax_run(machip_esp* h, int64_t k, int max_iters, double gap_tol
     if (!h || !iters_out || !upper_out || max_iters < 0) return fail(MACHIP_BAD_ARG, "NULL handle or output, or max_iters < 0");
     *iters_out = 0;
     *upper_out = INFINITY;
-    if (h->edge_relax ? h->m > kEspDenseMaxN : h->n > kEspDenseMaxN) return esp_relax_prepare(h);      // (the limit's message, nothing allocated)
+    if (h->edge_tree ? (int64_t)h->m + h->tr->seeds > kEspDenseMaxN : h->edge_relax ? h->m > kEspDenseMaxN : h->n > kEspDenseMaxN)
+        return esp_relax_prepare(h);      // (the limit's message, nothing allocated)
     if (k <= 0 || k > h->m) return fail(MACHIP_BAD_ARG, "k must be in [1, m] (m = " + std::to_string(h->m) + " candidates)");
     ST_TRY(esp_relax_check_x(h, x_inout));
     ST_TRY(esp_relax_prepare(h));
@@ -1931,8 +1940,24 @@ int machip_esp_relax_inner(machip_esp* h, const double* a, const double* b, doub
 
 int machip_esp_relax_info(machip_esp* h, int32_t* info2) {
     if (!h || !info2) return fail(MACHIP_BAD_ARG, "NULL handle or output");
-    info2[0] = h->edge_relax ? 1 : 0;
-    info2[1] = h->rx ? h->rx->ld : h->edge_relax ? (std::max(h->m, 1) + kGjT - 1) / kGjT * kGjT : 0;
+    info2[0] = h->edge_tree ? 2 : h->edge_relax ? 1 : 0;
+    info2[1] = h->rx ? h->rx->ld : h->edge_tree ? esp_edge_tree_ld((int64_t)h->m + h->tr->seeds) : h->edge_relax ? (std::max(h->m, 1) + kGjT - 1) / kGjT * kGjT : 0;
+    return MACHIP_OK;
+}
+
+int machip_esp_relax_gram(machip_esp* h, double* G_out, int64_t M) {
+    if (!h || !G_out) return fail(MACHIP_BAD_ARG, "NULL handle or output");
+    if (!h->edge_tree) return fail(MACHIP_BAD_ARG, "the stored Gram matrix belongs to a MACHIP_ESP_EDGE_RELAX_TREE handle: this handle keeps none");
+    const int64_t cols = (int64_t)h->m + h->tr->seeds;
+    if (M != cols)
+        return fail(MACHIP_BAD_ARG, "M must be m + r = " + std::to_string((long long)cols) + " (m = " + std::to_string(h->m) + " candidates, r = " +
+                                        std::to_string(h->tr->seeds) + " seeds), not " + std::to_string((long long)M));
+    ST_TRY(esp_relax_prepare(h));
+    if (!M) return MACHIP_OK;
+    const EspEdgeTree* E = h->rx->et;
+    HIP_TRY(hipMemcpy2DAsync(G_out, sizeof(double) * (size_t)M, E->G, sizeof(double) * (size_t)E->ld, sizeof(double) * (size_t)M, (size_t)M,
+                             hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
     return MACHIP_OK;
 }
 

@@ -24,7 +24,7 @@ from mac_amd.utils.rounding import round_madow, round_nearest
 
 class ESPRelaxation:
     def __init__(self, fixed_edges: List[Edge], candidate_edges: List[Edge], num_nodes: int, *, device: int = 0,
-                 edge_space: bool = False):
+                 edge_space=False):
         """Arguments as GreedyESP.  The fixed graph may be disconnected as long as every node other than 0 has a fixed edge
         (beta = 1e-4 then, as in GreedyESP); num_nodes <= 16384 (the dense M(x) is inverted per evaluation).
 
@@ -32,14 +32,24 @@ class ESPRelaxation:
         the candidates' Gram matrix under the chain's resistances and D = diag(w x), F(x) = logdet(I + G D) and the gradient is
         w_e [(I + G D)^-1 G]_ee: an m x m inverse per evaluation instead of an (n - 1) x (n - 1) one.  Regime: the fixed edges are
         exactly the connected chain (i, i+1) (parallel links summed), at most 16384 candidates, any num_nodes.  Same results to
-        rounding, not the same bits: the default stays node space."""
+        rounding, not the same bits: the default stays node space.
+
+        edge_space="tree": edge space for any connected fixed graph (mac_amd/csrc/esp_relax_edge_tree.h).  The Gram matrix comes
+        from the spanning tree GreedyESP(matrix_free="tree") works from, and the r fixed links outside that tree (``info()["seeds"]``)
+        are r more columns of it: an (m + r) x (m + r) inverse per evaluation, the matrix itself built once and kept (three buffers,
+        24 ld^2 bytes, ld = m + r rounded up to 64).  Regime: a connected fixed graph with positive link weights, m + r <= 16384,
+        r << num_nodes, any num_nodes."""
+        if not isinstance(edge_space, (bool, np.bool_)) and edge_space != "tree":
+            raise ValueError(f'edge_space must be False, True or "tree", not {edge_space!r}')
         self.fixed_edges = fixed_edges
         self.all_candidate_edges = candidate_edges
         self.num_nodes = num_nodes
         fi, fj, fw = edges_to_arrays(fixed_edges)
         ci, cj, cw = edges_to_arrays(candidate_edges)
         self.weights = cw
-        if edge_space:
+        if isinstance(edge_space, str):
+            self._dev = _lib.Esp(num_nodes, fi, fj, fw, ci, cj, cw, device=device, matrix_free="tree", edge_relax="tree")
+        elif edge_space:
             self._dev = _lib.Esp(num_nodes, fi, fj, fw, ci, cj, cw, device=device, matrix_free=True, edge_relax=True)
         else:
             self._dev = _lib.Esp(num_nodes, fi, fj, fw, ci, cj, cw, device=device)
@@ -82,7 +92,7 @@ class ESPRelaxation:
         return rounded, w, float(r["upper"])
 
     def info(self) -> dict:
-        """The handle's description (GreedyESP.info), the space the relaxation works in (relax_form = "node" | "edge") with the
+        """The handle's description (GreedyESP.info), the space the relaxation works in (relax_form = "node" | "edge" | "edge_tree") with the
         leading dimension it inverts (relax_ld), and the iterations of the last solve."""
         d = self._dev.info()
         ri = self._dev.relax_info()
