@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define MACHIP_ABI_VERSION 12   /* 12: MACHIP_ESP_EDGE_RELAX (the relaxation in the candidates' space on a chain-fixed graph; machip_esp_relax_info); 11: MACHIP_ESP_SPANNING_TREE (the matrix-free route of GreedyESP for any connected fixed graph; machip_esp_tree_plan, machip_esp_seeds); 10: MACHIP_ESP_MATRIX_FREE (GreedyESP on a chain without a dense Sigma, option esp_free_split); 9: the relaxation of GreedyESP's problem (machip_esp_relax_*); 8: GreedyEig handle (machip_eig_*); 7: GreedyESP handle (machip_esp_*); 6: machip_solve_stats.drift, machip_panel_plan fills 12 entries; 5: per-handle option table (machip_set_option), machip_comm_drop_ipc; 4: inter-process communicator */
+#define MACHIP_ABI_VERSION 13   /* 13: machip_esp_exchange (best-swap local search on the log tree count; options esp_xch_lds_kb, esp_xch_max_mb, esp_xch_profile); 12: MACHIP_ESP_EDGE_RELAX (the relaxation in the candidates' space on a chain-fixed graph; machip_esp_relax_info); 11: MACHIP_ESP_SPANNING_TREE (the matrix-free route of GreedyESP for any connected fixed graph; machip_esp_tree_plan, machip_esp_seeds); 10: MACHIP_ESP_MATRIX_FREE (GreedyESP on a chain without a dense Sigma, option esp_free_split); 9: the relaxation of GreedyESP's problem (machip_esp_relax_*); 8: GreedyEig handle (machip_eig_*); 7: GreedyESP handle (machip_esp_*); 6: machip_solve_stats.drift, machip_panel_plan fills 12 entries; 5: per-handle option table (machip_set_option), machip_comm_drop_ipc; 4: inter-process communicator */
 
 typedef enum machip_status {
     MACHIP_OK = 0,
@@ -474,6 +474,30 @@ int machip_esp_relax_info(machip_esp* h, int32_t* info2);
 /* The stored Gram matrix of a MACHIP_ESP_EDGE_RELAX_TREE handle, M x M row-major into G_out (M = m + r, built if no relaxation
  * call has built it yet).  MACHIP_BAD_ARG on every other kind of handle and when M is not m + r. */
 int machip_esp_relax_gram(machip_esp* h, double* G_out, int64_t M);
+
+/* The Fedorov exchange on the log tree count (mac_amd/csrc/esp_exchange.h): best-swap local search from the k-edge selection
+ * sel_in (k distinct candidate indices, any order).  With S the selection, Sigma = (L_red + sum_{e in S} w_e a_e a_e^T)^-1,
+ * s_e = w_e a_e^T Sigma a_e and r_ef = a_e^T Sigma a_f, taking e in S out and putting f outside S in multiplies the tree count by
+ *     Delta(e, f) = (1 - s_e)(1 + s_f) + w_e w_f r_ef^2.
+ * A round evaluates all k (m - k) pairs and takes the largest Delta (ties, exact equality: lowest e, then lowest f); the call
+ * stops with *converged = 1 when Delta - 1 <= min_gain, or with *converged = 0 after max_swaps swaps (max_swaps = 0 is legal:
+ * the selection is loaded and returned).  The swap is applied as two rank-1 updates of Sigma, the removal with
+ * c = -w_e / (1 - s_e), the insertion with c = w_f / (1 + s_f'), s_f' the score after the removal.  Outputs: sel_out[k] the final
+ * selection ascending; out_idx[t], in_idx[t], ratio[t] = (1 - s_e)(1 + s_f') for swap t < *n_swaps (max_swaps entries each; they
+ * may be NULL when max_swaps = 0; sum log ratio = the growth of the log tree count); t_ms (6 doubles, may be NULL): device time of
+ * the call, and -- only with option esp_xch_profile = 1, else 0 -- of the load with T's build, the pair passes, T's updates, the
+ * forced steps with their score updates, the folds.  Results are a function of the inputs alone: runs repeat bit for bit.
+ * The call keeps k rows of Sigma (8 k ld bytes, allocated by the first call, freed by machip_esp_destroy) and reads one 24-byte
+ * record per round.  Option esp_xch_lds_kb (KiB; default 48, at most 152; a launch the runtime refuses falls back to global rows): a pair pass holds its row in LDS when 8 ld bytes fit, else
+ * reads it from global memory -- the same bits either way.
+ * MACHIP_BAD_ARG (machip_last_error names the reason): NULL pointers; k < 1 or k >= m; an index outside [0, m); a repeated index;
+ * max_swaps < 0; min_gain < 0 or not finite; a MACHIP_ESP_MATRIX_FREE handle (no Sigma to exchange on); a handle with beta != 0
+ * (disconnected fixed graph: 1 - s_e can be of the order of beta); 8 k ld bytes beyond the device's free memory (or option
+ * esp_xch_max_mb, MiB) or k ld >= 2^31.  MACHIP_NOT_CONVERGED: a removal's 1 - s_e was not positive.
+ * Afterwards machip_esp_weighted_resistances refers to the fixed graph plus sel_out; machip_esp_select and machip_esp_relax_* return
+ * what they return on a fresh handle. */
+int machip_esp_exchange(machip_esp* h, int64_t k, const int32_t* sel_in, int64_t max_swaps, double min_gain, int32_t* sel_out,
+                        int32_t* out_idx, int32_t* in_idx, double* ratio, int64_t* n_swaps, int32_t* converged, double* t_ms);
 
 /* GreedyEig (mac/solvers/greedy_eig.py of the reference: the greedy k-edge selection by algebraic connectivity; mac_amd/csrc/eig.h).
  * Every pick evaluates lambda_2(L_cur + w_e a_e a_e^T) for the unselected candidates whose supergradient bound

@@ -115,6 +115,8 @@ SIGNATURES = {
     "machip_esp_relax_inner": (C.c_int, [C.c_void_p, _f64p, _f64p, C.POINTER(C.c_double)]),
     "machip_esp_relax_info": (C.c_int, [C.c_void_p, _i32p]),
     "machip_esp_relax_gram": (C.c_int, [C.c_void_p, _f64p, C.c_int64]),
+    "machip_esp_exchange": (C.c_int, [C.c_void_p, C.c_int64, _i32p, C.c_int64, C.c_double, _i32p, _i32p, _i32p, _f64p,
+                                      C.POINTER(C.c_int64), C.POINTER(C.c_int32), _f64p]),
     "machip_eig_create": (C.c_int, [C.c_int, C.c_int64, C.c_int64, _i32p, _i32p, _f64p, C.c_int64, _i32p, _i32p, _f64p,
                                     C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "machip_eig_destroy": (None, [C.c_void_p]),
@@ -532,6 +534,7 @@ class Esp:
                                     p_i32(ci), p_i32(cj), p_f64(cw), 0 if matrix_free else int(fold), flags, C.byref(h)))
         self._h = h
         self._lib = lib
+        self.matrix_free = matrix_free
 
     def close(self):
         if getattr(self, "_h", None):
@@ -608,6 +611,20 @@ class Esp:
                                              p_f64(f), p_f64(dual), p_f64(gn), C.byref(iters), C.byref(upper)))
         i = iters.value
         return dict(x=x, upper=upper.value, iters=i, f=f[:i], dual=dual[:i], gnorm=gn[:i])
+
+    def exchange(self, sel, max_swaps, min_gain=1e-9):
+        """Best-swap local search on the log tree count from the selection ``sel`` (candidate indices; machip_esp_exchange):
+        dict(selection int32[K] ascending, out, in, ratios (one entry per swap), swaps, converged, t_ms float64[6])."""
+        sel = i32(sel)
+        K, S = len(sel), max(int(max_swaps), 0)
+        sel_out = np.empty(max(K, 1), dtype=np.int32)
+        out, inn, ratio = np.empty(max(S, 1), dtype=np.int32), np.empty(max(S, 1), dtype=np.int32), np.empty(max(S, 1))
+        n, conv, t = C.c_int64(0), C.c_int32(0), np.zeros(6)
+        check(self._lib.machip_esp_exchange(self._h, K, p_i32(sel), int(max_swaps), float(min_gain), p_i32(sel_out), p_i32(out),
+                                            p_i32(inn), p_f64(ratio), C.byref(n), C.byref(conv), p_f64(t)))
+        q = int(n.value)
+        return {"selection": sel_out[:K], "out": out[:q], "in": inn[:q], "ratios": ratio[:q], "swaps": q,
+                "converged": int(conv.value), "t_ms": t}
 
     def relax_inner(self, a, b):
         """a . b summed on the device in the order relax_run sums g.(s - x) (machip_esp_relax_inner)."""

@@ -232,6 +232,7 @@ __global__ __launch_bounds__(256) void k_esp_fold(double* __restrict__ S, const 
 
 struct EspRelax;      // esp_relax.h: the state of the convex relaxation, made by the first relaxation call
 struct EspTreeState;  // esp_tree.h: the spanning tree's tables and the seeds of a MACHIP_ESP_SPANNING_TREE handle
+struct EspXch;        // esp_exchange.h: the rows of Sigma the exchange keeps, made by the first exchange call
 
 }  // namespace machip
 
@@ -260,6 +261,7 @@ struct machip_esp {
     std::vector<double> hfw, hcw;
     machip::EspRelax* rx = nullptr;
     machip::EspTreeState* tr = nullptr;
+    machip::EspXch* xc = nullptr;
 
     machip::EspView view() const {
         machip::EspView V;

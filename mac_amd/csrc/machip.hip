@@ -20,6 +20,7 @@
 #include "esp_free.h"
 #include "esp_tree.h"
 #include "esp_relax.h"
+#include "esp_exchange.h"
 #include "eig.h"
 
 namespace machip {
@@ -1747,6 +1748,7 @@ void machip_esp_destroy(machip_esp* h) {
     for (hipEvent_t e : h->ev) (void)hipEventDestroy(e);
     esp_relax_release(h);
     esp_tree_release(h);
+    esp_xch_release(h->xc);
     void* bufs[] = {h->bufA, h->bufB, h->cu, h->cv, h->sel, h->pi, h->order, h->bad, h->cw, h->s, h->Zb, h->cb, h->pv, h->gain, h->piv, h->best, h->R, h->part};
     for (void* q : bufs) if (q) (void)hipFree(q);
     if (h->stream) (void)hipStreamDestroy(h->stream);
@@ -1863,6 +1865,152 @@ int machip_esp_weighted_resistances(machip_esp* h, double* r_out) {
         HIP_TRY(hipMemcpyAsync(r_out, h->s, sizeof(double) * (size_t)h->m, hipMemcpyDeviceToHost, h->stream));
     }
     HIP_TRY(hipStreamSynchronize(h->stream));
+    return MACHIP_OK;
+}
+
+// ---- the exchange on GreedyESP's handle (esp_exchange.h) ----
+
+namespace {
+// Device time per phase of the exchange (option esp_xch_profile): events between the phases, read after the round's own
+// synchronisation.  Interval q lies between marks q - 1 and q and belongs to the phase mark q names (-1: nobody's -- the host waited).
+struct XchClock {
+    machip_esp* h;
+    bool on;
+    size_t base, used = 0;
+    std::vector<int> tag;
+    double acc[6] = {0, 0, 0, 0, 0, 0};
+    int mark(int phase) {
+        if (!on) return MACHIP_OK;
+        while (h->ev.size() <= base + used) {
+            hipEvent_t e;
+            HIP_TRY(hipEventCreate(&e));
+            h->ev.push_back(e);
+        }
+        HIP_TRY(hipEventRecord(h->ev[base + used], h->stream));
+        tag.push_back(phase);
+        ++used;
+        return MACHIP_OK;
+    }
+    int collect() {      // (the stream is idle)
+        for (size_t q = 1; q < used; ++q) {
+            if (tag[q] < 0) continue;
+            float ms = 0.0f;
+            HIP_TRY(hipEventElapsedTime(&ms, h->ev[base + q - 1], h->ev[base + q]));
+            acc[tag[q]] += ms;
+        }
+        used = 0;
+        tag.clear();
+        return MACHIP_OK;
+    }
+};
+}  // namespace
+
+int machip_esp_exchange(machip_esp* h, int64_t k, const int32_t* sel_in, int64_t max_swaps, double min_gain, int32_t* sel_out,
+                        int32_t* out_idx, int32_t* in_idx, double* ratio, int64_t* n_swaps, int32_t* converged, double* t_ms) {
+    std::vector<int> rowe;
+    ST_TRY(esp_xch_check(h, k, sel_in, max_swaps, min_gain, sel_out, out_idx, in_idx, ratio, n_swaps, converged, rowe));
+    *n_swaps = 0;
+    *converged = 0;
+    HIP_TRY(hipSetDevice(h->device));
+    const Options& O = default_options();
+    const int K = (int)k, m = h->m, B = h->fold, P = h->grid_m(), zg = (h->ld + kBlock - 1) / kBlock;
+    const int chunks = std::max(1, std::min((m + kBlock - 1) / kBlock, (kEspXchTargetGroups + K - 1) / K));
+    const int per = (m + chunks - 1) / chunks;
+    const long lds_kb = std::max(0l, std::min<long>(O.get(kOpt_esp_xch_lds_kb, kEspXchLdsDefaultKb), kEspXchLdsMaxKb));
+    const size_t row_bytes = sizeof(double) * (size_t)h->ld;
+    bool lds = row_bytes <= (size_t)lds_kb * 1024;
+    ST_TRY(esp_xch_prepare(h, h->xc, (size_t)K, (size_t)K * (size_t)chunks, (size_t)std::max<int64_t>(max_swaps, 1)));
+    EspXch* X = h->xc;
+    if (lds && row_bytes > 48 * 1024 &&
+        hipFuncSetAttribute(reinterpret_cast<const void*>(&k_esp_xch_pairs<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)row_bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        lds = false;      // (the runtime does not grant the row: the global-memory rows give the same bits)
+    }
+    while (h->ev.size() < 2) {
+        hipEvent_t e;
+        HIP_TRY(hipEventCreate(&e));
+        h->ev.push_back(e);
+    }
+    XchClock clk{h, O.get(kOpt_esp_xch_profile, 0) != 0, 2};
+    enum { kLoad = 1, kPairs = 2, kTrows = 3, kSteps = 4, kFolds = 5 };
+    hipStream_t st = h->stream;
+    const EspView V = h->view();
+    std::vector<char> in_sel((size_t)m, 0);
+    for (int e : rowe) in_sel[(size_t)e] = 1;
+    int j = 0;      // columns of Zb pending
+    // one rank-1 update of Sigma: the z of e into Zb[:, j], all m scores, T's rows (with_rows), the fold when Zb is full
+    auto step = [&](int e, int mode, double* rt, bool with_rows, int xrow, int f_in) -> int {
+        k_esp_xch_step<<<zg, kBlock, 0, st>>>(V, h->sig, j, e, mode, rt, X->scale);
+        k_esp_update<<<P, kBlock, 0, st>>>(V, j);
+        if (with_rows) ST_TRY(clk.mark(kSteps));      // (the load is one interval, marked at its end)
+        if (with_rows) {
+            k_esp_xch_tupdate<<<dim3((unsigned)K, (unsigned)zg), kBlock, 0, st>>>(V, X->T, X->rowe, j, xrow, f_in, X->scale);
+            ST_TRY(clk.mark(kTrows));
+        }
+        if (++j == B) {
+            h->fold_into(h->sig, B);
+            j = 0;
+            if (with_rows) ST_TRY(clk.mark(kFolds));
+        }
+        return MACHIP_OK;
+    };
+    // the load: Sigma0, the scores, the K given edges as forced picks in ascending index order, then T
+    h->live = false;
+    h->pending = 0;
+    HIP_TRY(hipEventRecord(h->ev[0], st));
+    ST_TRY(clk.mark(-1));
+    HIP_TRY(hipMemcpyAsync(h->sig, h->sig0, sizeof(double) * (size_t)h->ld * (size_t)h->ld, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipMemsetAsync(h->sel, 0, sizeof(int) * (size_t)m, st));
+    HIP_TRY(hipMemsetAsync(h->bad, 0, sizeof(int), st));
+    HIP_TRY(hipMemcpyAsync(X->rowe, rowe.data(), sizeof(int) * (size_t)K, hipMemcpyHostToDevice, st));
+    k_esp_scores<<<P, kBlock, 0, st>>>(V, h->sig, 0);
+    for (int q = 0; q < K; ++q) ST_TRY(step(rowe[(size_t)q], 1, nullptr, false, -1, -1));
+    if (max_swaps > 0) k_esp_xch_tbuild<<<dim3((unsigned)K, (unsigned)zg), kBlock, 0, st>>>(V, h->sig, j, X->rowe, X->T);
+    HIP_TRY(hipGetLastError());
+    ST_TRY(clk.mark(kLoad));
+    int64_t t = 0;
+    int hbad = 0;
+    for (; t < max_swaps; ++t) {
+        if (lds) {
+            k_esp_xch_pairs<true><<<dim3((unsigned)K, (unsigned)chunks), kBlock, row_bytes, st>>>(V, X->T, X->rowe, per, X->pv, X->pf);
+            if (hipGetLastError() != hipSuccess) lds = false;      // (the launch was refused, nothing ran: global-memory rows from here on)
+        }
+        if (!lds) k_esp_xch_pairs<false><<<dim3((unsigned)K, (unsigned)chunks), kBlock, 0, st>>>(V, X->T, X->rowe, per, X->pv, X->pf);
+        k_esp_xch_argmax<<<1, kBlock, 0, st>>>(V, X->rowe, X->pv, X->pf, K * chunks, chunks, X->best);
+        HIP_TRY(hipGetLastError());
+        ST_TRY(clk.mark(kPairs));
+        EspXchBest b;
+        HIP_TRY(hipMemcpyAsync(&b, X->best, sizeof(b), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(&hbad, h->bad, sizeof(int), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        ST_TRY(clk.collect());
+        if (hbad) break;
+        if (b.val - 1.0 <= min_gain) { *converged = 1; break; }
+        ST_TRY(esp_xch_apply(rowe, in_sel, b.row, b.e, b.f));
+        out_idx[t] = b.e;
+        in_idx[t] = b.f;
+        ST_TRY(clk.mark(-1));
+        ST_TRY(step(b.e, -1, X->ratio + t, true, b.row, -1));
+        ST_TRY(step(b.f, +1, X->ratio + t, true, b.row, b.f));
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipEventRecord(h->ev[1], st));
+    if (t > 0) HIP_TRY(hipMemcpyAsync(ratio, X->ratio, sizeof(double) * (size_t)t, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&hbad, h->bad, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    ST_TRY(clk.collect());
+    h->pending = j;
+    h->live = true;
+    if (hbad)
+        return fail(MACHIP_NOT_CONVERGED, "exchange: 1 - s_e of a removal or 1 + s_f of an insertion is not positive, or no finite Delta (the selection holds a bridge of the graph, or lost numerically)");
+    *n_swaps = t;
+    for (int e = 0, q = 0; e < m; ++e) if (in_sel[(size_t)e]) sel_out[q++] = e;
+    if (t_ms) {
+        float ms = 0.0f;
+        HIP_TRY(hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
+        t_ms[0] = ms;
+        for (int q = 1; q < 6; ++q) t_ms[q] = clk.acc[q];
+    }
     return MACHIP_OK;
 }
 

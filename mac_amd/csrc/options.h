@@ -34,7 +34,10 @@ namespace machip {
     X(sel_small) X(sel_fuse) X(asm_g) X(asm_maxgrid) X(vbudget_mb) X(vcap) X(lanes) X(lane_vbudget_mb) X(lane_queues) X(shard_eig) X(ipc_panel) \
     X(rccl_timeout_s)                                                                                                              \
     /* GreedyESP, matrix-free route (read when the handle is made): slices of the history's columns per pick, 1..32 */           \
-    X(esp_free_split)
+    X(esp_free_split)                                                                                                              \
+    /* the exchange (esp_exchange.h; process defaults, read by every machip_esp_exchange call): KiB of LDS a row of T may take   \
+       (0: rows are read from global memory); a cap on T in MiB below the device's free memory; 1: time the phases of a round */   \
+    X(esp_xch_lds_kb) X(esp_xch_max_mb) X(esp_xch_profile)
 
 enum OptId {
 #define X(n) kOpt_##n,

@@ -21,6 +21,29 @@ from mac_amd import _lib
 from mac_amd.utils.graphs import Edge, edges_to_arrays, weight_reduced_graph_lap_from_edge_list
 
 
+def exchange_on(dev, candidate_edges, selection, max_swaps=None, min_gain=1e-9):
+    """``GreedyESP.exchange`` on the handle ``dev`` (a ``_lib.Esp``): shared with ``ESPRelaxation.exchange``."""
+    if dev.matrix_free:
+        raise ValueError("exchange works on the dense inverse: not available with matrix_free=" + repr(dev.matrix_free))
+    m = len(candidate_edges)
+    sel = np.asarray(selection)
+    if sel.ndim != 1:
+        raise ValueError("selection must be a 0/1 array of length m or a sequence of candidate indices")
+    if len(sel) == m and set(np.unique(sel).tolist()) <= {0, 1}:
+        sel = np.flatnonzero(sel)
+    elif sel.dtype.kind not in "iu":
+        raise ValueError("selection must be a 0/1 array of length m or a sequence of candidate indices")
+    if max_swaps is None:
+        max_swaps = 10 * len(sel)
+    r = dev.exchange(sel, max_swaps, min_gain)
+    result = np.zeros(m)
+    result[r["selection"]] = 1.0
+    info = {"swaps": r["swaps"], "out": r["out"], "in": r["in"], "ratios": r["ratios"],
+            "growth": float(np.sum(np.log(r["ratios"]))), "converged": bool(r["converged"]), "seconds": float(r["t_ms"][0]) / 1e3,
+            "phase_seconds": r["t_ms"][1:] / 1e3}
+    return result, [candidate_edges[i] for i in r["selection"]], info
+
+
 class GreedyESP:
     def __init__(self, fixed_edges: List[Edge], candidate_edges: List[Edge], num_nodes: int, lazy: bool = False, *,
                  device: int = 0, fold: int = 64, dense_inverse: bool = False, matrix_free=False):
@@ -82,6 +105,17 @@ class GreedyESP:
     def subset_lazy(self, k: int, verbose: bool = False):
         results, selected_edges, times = self.subsets_lazy([k], verbose=verbose)
         return results[0], selected_edges, times[0]
+
+    def exchange(self, selection, max_swaps: Optional[int] = None, min_gain: float = 1e-9):
+        """Best-swap local search (the Fedorov exchange of D-optimal design) on the log tree count, from ``selection``: a 0/1
+        array of length m or a sequence of candidate indices.  Every round takes the (selected, unselected) pair whose swap
+        raises the tree count most and stops when no swap raises it by more than a factor 1 + ``min_gain``, or after
+        ``max_swaps`` swaps (None: 10 K, a cap, not a tuning).  Returns ``(result, selected_edges, info)``: the 0/1 array, the edges in
+        index order, and ``info = dict(swaps, out, in, ratios, growth, converged, seconds)`` -- ``growth`` = sum(log(ratios)), the
+        gain of the log tree count in nats; ``seconds`` the device time of the call (``phase_seconds``, beside it: load, pair
+        passes, T updates, forced steps, folds -- zeros unless the process option esp_xch_profile is 1; tools/esp_xch_time.py).
+        Dense handles with a connected fixed graph only; ValueError on a matrix-free handle."""
+        return exchange_on(self._dev, self.all_candidate_edges, selection, max_swaps, min_gain)
 
     def weighted_resistances(self) -> np.ndarray:
         """w_e r_e of every candidate in the fixed graph plus the last run's selections."""

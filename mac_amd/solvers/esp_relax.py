@@ -18,6 +18,7 @@ from typing import List
 import numpy as np
 
 from mac_amd import _lib
+from mac_amd.solvers.esp import exchange_on
 from mac_amd.utils.graphs import Edge, edges_to_arrays
 from mac_amd.utils.rounding import round_madow, round_nearest
 
@@ -53,6 +54,7 @@ class ESPRelaxation:
             self._dev = _lib.Esp(num_nodes, fi, fj, fw, ci, cj, cw, device=device, matrix_free=True, edge_relax=True)
         else:
             self._dev = _lib.Esp(num_nodes, fi, fj, fw, ci, cj, cw, device=device)
+        self.edge_space = edge_space
         self.trace = []          # [(F, running upper bound, ||g||_2)] per iteration of the last solve
 
     def evaluate_objective(self, x) -> float:
@@ -69,9 +71,16 @@ class ESPRelaxation:
         return self._dev.relax_inner(np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64))
 
     def solve(self, k, x_init, rounding="nearest", max_iters=20, relative_duality_gap_tol=1e-4, grad_norm_tol=1e-8,
-              random_rounding_max_iters=1, verbose=False):
+              random_rounding_max_iters=1, verbose=False, *, exchange=False):
         """Frank-Wolfe (open-loop step 2 / (2 + t)) from ``x_init``, then rounding: ``(rounded, unrounded, upper)`` with
-        ``upper`` >= F of every k-edge selection.  The loop runs on the C side (machip_esp_relax_run)."""
+        ``upper`` >= F of every k-edge selection.  The loop runs on the C side (machip_esp_relax_run).  ``exchange=True``: the
+        rounded selection is polished by best-swap local search on the same handle (``exchange``) before it is returned; node
+        space and connected fixed graphs only (ValueError on an ``edge_space`` handle, which keeps no dense inverse, and on a
+        handle with beta != 0, both before any iteration)."""
+        if exchange and self.edge_space:
+            raise ValueError(f"exchange=True needs the dense inverse: not available with edge_space={self.edge_space!r}")
+        if exchange and k < len(self.weights) and self._dev.info()["beta"] != 0.0:      # (refused before the Frank-Wolfe run, not after it)
+            raise ValueError("exchange=True needs a connected fixed graph: this handle has beta = %g" % self._dev.info()["beta"])
         m = len(self.weights)
         if k >= m:
             result = np.ones(m)
@@ -89,7 +98,15 @@ class ESPRelaxation:
             rounded = round_madow(w, k, value_fn=self.evaluate_objective, max_iters=random_rounding_max_iters)
         else:
             rounded = round_nearest(w, k, self.weights, 10)
+        if exchange:
+            rounded = self.exchange(rounded)[0]
         return rounded, w, float(r["upper"])
+
+    def exchange(self, selection, max_swaps=None, min_gain=1e-9):
+        """``GreedyESP.exchange`` on this handle: ``(result, selected_edges, info)``."""
+        if self.edge_space:
+            raise ValueError(f"exchange needs the dense inverse: not available with edge_space={self.edge_space!r}")
+        return exchange_on(self._dev, self.all_candidate_edges, selection, max_swaps, min_gain)
 
     def info(self) -> dict:
         """The handle's description (GreedyESP.info), the space the relaxation works in (relax_form = "node" | "edge" | "edge_tree") with the
