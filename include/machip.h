@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define MACHIP_ABI_VERSION 13   /* 13: machip_esp_exchange (best-swap local search on the log tree count; options esp_xch_lds_kb, esp_xch_max_mb, esp_xch_profile); 12: MACHIP_ESP_EDGE_RELAX (the relaxation in the candidates' space on a chain-fixed graph; machip_esp_relax_info); 11: MACHIP_ESP_SPANNING_TREE (the matrix-free route of GreedyESP for any connected fixed graph; machip_esp_tree_plan, machip_esp_seeds); 10: MACHIP_ESP_MATRIX_FREE (GreedyESP on a chain without a dense Sigma, option esp_free_split); 9: the relaxation of GreedyESP's problem (machip_esp_relax_*); 8: GreedyEig handle (machip_eig_*); 7: GreedyESP handle (machip_esp_*); 6: machip_solve_stats.drift, machip_panel_plan fills 12 entries; 5: per-handle option table (machip_set_option), machip_comm_drop_ipc; 4: inter-process communicator */
+#define MACHIP_ABI_VERSION 14   /* 14: machip_esp_exchange_edge (the exchange in the candidates' space on MACHIP_ESP_EDGE_RELAX / MACHIP_ESP_EDGE_RELAX_TREE handles); 13: machip_esp_exchange (best-swap local search on the log tree count; options esp_xch_lds_kb, esp_xch_max_mb, esp_xch_profile); 12: MACHIP_ESP_EDGE_RELAX (the relaxation in the candidates' space on a chain-fixed graph; machip_esp_relax_info); 11: MACHIP_ESP_SPANNING_TREE (the matrix-free route of GreedyESP for any connected fixed graph; machip_esp_tree_plan, machip_esp_seeds); 10: MACHIP_ESP_MATRIX_FREE (GreedyESP on a chain without a dense Sigma, option esp_free_split); 9: the relaxation of GreedyESP's problem (machip_esp_relax_*); 8: GreedyEig handle (machip_eig_*); 7: GreedyESP handle (machip_esp_*); 6: machip_solve_stats.drift, machip_panel_plan fills 12 entries; 5: per-handle option table (machip_set_option), machip_comm_drop_ipc; 4: inter-process communicator */
 
 typedef enum machip_status {
     MACHIP_OK = 0,
@@ -498,6 +498,23 @@ int machip_esp_relax_gram(machip_esp* h, double* G_out, int64_t M);
  * what they return on a fresh handle. */
 int machip_esp_exchange(machip_esp* h, int64_t k, const int32_t* sel_in, int64_t max_swaps, double min_gain, int32_t* sel_out,
                         int32_t* out_idx, int32_t* in_idx, double* ratio, int64_t* n_swaps, int32_t* converged, double* t_ms);
+/* The same exchange carried out in the space of the candidates (mac_amd/csrc/esp_exchange_edge.h), on a handle made with
+ * MACHIP_ESP_EDGE_RELAX or MACHIP_ESP_EDGE_RELAX_TREE: any num_nodes, m + r <= 16384 (r the seeds of a tree handle, 0 on a chain).
+ * With G the Gram matrix of the m + r columns the relaxation of the handle works with and S' the selection plus the seeds,
+ * R = A^T Sigma(S') A is (m + r) x (m + r) and s_f = w_f R[f][f], r_ef = R[e][f]; a pick or a removal of column e is
+ * R -= c R[:, e] R[e, :] with the coefficients above.  Arguments, outputs, stop rule, tie rule, the meaning of max_swaps = 0 and the
+ * layout of t_ms are machip_esp_exchange's; results are a function of the inputs alone.  R lives in the relaxation's own N buffer
+ * (the relaxation's state is made if this is the first call on the handle; a tree handle's G is built if it was not); the call keeps
+ * k rows of R (8 k ld bytes, ld = m + r rounded up to 64) and a view of m + r columns, made by the first call, freed by
+ * machip_esp_destroy.  The greedy's history, scores, flags and pending count are never written.
+ * After an insertion the entering column's own score is written in closed form, 1 - 1 / (1 + s), instead of s - w c z_e^2 (G's
+ * entries grow with the length of a chain, the scores of the selected stay below 1); exact duplicates of the column get its bits.
+ * MACHIP_BAD_ARG (machip_last_error names the reason): what machip_esp_exchange refuses except the matrix-free clause; a handle made
+ * without MACHIP_ESP_EDGE_RELAX / MACHIP_ESP_EDGE_RELAX_TREE; m + r > 16384; 8 k ld bytes beyond the device's free memory (or option
+ * esp_xch_max_mb).  MACHIP_NOT_CONVERGED: a removal's 1 - s_e was not positive, or a round had no finite Delta.
+ * Afterwards machip_esp_relax_*, machip_esp_select and machip_esp_weighted_resistances return what they return on a fresh handle. */
+int machip_esp_exchange_edge(machip_esp* h, int64_t k, const int32_t* sel_in, int64_t max_swaps, double min_gain, int32_t* sel_out,
+                             int32_t* out_idx, int32_t* in_idx, double* ratio, int64_t* n_swaps, int32_t* converged, double* t_ms);
 
 /* GreedyEig (mac/solvers/greedy_eig.py of the reference: the greedy k-edge selection by algebraic connectivity; mac_amd/csrc/eig.h).
  * Every pick evaluates lambda_2(L_cur + w_e a_e a_e^T) for the unselected candidates whose supergradient bound

@@ -117,6 +117,8 @@ SIGNATURES = {
     "machip_esp_relax_gram": (C.c_int, [C.c_void_p, _f64p, C.c_int64]),
     "machip_esp_exchange": (C.c_int, [C.c_void_p, C.c_int64, _i32p, C.c_int64, C.c_double, _i32p, _i32p, _i32p, _f64p,
                                       C.POINTER(C.c_int64), C.POINTER(C.c_int32), _f64p]),
+    "machip_esp_exchange_edge": (C.c_int, [C.c_void_p, C.c_int64, _i32p, C.c_int64, C.c_double, _i32p, _i32p, _i32p, _f64p,
+                                           C.POINTER(C.c_int64), C.POINTER(C.c_int32), _f64p]),
     "machip_eig_create": (C.c_int, [C.c_int, C.c_int64, C.c_int64, _i32p, _i32p, _f64p, C.c_int64, _i32p, _i32p, _f64p,
                                     C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "machip_eig_destroy": (None, [C.c_void_p]),
@@ -615,13 +617,20 @@ class Esp:
     def exchange(self, sel, max_swaps, min_gain=1e-9):
         """Best-swap local search on the log tree count from the selection ``sel`` (candidate indices; machip_esp_exchange):
         dict(selection int32[K] ascending, out, in, ratios (one entry per swap), swaps, converged, t_ms float64[6])."""
+        return self._exchange(self._lib.machip_esp_exchange, sel, max_swaps, min_gain)
+
+    def exchange_edge(self, sel, max_swaps, min_gain=1e-9):
+        """``exchange`` in the space of the candidates, on an edge_relax handle (machip_esp_exchange_edge): the same dict."""
+        return self._exchange(self._lib.machip_esp_exchange_edge, sel, max_swaps, min_gain)
+
+    def _exchange(self, entry, sel, max_swaps, min_gain):
         sel = i32(sel)
         K, S = len(sel), max(int(max_swaps), 0)
         sel_out = np.empty(max(K, 1), dtype=np.int32)
         out, inn, ratio = np.empty(max(S, 1), dtype=np.int32), np.empty(max(S, 1), dtype=np.int32), np.empty(max(S, 1))
         n, conv, t = C.c_int64(0), C.c_int32(0), np.zeros(6)
-        check(self._lib.machip_esp_exchange(self._h, K, p_i32(sel), int(max_swaps), float(min_gain), p_i32(sel_out), p_i32(out),
-                                            p_i32(inn), p_f64(ratio), C.byref(n), C.byref(conv), p_f64(t)))
+        check(entry(self._h, K, p_i32(sel), int(max_swaps), float(min_gain), p_i32(sel_out), p_i32(out), p_i32(inn), p_f64(ratio),
+                    C.byref(n), C.byref(conv), p_f64(t)))
         q = int(n.value)
         return {"selection": sel_out[:K], "out": out[:q], "in": inn[:q], "ratios": ratio[:q], "swaps": q,
                 "converged": int(conv.value), "t_ms": t}

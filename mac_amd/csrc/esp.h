@@ -233,6 +233,7 @@ __global__ __launch_bounds__(256) void k_esp_fold(double* __restrict__ S, const 
 struct EspRelax;      // esp_relax.h: the state of the convex relaxation, made by the first relaxation call
 struct EspTreeState;  // esp_tree.h: the spanning tree's tables and the seeds of a MACHIP_ESP_SPANNING_TREE handle
 struct EspXch;        // esp_exchange.h: the rows of Sigma the exchange keeps, made by the first exchange call
+struct EspXchEdge;    // esp_exchange_edge.h: the view and the rows of the edge-space exchange, made by its first call
 
 }  // namespace machip
 
@@ -262,6 +263,7 @@ struct machip_esp {
     machip::EspRelax* rx = nullptr;
     machip::EspTreeState* tr = nullptr;
     machip::EspXch* xc = nullptr;
+    machip::EspXchEdge* xe = nullptr;
 
     machip::EspView view() const {
         machip::EspView V;

@@ -189,16 +189,19 @@ inline void esp_xch_release(EspXch*& x) {
     x = nullptr;
 }
 
-// The arguments, decided on the host before a device is touched.  sorted_out: the selection ascending.
+// The arguments, decided on the host before a device is touched.  sorted_out: the selection ascending.  edge: the call is
+// machip_esp_exchange_edge (esp_exchange_edge.h), which takes the edge-space relaxation's handles and no other.
 inline int esp_xch_check(const machip_esp* h, int64_t k, const int32_t* sel_in, int64_t max_swaps, double min_gain, const void* sel_out,
                          const void* out_idx, const void* in_idx, const void* ratio, const void* n_swaps, const void* converged,
-                         std::vector<int>& sorted_out) {
+                         std::vector<int>& sorted_out, bool edge = false) {
     if (!h) return fail(MACHIP_BAD_ARG, "NULL handle");
     if (!sel_in || !sel_out || !n_swaps || !converged) return fail(MACHIP_BAD_ARG, "sel_in, sel_out, n_swaps or converged is NULL");
     if (max_swaps < 0) return fail(MACHIP_BAD_ARG, "max_swaps must be >= 0 (got " + std::to_string((long long)max_swaps) + ")");
     if (max_swaps > 0 && (!out_idx || !in_idx || !ratio)) return fail(MACHIP_BAD_ARG, "out_idx, in_idx or ratio is NULL with max_swaps > 0");
     if (!(min_gain >= 0.0) || !std::isfinite(min_gain)) return fail(MACHIP_BAD_ARG, "min_gain must be finite and >= 0");
-    if (h->form == kEspFormFree || h->form == kEspFormTree)
+    if (edge && !h->edge_relax && !h->edge_tree)
+        return fail(MACHIP_BAD_ARG, "the edge-space exchange works on the relaxation's Gram matrix: the handle must be made with MACHIP_ESP_EDGE_RELAX or MACHIP_ESP_EDGE_RELAX_TREE");
+    if (!edge && (h->form == kEspFormFree || h->form == kEspFormTree))
         return fail(MACHIP_BAD_ARG, "the exchange works on the dense Sigma: not available on a MACHIP_ESP_MATRIX_FREE handle");
     if (h->beta != 0.0)
         return fail(MACHIP_BAD_ARG, "the exchange needs a connected fixed graph: with beta = " + std::to_string(h->beta) +
@@ -231,25 +234,25 @@ inline int esp_xch_apply(std::vector<int>& rowe, std::vector<char>& in_sel, int 
 
 // The call's state: K rows of T, the partials, the swaps' ratios.  Made by the first exchange call on a handle, grown by a later
 // one that needs more, freed by machip_esp_destroy.  T is refused when it exceeds the device's free memory (or option
-// esp_xch_max_mb, a cap in MiB).
-inline int esp_xch_prepare(machip_esp* h, EspXch*& x, size_t K, size_t parts, size_t swaps) {
+// esp_xch_max_mb, a cap in MiB).  ld: the leading dimension of T's rows (the handle's Sigma; esp_exchange_edge.h: the relaxation's).
+inline int esp_xch_prepare(EspXch*& x, size_t K, size_t parts, size_t swaps, size_t ld) {
     if (!x) x = new EspXch();
     if (x->rows < K) {
         if (x->T) { (void)hipFree(x->T); x->T = nullptr; x->rows = 0; }
         if (x->rowe) { (void)hipFree(x->rowe); x->rowe = nullptr; }
-        const size_t need = K * (size_t)h->ld * sizeof(double);
-        if (K * (size_t)h->ld >= ((size_t)1 << 31))      // (the row kernels launch K x ld threads; a pair pass of that size is out of the regime anyway)
+        const size_t need = K * ld * sizeof(double);
+        if (K * ld >= ((size_t)1 << 31))      // (the row kernels launch K x ld threads; a pair pass of that size is out of the regime anyway)
             return fail(MACHIP_BAD_ARG, "the exchange keeps one row of Sigma per selected edge and takes K x ld < 2^31: K x ld x 8 = " +
-                                            std::to_string(K) + " x " + std::to_string(h->ld) + " x 8 = " + std::to_string(need) + " bytes is beyond it");
+                                            std::to_string(K) + " x " + std::to_string(ld) + " x 8 = " + std::to_string(need) + " bytes is beyond it");
         size_t avail = 0, total = 0;
         HIP_TRY(hipMemGetInfo(&avail, &total));
         const long cap_mb = default_options().get(kOpt_esp_xch_max_mb, 0);
         if (cap_mb > 0) avail = std::min(avail, (size_t)cap_mb << 20);
         if (need > avail)
             return fail(MACHIP_BAD_ARG, "the exchange keeps one row of Sigma per selected edge: K x ld x 8 = " + std::to_string(K) + " x " +
-                                            std::to_string(h->ld) + " x 8 = " + std::to_string(need) + " bytes, more than the " +
+                                            std::to_string(ld) + " x 8 = " + std::to_string(need) + " bytes, more than the " +
                                             std::to_string(avail) + " bytes available" + (cap_mb > 0 ? " (option esp_xch_max_mb)" : " on the device"));
-        ST_TRY(dev_alloc(&x->T, K * (size_t)h->ld));
+        ST_TRY(dev_alloc(&x->T, K * ld));
         ST_TRY(dev_alloc(&x->rowe, K));
         x->rows = K;
     }

@@ -21,6 +21,7 @@
 #include "esp_tree.h"
 #include "esp_relax.h"
 #include "esp_exchange.h"
+#include "esp_exchange_edge.h"
 #include "eig.h"
 
 namespace machip {
@@ -1749,6 +1750,7 @@ void machip_esp_destroy(machip_esp* h) {
     esp_relax_release(h);
     esp_tree_release(h);
     esp_xch_release(h->xc);
+    esp_xe_release(h->xe);
     void* bufs[] = {h->bufA, h->bufB, h->cu, h->cv, h->sel, h->pi, h->order, h->bad, h->cw, h->s, h->Zb, h->cb, h->pv, h->gain, h->piv, h->best, h->R, h->part};
     for (void* q : bufs) if (q) (void)hipFree(q);
     if (h->stream) (void)hipStreamDestroy(h->stream);
@@ -1919,7 +1921,7 @@ int machip_esp_exchange(machip_esp* h, int64_t k, const int32_t* sel_in, int64_t
     const long lds_kb = std::max(0l, std::min<long>(O.get(kOpt_esp_xch_lds_kb, kEspXchLdsDefaultKb), kEspXchLdsMaxKb));
     const size_t row_bytes = sizeof(double) * (size_t)h->ld;
     bool lds = row_bytes <= (size_t)lds_kb * 1024;
-    ST_TRY(esp_xch_prepare(h, h->xc, (size_t)K, (size_t)K * (size_t)chunks, (size_t)std::max<int64_t>(max_swaps, 1)));
+    ST_TRY(esp_xch_prepare(h->xc, (size_t)K, (size_t)K * (size_t)chunks, (size_t)std::max<int64_t>(max_swaps, 1), (size_t)h->ld));
     EspXch* X = h->xc;
     if (lds && row_bytes > 48 * 1024 &&
         hipFuncSetAttribute(reinterpret_cast<const void*>(&k_esp_xch_pairs<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)row_bytes) != hipSuccess) {
@@ -2001,6 +2003,113 @@ int machip_esp_exchange(machip_esp* h, int64_t k, const int32_t* sel_in, int64_t
     ST_TRY(clk.collect());
     h->pending = j;
     h->live = true;
+    if (hbad)
+        return fail(MACHIP_NOT_CONVERGED, "exchange: 1 - s_e of a removal or 1 + s_f of an insertion is not positive, or no finite Delta (the selection holds a bridge of the graph, or lost numerically)");
+    *n_swaps = t;
+    for (int e = 0, q = 0; e < m; ++e) if (in_sel[(size_t)e]) sel_out[q++] = e;
+    if (t_ms) {
+        float ms = 0.0f;
+        HIP_TRY(hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
+        t_ms[0] = ms;
+        for (int q = 1; q < 6; ++q) t_ms[q] = clk.acc[q];
+    }
+    return MACHIP_OK;
+}
+
+// ---- the exchange in the candidates' space, on the edge-space relaxation's handles (esp_exchange_edge.h) ----
+
+int machip_esp_exchange_edge(machip_esp* h, int64_t k, const int32_t* sel_in, int64_t max_swaps, double min_gain, int32_t* sel_out,
+                             int32_t* out_idx, int32_t* in_idx, double* ratio, int64_t* n_swaps, int32_t* converged, double* t_ms) {
+    std::vector<int> rowe;
+    ST_TRY(esp_xch_check(h, k, sel_in, max_swaps, min_gain, sel_out, out_idx, in_idx, ratio, n_swaps, converged, rowe, true));
+    *n_swaps = 0;
+    *converged = 0;
+    ST_TRY(esp_relax_limits(h));
+    HIP_TRY(hipSetDevice(h->device));
+    const Options& O = default_options();
+    const int K = (int)k, m = h->m, B = kEspDefaultFold, ld = esp_xe_ld(h), zg = (ld + kBlock - 1) / kBlock;
+    const int chunks = std::max(1, std::min((m + kBlock - 1) / kBlock, (kEspXchTargetGroups + K - 1) / K));
+    const int per = ((m + chunks - 1) / chunks + 1) & ~1;      // (even: a chunk starts on a 16-byte boundary of its rows)
+    if (!h->xe) h->xe = new EspXchEdge();
+    EspXchEdge* E = h->xe;
+    ST_TRY(esp_xch_prepare(E->x, (size_t)K, (size_t)K * (size_t)chunks, (size_t)std::max<int64_t>(max_swaps, 1), (size_t)ld));      // (T is refused before G is built)
+    ST_TRY(esp_relax_prepare(h));
+    if (const int stp = esp_xe_prepare(h, E)) {      // (nothing half-made stays on the handle)
+        esp_xe_release(h->xe);
+        return stp;
+    }
+    EspXch* X = E->x;
+    while (h->ev.size() < 2) {
+        hipEvent_t e;
+        HIP_TRY(hipEventCreate(&e));
+        h->ev.push_back(e);
+    }
+    XchClock clk{h, O.get(kOpt_esp_xch_profile, 0) != 0, 2};
+    enum { kLoad = 1, kPairs = 2, kTrows = 3, kSteps = 4, kFolds = 5 };
+    hipStream_t st = h->stream;
+    const EspView V = E->view();
+    const int M = E->M, P = E->grid(), tiles = ld / kGjT;
+    std::vector<char> in_sel((size_t)m, 0);
+    for (int e : rowe) in_sel[(size_t)e] = 1;
+    double* Rm = nullptr;
+    int j = 0;      // columns of Zb pending
+    // one rank-1 update of R: row e less the pending columns into Zb[:, j], all M scores, T's rows (with_rows), the fold when Zb is full
+    auto step = [&](int e, int mode, double* rt, bool with_rows, int xrow, int f_in) -> int {
+        k_esp_xch_step<<<zg, kBlock, 0, st>>>(V, Rm, j, e, mode, rt, X->scale);
+        k_esp_update<<<P, kBlock, 0, st>>>(V, j);
+        if (mode > 0) k_esp_xe_entered<<<1, kBlock, 0, st>>>(V, e, j, X->scale);      // (s_e / (1 + s_e) without the cancellation)
+        if (with_rows) ST_TRY(clk.mark(kSteps));      // (the load is one interval, marked at its end)
+        if (with_rows) {
+            k_esp_xch_tupdate<<<dim3((unsigned)K, (unsigned)zg), kBlock, 0, st>>>(V, X->T, X->rowe, j, xrow, f_in, X->scale);
+            ST_TRY(clk.mark(kTrows));
+        }
+        if (++j == B) {
+            k_esp_fold<<<dim3(tiles, tiles), 256, 0, st>>>(Rm, E->Zb, E->cb, ld, B);
+            j = 0;
+            if (with_rows) ST_TRY(clk.mark(kFolds));
+        }
+        return MACHIP_OK;
+    };
+    // the load: R <- G, the scores, the seeds and then the K given candidates (ascending) as forced picks, then T
+    HIP_TRY(hipEventRecord(h->ev[0], st));
+    ST_TRY(clk.mark(-1));
+    ST_TRY(esp_xe_load_gram(h, E, &Rm));
+    HIP_TRY(hipMemsetAsync(E->sel, 0, sizeof(int) * (size_t)ld, st));
+    HIP_TRY(hipMemsetAsync(E->bad, 0, sizeof(int), st));
+    HIP_TRY(hipMemcpyAsync(X->rowe, rowe.data(), sizeof(int) * (size_t)K, hipMemcpyHostToDevice, st));
+    k_esp_scores<<<P, kBlock, 0, st>>>(V, Rm, 0);
+    for (int q = m; q < M; ++q) ST_TRY(step(q, 1, nullptr, false, -1, -1));
+    for (int q = 0; q < K; ++q) ST_TRY(step(rowe[(size_t)q], 1, nullptr, false, -1, -1));
+    if (max_swaps > 0) k_esp_xch_tbuild<<<dim3((unsigned)K, (unsigned)zg), kBlock, 0, st>>>(V, Rm, j, X->rowe, X->T);
+    HIP_TRY(hipGetLastError());
+    ST_TRY(clk.mark(kLoad));
+    int64_t t = 0;
+    int hbad = 0;
+    for (; t < max_swaps; ++t) {
+        k_esp_xch_pairs_edge<<<dim3((unsigned)K, (unsigned)chunks), kBlock, 0, st>>>(V, m, X->T, X->rowe, per, X->pv, X->pf);
+        k_esp_xch_argmax<<<1, kBlock, 0, st>>>(V, X->rowe, X->pv, X->pf, K * chunks, chunks, X->best);
+        HIP_TRY(hipGetLastError());
+        ST_TRY(clk.mark(kPairs));
+        EspXchBest b;
+        HIP_TRY(hipMemcpyAsync(&b, X->best, sizeof(b), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(&hbad, E->bad, sizeof(int), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        ST_TRY(clk.collect());
+        if (hbad) break;
+        if (b.val - 1.0 <= min_gain) { *converged = 1; break; }
+        ST_TRY(esp_xch_apply(rowe, in_sel, b.row, b.e, b.f));
+        out_idx[t] = b.e;
+        in_idx[t] = b.f;
+        ST_TRY(clk.mark(-1));
+        ST_TRY(step(b.e, -1, X->ratio + t, true, b.row, -1));
+        ST_TRY(step(b.f, +1, X->ratio + t, true, b.row, b.f));
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipEventRecord(h->ev[1], st));
+    if (t > 0) HIP_TRY(hipMemcpyAsync(ratio, X->ratio, sizeof(double) * (size_t)t, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&hbad, E->bad, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    ST_TRY(clk.collect());
     if (hbad)
         return fail(MACHIP_NOT_CONVERGED, "exchange: 1 - s_e of a removal or 1 + s_f of an insertion is not positive, or no finite Delta (the selection holds a bridge of the graph, or lost numerically)");
     *n_swaps = t;

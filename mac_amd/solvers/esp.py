@@ -21,9 +21,10 @@ from mac_amd import _lib
 from mac_amd.utils.graphs import Edge, edges_to_arrays, weight_reduced_graph_lap_from_edge_list
 
 
-def exchange_on(dev, candidate_edges, selection, max_swaps=None, min_gain=1e-9):
-    """``GreedyESP.exchange`` on the handle ``dev`` (a ``_lib.Esp``): shared with ``ESPRelaxation.exchange``."""
-    if dev.matrix_free:
+def exchange_on(dev, candidate_edges, selection, max_swaps=None, min_gain=1e-9, *, edge=False):
+    """``GreedyESP.exchange`` on the handle ``dev`` (a ``_lib.Esp``): shared with ``ESPRelaxation.exchange`` and, with
+    ``edge=True`` (the handle's ``exchange_edge`` instead of its ``exchange``), with ``ESPRelaxation.exchange_edge``."""
+    if not edge and dev.matrix_free:
         raise ValueError("exchange works on the dense inverse: not available with matrix_free=" + repr(dev.matrix_free))
     m = len(candidate_edges)
     sel = np.asarray(selection)
@@ -35,7 +36,7 @@ def exchange_on(dev, candidate_edges, selection, max_swaps=None, min_gain=1e-9):
         raise ValueError("selection must be a 0/1 array of length m or a sequence of candidate indices")
     if max_swaps is None:
         max_swaps = 10 * len(sel)
-    r = dev.exchange(sel, max_swaps, min_gain)
+    r = (dev.exchange_edge if edge else dev.exchange)(sel, max_swaps, min_gain)
     result = np.zeros(m)
     result[r["selection"]] = 1.0
     info = {"swaps": r["swaps"], "out": r["out"], "in": r["in"], "ratios": r["ratios"],

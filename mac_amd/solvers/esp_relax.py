@@ -76,10 +76,18 @@ class ESPRelaxation:
         ``upper`` >= F of every k-edge selection.  The loop runs on the C side (machip_esp_relax_run).  ``exchange=True``: the
         rounded selection is polished by best-swap local search on the same handle (``exchange``) before it is returned; node
         space and connected fixed graphs only (ValueError on an ``edge_space`` handle, which keeps no dense inverse, and on a
-        handle with beta != 0, both before any iteration)."""
-        if exchange and self.edge_space:
-            raise ValueError(f"exchange=True needs the dense inverse: not available with edge_space={self.edge_space!r}")
-        if exchange and k < len(self.weights) and self._dev.info()["beta"] != 0.0:      # (refused before the Frank-Wolfe run, not after it)
+        handle with beta != 0, both before any iteration).  ``exchange="edge"``: the same polish by ``exchange_edge``, on an
+        ``edge_space`` handle only (ValueError on a node-space handle, and for any other string, before any iteration)."""
+        if isinstance(exchange, str):
+            if exchange != "edge":
+                raise ValueError(f'exchange must be False, True or "edge", not {exchange!r}')
+            if not self.edge_space:
+                raise ValueError('exchange="edge" works on the Gram matrix of an edge_space handle: this one has edge_space=False '
+                                 "(use exchange=True)")
+        elif exchange and self.edge_space:
+            raise ValueError(f"exchange=True needs the dense inverse: not available with edge_space={self.edge_space!r} "
+                             '(use exchange="edge")')
+        if exchange and not isinstance(exchange, str) and k < len(self.weights) and self._dev.info()["beta"] != 0.0:      # (refused before the Frank-Wolfe run, not after it)
             raise ValueError("exchange=True needs a connected fixed graph: this handle has beta = %g" % self._dev.info()["beta"])
         m = len(self.weights)
         if k >= m:
@@ -99,14 +107,24 @@ class ESPRelaxation:
         else:
             rounded = round_nearest(w, k, self.weights, 10)
         if exchange:
-            rounded = self.exchange(rounded)[0]
+            rounded = (self.exchange_edge if isinstance(exchange, str) else self.exchange)(rounded)[0]
         return rounded, w, float(r["upper"])
 
     def exchange(self, selection, max_swaps=None, min_gain=1e-9):
         """``GreedyESP.exchange`` on this handle: ``(result, selected_edges, info)``."""
         if self.edge_space:
-            raise ValueError(f"exchange needs the dense inverse: not available with edge_space={self.edge_space!r}")
+            raise ValueError(f"exchange needs the dense inverse: not available with edge_space={self.edge_space!r} (use exchange_edge)")
         return exchange_on(self._dev, self.all_candidate_edges, selection, max_swaps, min_gain)
+
+    def exchange_edge(self, selection, max_swaps=None, min_gain=1e-9):
+        """``exchange`` for an ``edge_space`` handle: the same best-swap local search carried out on the (m + r) x (m + r) Gram
+        matrix the relaxation works with (mac_amd/csrc/esp_exchange_edge.h), so it runs at any num_nodes.
+        ``selection`` and the returned ``(result, selected_edges, info)`` are those of ``GreedyESP.exchange``.  ValueError on a
+        node-space handle (``edge_space=False``), before any device work.  (This second spelling exists only because ``exchange``
+        and ``solve(exchange=True)`` are pinned to refuse ``edge_space`` handles; folding the two into one is left for later.)"""
+        if not self.edge_space:
+            raise ValueError("exchange_edge works on the Gram matrix of an edge_space handle: this one has edge_space=False (use exchange)")
+        return exchange_on(self._dev, self.all_candidate_edges, selection, max_swaps, min_gain, edge=True)
 
     def info(self) -> dict:
         """The handle's description (GreedyESP.info), the space the relaxation works in (relax_form = "node" | "edge" | "edge_tree") with the
