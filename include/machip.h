@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define MACHIP_ABI_VERSION 14   /* 14: machip_esp_exchange_edge (the exchange in the candidates' space on MACHIP_ESP_EDGE_RELAX / MACHIP_ESP_EDGE_RELAX_TREE handles); 13: machip_esp_exchange (best-swap local search on the log tree count; options esp_xch_lds_kb, esp_xch_max_mb, esp_xch_profile); 12: MACHIP_ESP_EDGE_RELAX (the relaxation in the candidates' space on a chain-fixed graph; machip_esp_relax_info); 11: MACHIP_ESP_SPANNING_TREE (the matrix-free route of GreedyESP for any connected fixed graph; machip_esp_tree_plan, machip_esp_seeds); 10: MACHIP_ESP_MATRIX_FREE (GreedyESP on a chain without a dense Sigma, option esp_free_split); 9: the relaxation of GreedyESP's problem (machip_esp_relax_*); 8: GreedyEig handle (machip_eig_*); 7: GreedyESP handle (machip_esp_*); 6: machip_solve_stats.drift, machip_panel_plan fills 12 entries; 5: per-handle option table (machip_set_option), machip_comm_drop_ipc; 4: inter-process communicator */
+#define MACHIP_ABI_VERSION 15   /* 15: machip_eig_exchange (best-swap local search on lambda_2; option eig_xch_max_mb); 14: machip_esp_exchange_edge (the exchange in the candidates' space on MACHIP_ESP_EDGE_RELAX / MACHIP_ESP_EDGE_RELAX_TREE handles); 13: machip_esp_exchange (best-swap local search on the log tree count; options esp_xch_lds_kb, esp_xch_max_mb, esp_xch_profile); 12: MACHIP_ESP_EDGE_RELAX (the relaxation in the candidates' space on a chain-fixed graph; machip_esp_relax_info); 11: MACHIP_ESP_SPANNING_TREE (the matrix-free route of GreedyESP for any connected fixed graph; machip_esp_tree_plan, machip_esp_seeds); 10: MACHIP_ESP_MATRIX_FREE (GreedyESP on a chain without a dense Sigma, option esp_free_split); 9: the relaxation of GreedyESP's problem (machip_esp_relax_*); 8: GreedyEig handle (machip_eig_*); 7: GreedyESP handle (machip_esp_*); 6: machip_solve_stats.drift, machip_panel_plan fills 12 entries; 5: per-handle option table (machip_set_option), machip_comm_drop_ipc; 4: inter-process communicator */
 
 typedef enum machip_status {
     MACHIP_OK = 0,
@@ -539,6 +539,33 @@ int machip_eig_candidate_bounds(machip_eig* h, double* out);
  * beta_lambda2 = {beta (always 0), current lambda_2}; per pick of the last run (at most cap entries): candidates solved exactly and
  * operator applications (summed over the columns). */
 int machip_eig_info(machip_eig* h, int32_t* info6, double* beta_lambda2, int64_t cap, int32_t* solved_out, int32_t* applies_out);
+/* Best-swap local search on lambda_2 (mac_amd/csrc/eig_exchange.h) from the k-edge selection sel_in (k distinct candidate
+ * indices, any order).  With S the selection and L_S the fixed graph plus S, a round
+ *   1. solves the K removal pairs (lambda_2(S \ e), v^-e), e in S, as columns of the batch solver (a removal is the candidate with
+ *      weight -w_e; the downdate coefficient is -w_e / (1 - w_e s_e));
+ *   2. bounds every pair: u(e, f) = lambda_2(S \ e) + w_f (v^-e_i - v^-e_j)^2 >= lambda_2(S \ e + f) (concavity; one kernel, K x m);
+ *   3. solves exactly, row after row in decreasing order of the row's largest bound and inside a row in decreasing order of the
+ *      bound, only what can still exceed max(tau, top): tau = lambda_2(S) + min_gain, top the largest value solved in the round;
+ *   4. scans the solved pairs in (e, f) order: a pair replaces the running value (initially tau) only if it exceeds it by more than
+ *      1e-8.  No pair: *converged = 1 and the call returns.  Else the swap is applied (two columns of the low-rank block, folded when
+ *      due) and the new Fiedler pair polished.
+ * The call stops with *converged = 0 after max_swaps swaps (max_swaps = 0 is legal: the selection is loaded, lambda2_out[0]
+ * reported).  Every accepted swap raises lambda_2 by more than 1e-8; every reported lambda_2 obeys GreedyEig's stop rule.
+ * Outputs, any of which may be NULL: sel_out[k] the final selection ascending; out_idx[t], in_idx[t] the edges of swap
+ * t < *n_swaps (max_swaps entries each); lambda2_out[max_swaps + 1]: entry 0 is lambda_2 of sel_in, entry t + 1 lambda_2 after swap
+ * t; counts[3 max_swaps]: per round r < *n_swaps + *converged the triple {pairs solved exactly, operator applications summed over
+ * all columns of the round, removal pairs solved}; t_ms[2] = {wall time of the call, device time between its first and last
+ * command}.  Results are a function of the inputs alone: runs repeat bit for bit.  The call keeps k Fiedler vectors and k rows of
+ * bounds (8 k (ldv + ldm) bytes; ldv = n rounded up to 64, ldm = m rounded up to 4), made by the first call, freed by
+ * machip_eig_destroy.
+ * MACHIP_BAD_ARG, decided on the host (machip_last_error names the reason): NULL handle or sel_in; k < 1 or k >= m; an index
+ * outside [0, m); a repeated index; max_swaps < 0; min_gain < 0 or not finite; 8 k (ldv + ldm) bytes beyond the device's free
+ * memory (or option eig_xch_max_mb, MiB).  MACHIP_NOT_CONVERGED: a Fiedler solve missed the stop rule (the handle is reset).
+ * Afterwards machip_eig_candidate_lambda2, machip_eig_candidate_bounds and machip_eig_info (its per-pick arrays: per round) refer
+ * to the fixed graph plus sel_out; machip_eig_select resets as it always has. */
+int machip_eig_exchange(machip_eig* h, int64_t k, const int32_t* sel_in, int64_t max_swaps, double min_gain, int32_t* sel_out,
+                        int32_t* out_idx, int32_t* in_idx, double* lambda2_out, int64_t* n_swaps, int32_t* converged, int32_t* counts,
+                        double* t_ms);
 
 #ifdef __cplusplus
 }

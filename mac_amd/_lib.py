@@ -126,6 +126,8 @@ SIGNATURES = {
     "machip_eig_candidate_lambda2": (C.c_int, [C.c_void_p, _f64p]),
     "machip_eig_candidate_bounds": (C.c_int, [C.c_void_p, _f64p]),
     "machip_eig_info": (C.c_int, [C.c_void_p, _i32p, _f64p, C.c_int64, _i32p, _i32p]),
+    "machip_eig_exchange": (C.c_int, [C.c_void_p, C.c_int64, _i32p, C.c_int64, C.c_double, _i32p, _i32p, _i32p, _f64p,
+                                      C.POINTER(C.c_int64), C.POINTER(C.c_int32), _i32p, _f64p]),
 }
 
 
@@ -691,6 +693,24 @@ class Eig:
         out = np.empty(max(self.m, 1))
         check(self._lib.machip_eig_candidate_bounds(self._h, p_f64(out)))
         return out[:self.m]
+
+    def exchange(self, sel, max_swaps, min_gain=0.0):
+        """Best-swap local search on lambda_2 from the selection ``sel`` (candidate indices; machip_eig_exchange):
+        dict(selection int32[K] ascending, out, in (one entry per swap), lambda2 float64[swaps + 1], swaps, converged,
+        solved, applications, removal_solves (one entry per round), t_ms float64[2])."""
+        sel = i32(sel)
+        K, S = len(sel), max(int(max_swaps), 0)
+        sel_out = np.empty(max(K, 1), dtype=np.int32)
+        out, inn = np.empty(max(S, 1), dtype=np.int32), np.empty(max(S, 1), dtype=np.int32)
+        lam, counts = np.empty(S + 1), np.zeros(3 * max(S, 1), dtype=np.int32)
+        n, conv, t = C.c_int64(0), C.c_int32(0), np.zeros(2)
+        check(self._lib.machip_eig_exchange(self._h, K, p_i32(sel), int(max_swaps), float(min_gain), p_i32(sel_out), p_i32(out),
+                                            p_i32(inn), p_f64(lam), C.byref(n), C.byref(conv), p_i32(counts), p_f64(t)))
+        q = int(n.value)
+        c = counts[:3 * (q + int(conv.value))].reshape(-1, 3)
+        return {"selection": sel_out[:K], "out": out[:q], "in": inn[:q], "lambda2": lam[:q + 1], "swaps": q,
+                "converged": int(conv.value), "solved": c[:, 0].copy(), "applications": c[:, 1].copy(),
+                "removal_solves": c[:, 2].copy(), "t_ms": t}
 
     def info(self):
         """dict(form, ld, fold, batch, pending, beta, lambda2, solved[picks], applications[picks])."""

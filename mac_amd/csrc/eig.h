@@ -322,6 +322,8 @@ __global__ __launch_bounds__(kBlock) void k_eig_rr(EigView E, const double* __re
     if (tid == 0) { E.hasp[b] = 1; E.iters[b] += 1; }
 }
 
+struct EigXch;      // eig_exchange.h: the exchange's candidate arrays, removal pairs and bound matrix, made by its first call
+
 }  // namespace machip
 
 // ---- the handle (include/machip.h: machip_eig) ----
@@ -342,16 +344,26 @@ struct machip_eig {
     double maxdeg = 0.0, lam0 = 0.0, lamcur = 0.0, tol = machip::kEigTol;
     size_t nnz_cap = 0;
     std::vector<int> solved, applies;    // per pick of the last run
+    std::vector<int> removal;            // per round of the last exchange: removal pairs solved (eig_exchange.h)
+    machip::EigXch* xc = nullptr;
+    const int *xcu = nullptr, *xcv = nullptr;      // while an exchange runs: its own candidate arrays (the m candidates, then
+    const double* xcw = nullptr;                   // the negated copies of the selected ones); NULL: the greedy's
     std::vector<int> h_bc, h_conv;
     std::vector<double> h_lam;
 
     machip::EigView view() const {
         machip::EigView E;
         E.n = n; E.np = base->np; E.ld = base->ld; E.ldv = ldv; E.ldq = ldq; E.rp = rp; E.cj = cj; E.cv = cv; E.deg = deg; E.maxdeg = maxdeg;
-        E.cu = base->cu; E.cv2 = base->cv; E.cw = base->cw; E.bc = bc; E.X = X; E.P = P; E.W = W; E.LX = LX; E.LW = LW; E.LP = LP;
+        E.cu = xcu ? xcu : base->cu; E.cv2 = xcv ? xcv : base->cv; E.cw = xcw ? xcw : base->cw; E.bc = bc; E.X = X; E.P = P; E.W = W; E.LX = LX; E.LW = LW; E.LP = LP;
         E.Q = Q; E.T = T; E.Z = Z; E.cc = cc; E.lam = lam; E.res = res; E.conv = conv; E.iters = iters; E.hasp = hasp; E.nactive = nactive;
         E.rbest = rbest; E.stall = stall; E.tol = tol;
         return E;
+    }
+
+    machip::EspView zview() const {      // what k_eig_z reads the candidates from
+        machip::EspView V = base->view();
+        if (xcu) { V.cu = xcu; V.cv = xcv; V.cw = xcw; }
+        return V;
     }
 
     int alloc() {
@@ -411,7 +423,7 @@ struct machip_eig {
         hipStream_t st = base->stream;
         HIP_TRY(hipMemcpyAsync(bc, bcand, sizeof(int) * (size_t)count, hipMemcpyHostToDevice, st));
         const EigView E = view();
-        const EspView V = base->view();
+        const EspView V = zview();
         const int zg = (base->ld + kBlock - 1) / kBlock;
         k_eig_z<<<dim3(zg, count), kBlock, 0, st>>>(V, base->sig, base->pending, bc, Z, cc);
         k_eig_init<<<dim3((n + kBlock - 1) / kBlock, count), kBlock, 0, st>>>(E, vstart);
@@ -449,7 +461,7 @@ struct machip_eig {
         ST_TRY(upload_graph());
         HIP_TRY(hipMemcpyAsync(vcur, v0, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, st));
         lamcur = lam0;
-        solved.clear(); applies.clear();
+        solved.clear(); applies.clear(); removal.clear();
         return MACHIP_OK;
     }
 

@@ -23,6 +23,7 @@
 #include "esp_exchange.h"
 #include "esp_exchange_edge.h"
 #include "eig.h"
+#include "eig_exchange.h"
 
 namespace machip {
 thread_local std::string g_err;
@@ -2268,6 +2269,7 @@ void machip_eig_destroy(machip_eig* h) {
     if (!h) return;
     (void)hipSetDevice(h->base->device);
     if (h->base->stream) (void)hipStreamSynchronize(h->base->stream);
+    eig_xch_release(h->xc);
     h->release();
     machip_esp_destroy(h->base);
     delete h;
@@ -2278,6 +2280,22 @@ int machip_eig_select(machip_eig* h, int64_t k, int32_t* order_out, double* lamb
     if (k > h->m) return fail(MACHIP_BAD_ARG, "not enough candidate edges to satisfy the budget");
     HIP_TRY(hipSetDevice(h->base->device));
     return h->select((int)k, order_out, lambda2_out, t_ms_out);
+}
+
+int machip_eig_exchange(machip_eig* h, int64_t k, const int32_t* sel_in, int64_t max_swaps, double min_gain, int32_t* sel_out,
+                        int32_t* out_idx, int32_t* in_idx, double* lambda2_out, int64_t* n_swaps, int32_t* converged, int32_t* counts, double* t_ms) {
+    std::vector<int> rowe;
+    ST_TRY(eig_xch_check(h, k, sel_in, max_swaps, min_gain, rowe));
+    if (n_swaps) *n_swaps = 0;
+    if (converged) *converged = 0;
+    HIP_TRY(hipSetDevice(h->base->device));
+    const int st = eig_exchange(h, rowe, max_swaps, min_gain, sel_out, out_idx, in_idx, lambda2_out, n_swaps, converged, counts, t_ms);
+    h->xcu = h->xcv = nullptr; h->xcw = nullptr;
+    if (st != MACHIP_OK) {      // (a solve that did not converge, a HIP error: back to the fixed graph, the message kept)
+        const std::string msg = machip_last_error();
+        if (h->reset() == MACHIP_OK) return fail((machip_status)st, msg);
+    }
+    return st;
 }
 
 int machip_eig_candidate_lambda2(machip_eig* h, double* out) {

@@ -37,7 +37,10 @@ namespace machip {
     X(esp_free_split)                                                                                                              \
     /* the exchange (esp_exchange.h; process defaults, read by every machip_esp_exchange call): KiB of LDS a row of T may take   \
        (0: rows are read from global memory); a cap on T in MiB below the device's free memory; 1: time the phases of a round */   \
-    X(esp_xch_lds_kb) X(esp_xch_max_mb) X(esp_xch_profile)
+    X(esp_xch_lds_kb) X(esp_xch_max_mb) X(esp_xch_profile)                                                                         \
+    /* the exchange on lambda_2 (eig_exchange.h; process default, read by every machip_eig_exchange call): a cap in MiB, below     \
+       the device's free memory, on the removal vectors and the bound matrix */                                                   \
+    X(eig_xch_max_mb)
 
 enum OptId {
 #define X(n) kOpt_##n,

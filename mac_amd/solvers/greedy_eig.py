@@ -24,6 +24,19 @@ from mac_amd.utils import fiedler as _fiedler
 from mac_amd.utils.graphs import Edge, edges_to_arrays, weight_graph_lap_from_edge_list, weight_graph_lap_from_edges
 
 
+def selection_indices(selection, m):
+    """The candidate indices ``selection`` names: a 0/1 array of length m, or a sequence of indices (``GreedyESP.exchange``'s rule
+    and its errors; decided before any device is asked for)."""
+    sel = np.asarray(selection)
+    if sel.ndim != 1:
+        raise ValueError("selection must be a 0/1 array of length m or a sequence of candidate indices")
+    if len(sel) == m and set(np.unique(sel).tolist()) <= {0, 1}:
+        return np.flatnonzero(sel)
+    if sel.dtype.kind not in "iu":
+        raise ValueError("selection must be a 0/1 array of length m or a sequence of candidate indices")
+    return sel
+
+
 class GreedyEig:
     def __init__(self, odom_measurements: List[Edge], lc_measurements: List[Edge], num_poses: int, *, device: int = 0,
                  batch: int = 512, fold: int = 16, dense_inverse: bool = False):
@@ -77,6 +90,28 @@ class GreedyEig:
         self.last_times = t_ms / 1e3
         solution[order] = 1.0
         return solution, [Edge(int(self.edge_list[e, 0]), int(self.edge_list[e, 1]), float(self.weights[e])) for e in order]
+
+    def exchange(self, selection, max_swaps: Optional[int] = None, min_gain: float = 0.0):
+        """Best-swap local search on lambda_2 from ``selection``: a 0/1 array of length m or a sequence of candidate indices.
+        Every round takes the (selected, unselected) pair whose swap raises lambda_2 most -- found among the pairs whose
+        concavity bound lambda_2(S - e) + w_f (v_i - v_j)^2 (v the Fiedler vector without e) can still win, by the scan ``subset``
+        uses: (out, in) index order, a pair replaces the running value, initially lambda_2 + ``min_gain``, only if it exceeds it
+        by more than 1e-8 -- and stops when no pair does, or after ``max_swaps`` swaps (None: 10 K, a cap, not a tuning).
+        Returns ``(result, selected_edges, info)``: the 0/1 array, the edges in index order, and ``info = dict(swaps: list of
+        (out, in), lambda2: swaps + 1 values starting with the given selection's, converged, solved, applies, removal_solves:
+        per round the pairs solved exactly, the operator applications and the removal pairs solved, t_ms: wall and device
+        milliseconds of the call)``.  Afterwards ``candidate_lambda2``, ``candidate_bounds`` and ``info`` refer to the result
+        (DESIGN section 20)."""
+        m = len(self.weights)
+        sel = selection_indices(selection, m)
+        if max_swaps is None:
+            max_swaps = 10 * len(sel)
+        r = self._dev.exchange(sel, max_swaps, min_gain)
+        result = np.zeros(m)
+        result[r["selection"]] = 1.0
+        info = {"swaps": [(int(a), int(b)) for a, b in zip(r["out"], r["in"])], "lambda2": r["lambda2"], "converged": bool(r["converged"]),
+                "solved": r["solved"], "applies": r["applications"], "removal_solves": r["removal_solves"], "t_ms": r["t_ms"]}
+        return result, [Edge(int(self.edge_list[e, 0]), int(self.edge_list[e, 1]), float(self.weights[e])) for e in r["selection"]], info
 
     def candidate_lambda2(self) -> np.ndarray:
         """lambda_2(L_cur + e) of every candidate (NaN for the selected), L_cur = the fixed graph plus the last run's picks."""

@@ -44,6 +44,8 @@ class MAC:
 
         self.L_fixed = weight_graph_lap_from_edge_list(fixed_edges, num_nodes)   # mac.py:55
         self.num_nodes = num_nodes
+        self._edges = (fixed_edges, candidate_edges, device)        # what ``exchange`` builds its GreedyEig from
+        self._greedy_eig = None
         fi, fj, fw = edges_to_arrays(fixed_edges)
         ci, cj, cw = edges_to_arrays(candidate_edges)
         self.weights = cw                                            # mac.py:58-65
@@ -153,11 +155,24 @@ class MAC:
             self.sweep_trace = r["f_traj"]
         return out
 
+    def exchange(self, selection, max_swaps=None, min_gain=0.0):
+        """``GreedyEig.exchange`` (best-swap local search on lambda_2) on these edges and this device: the
+        GreedyEig is built on first use and kept.  Returns its ``(result, selected_edges, info)``."""
+        from mac_amd.solvers.greedy_eig import GreedyEig, selection_indices
+        sel = selection_indices(selection, len(self.weights))
+        if self._greedy_eig is None:
+            fixed, cand, device = self._edges
+            self._greedy_eig = GreedyEig(fixed, cand, self.num_nodes, device=device)
+        return self._greedy_eig.exchange(sel, max_swaps, min_gain)
+
     def solve(self, k, x_init=None, rounding="nearest", fallback=False, max_iters=5,
               relative_duality_gap_tol=1e-4, grad_norm_tol=1e-8, random_rounding_max_iters=1,
-              verbose=False, return_rounding_time=False, use_cache=False):
+              verbose=False, return_rounding_time=False, use_cache=False, *, exchange=False):
         """Frank-Wolfe on the relaxation, then rounding (mac.py:130-225); returns
-        ``(rounded, unrounded, upper_bound[, rounding_time])``."""
+        ``(rounded, unrounded, upper_bound[, rounding_time])``.  ``exchange=True`` (not in the reference): the rounded selection
+        is polished by ``exchange`` -- lambda_2 of what is returned is not below the rounded one's; the unrounded solution and
+        the upper bound are the relaxation's, unchanged.  An integer instead of True caps the swaps (``max_swaps``); what the
+        polish did is kept in ``exchange_info``."""
         m = len(self.weights)
         if k >= m:                                                   # mac.py:173-180
             result = np.ones(m)
@@ -198,6 +213,9 @@ class MAC:
             # evident intent -- keep the initial point if rounding made it worse -- is implemented.
             if self.evaluate_objective(rounded) < self.evaluate_objective(x_init):
                 rounded = np.asarray(x_init, dtype=np.float64)
+
+        if exchange:
+            rounded, _, self.exchange_info = self.exchange(rounded, max_swaps=None if exchange is True else int(exchange))
 
         if return_rounding_time:
             return rounded, w, u, rounding_time
