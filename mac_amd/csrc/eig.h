@@ -253,13 +253,15 @@ __global__ __launch_bounds__(kBlock) void k_eig_rr(EigView E, const double* __re
         s += t;
     }
     const double mean = block_sum(s, sm) / n;
-    double xw = 0.0;
-    for (int i = tid; i < n; i += kBlock) { const double t = w[i] - mean; w[i] = t; xw = __builtin_fma(x[i], t, xw); }
-    xw = block_sum(xw, sm);
+    double xw = 0.0, ww0 = 0.0;
+    for (int i = tid; i < n; i += kBlock) { const double t = w[i] - mean; w[i] = t; xw = __builtin_fma(x[i], t, xw); ww0 = __builtin_fma(t, t, ww0); }
+    xw = block_sum(xw, sm); ww0 = block_sum(ww0, sm);
     double ww = 0.0;
     for (int i = tid; i < n; i += kBlock) { const double t = w[i] - xw * x[i]; w[i] = t; ww = __builtin_fma(t, t, ww); }
     ww = block_sum(ww, sm);
-    const double wi = ww > 0.0 ? 1.0 / sqrt(ww) : 0.0;
+    // w (nearly) a multiple of x -- always so for n = 2, where 1-perp is span{x}: what is left is rounding noise that would be
+    // normalised into a copy of x (a singular Gram matrix, x <- x - x).  Dropped like p below.
+    const double wi = ww > 1e-12 * ww0 ? 1.0 / sqrt(ww) : 0.0;
     const int hp = E.hasp[b];
     double xp = 0.0, wp = 0.0, pp0 = 0.0;
     for (int i = tid; i < n; i += kBlock) {

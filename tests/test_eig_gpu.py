@@ -211,6 +211,80 @@ def test_edge_cases_k_zero_k_too_large_disconnected():
         eig_of(n, fi[keep], fj[keep], fw[keep], ci, cj, cw)
 
 
+def edge_case_graph(tree):
+    """12 nodes, a fixed tree (the chain, or one that branches at node 0 and below) and candidates that are duplicates (one
+    reversed), a self-loop, parallel to a fixed link, at node 0, with weights from 1e-3 to 1e3."""
+    rng = np.random.default_rng(9)
+    n = 12
+    fi = np.arange(1, n)
+    fj = fi - 1 if tree == "chain" else np.array([0, 0, 1, 1, 2, 3, 3, 5, 6, 6, 8])
+    fw = rng.uniform(0.5, 2.0, n - 1)
+    cand = [(2, 7, 1.3), (7, 2, 1.3), (2, 7, 1.3),           # exact duplicates, one reversed
+            (5, 5, 2.0),                                      # self-loop: lambda_2(L_cur), and its bound is that
+            (int(fi[4]), int(fj[4]), 0.7),                    # parallel to a fixed link
+            (0, 9, 0.8), (11, 0, 1.1), (0, 4, 1e3),           # at node 0
+            (1, 10, 1e-3), (4, 8, 1e3), (6, 11, 0.03), (3, 9, 30.0)]
+    return n, fi, fj, fw, np.array([c[0] for c in cand]), np.array([c[1] for c in cand]), np.array([c[2] for c in cand])
+
+
+@pytest.mark.parametrize("tree", ["chain", "branching"])
+def test_edge_cases_duplicates_node0_selfloop_parallel(tree):
+    g = edge_case_graph(tree)
+    n, fi, fj, fw, ci, cj, cw = g
+    m, loop = len(cw), 3
+    L = R.laplacian(n, fi, fj, fw)
+    tol = 1e-8 * R.norm_inf_with(L, ci, cj, cw)
+    ge = eig_of(*g)
+    assert ge.info()["form"] == ("chain" if tree == "chain" else "dense")
+    lam, u = ge.candidate_lambda2(), ge.candidate_bounds()
+    ref, uref = R.values_brute(L, ci, cj, cw), R.bounds(L, ci, cj, cw)
+    print(tree, "max |lambda2 - ref| / tol:", float(np.max(np.abs(lam - ref) / tol)), "max rel bound error:", float(np.max(np.abs(u - uref) / np.abs(uref))))
+    assert np.all(np.abs(lam - ref) <= tol)
+    assert np.all(np.abs(u - uref) <= 1e-10 * np.abs(uref)) and np.all(u >= lam - tol)
+    assert u[loop] == ge.info()["lambda2"] and abs(lam[loop] - R.fiedler(L)[0]) <= tol[loop]
+    # a replay of all m picks (duplicates are equal Edge tuples: indices from the handle)
+    sol, sel = ge.subset(m)
+    order, lam2, _ = ge._dev.select(m)
+    assert sol.sum() == m and sorted(order.tolist()) == list(range(m)) and np.array_equal(lam2, ge.last_lambda2)
+    assert [(e.i, e.j, e.weight) for e in sel] == [(int(ci[e]), int(cj[e]), float(cw[e])) for e in order]
+    r = R.greedy(*g, m, method="brute", order=order)
+    for k in range(m):
+        tolL = 1e-8 * r["norms"][k].max()
+        vals = r["values"][k]
+        assert r["lam2"][k] >= np.nanmax(vals) - 1e-8 - 2 * tolL
+        assert abs(lam2[k] - r["lam2"][k]) <= tolL
+        if order[k] == loop:      # only when no other candidate raises lambda_2 by more than the tie tolerance (and the solver's error)
+            others = np.delete(vals, loop)
+            print(tree, "self-loop picked at", k, "of", m)
+            assert np.all(np.isnan(others)) or np.nanmax(others) - r["lam_before"][k] <= 1e-8 + 2 * tolL
+
+
+@pytest.mark.parametrize("n", [2, 3])
+def test_two_and_three_node_graphs(n):
+    """n' = 1 and 2: one 64-tile of Sigma that is nearly all padding; for n = 2 the start vector is the Fiedler vector already (a
+    zero residual at the start)."""
+    fi, fj, fw = np.arange(1, n), np.arange(n - 1), np.array([1.5, 0.75])[:n - 1]
+    cand = [(0, n - 1, 2.0), (n - 1, 0, 0.5), (1, 1, 3.0)] + ([(1, 2, 1e-3)] if n == 3 else [])
+    g = (n, fi, fj, fw, np.array([c[0] for c in cand]), np.array([c[1] for c in cand]), np.array([c[2] for c in cand]))
+    ci, cj, cw = g[4:]
+    m = len(cw)
+    L = R.laplacian(n, fi, fj, fw)
+    tol = 1e-8 * R.norm_inf_with(L, ci, cj, cw)
+    ge = eig_of(*g)
+    inf = ge.info()
+    assert inf["ld"] == 64 and abs(inf["lambda2"] - R.fiedler(L)[0]) <= 1e-8 * R.norm_inf(L)
+    lam, u = ge.candidate_lambda2(), ge.candidate_bounds()
+    assert np.all(np.abs(lam - R.values_brute(L, ci, cj, cw)) <= tol)
+    uref = R.bounds(L, ci, cj, cw)
+    assert np.all(np.abs(u - uref) <= 1e-10 * np.abs(uref)) and np.all(u >= lam - tol)
+    order, lam2, _ = ge._dev.select(m)
+    assert sorted(order.tolist()) == list(range(m))
+    r = R.greedy(*g, m, method="brute", order=order)
+    for k in range(m):
+        tolL = 1e-8 * r["norms"][k].max()
+        assert r["lam2"][k] >= np.nanmax(r["values"][k]) - 1e-8 - 2 * tolL and abs(lam2[k] - r["lam2"][k]) <= tolL
+
+
 def test_reference_example_lines_run(tmp_path):
     """The solver section of the reference's Petersen example, through the compat package, in a fresh interpreter."""
     import os, subprocess, sys
