@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define MACHIP_ABI_VERSION 15   /* 15: machip_eig_exchange (best-swap local search on lambda_2; option eig_xch_max_mb); 14: machip_esp_exchange_edge (the exchange in the candidates' space on MACHIP_ESP_EDGE_RELAX / MACHIP_ESP_EDGE_RELAX_TREE handles); 13: machip_esp_exchange (best-swap local search on the log tree count; options esp_xch_lds_kb, esp_xch_max_mb, esp_xch_profile); 12: MACHIP_ESP_EDGE_RELAX (the relaxation in the candidates' space on a chain-fixed graph; machip_esp_relax_info); 11: MACHIP_ESP_SPANNING_TREE (the matrix-free route of GreedyESP for any connected fixed graph; machip_esp_tree_plan, machip_esp_seeds); 10: MACHIP_ESP_MATRIX_FREE (GreedyESP on a chain without a dense Sigma, option esp_free_split); 9: the relaxation of GreedyESP's problem (machip_esp_relax_*); 8: GreedyEig handle (machip_eig_*); 7: GreedyESP handle (machip_esp_*); 6: machip_solve_stats.drift, machip_panel_plan fills 12 entries; 5: per-handle option table (machip_set_option), machip_comm_drop_ipc; 4: inter-process communicator */
+#define MACHIP_ABI_VERSION 16   /* 16: MACHIP_EIG_MATRIX_FREE (GreedyEig on a chain without a dense Sigma; options eig_free_rows, eig_free_split); 15: machip_eig_exchange (best-swap local search on lambda_2; option eig_xch_max_mb); 14: machip_esp_exchange_edge (the exchange in the candidates' space on MACHIP_ESP_EDGE_RELAX / MACHIP_ESP_EDGE_RELAX_TREE handles); 13: machip_esp_exchange (best-swap local search on the log tree count; options esp_xch_lds_kb, esp_xch_max_mb, esp_xch_profile); 12: MACHIP_ESP_EDGE_RELAX (the relaxation in the candidates' space on a chain-fixed graph; machip_esp_relax_info); 11: MACHIP_ESP_SPANNING_TREE (the matrix-free route of GreedyESP for any connected fixed graph; machip_esp_tree_plan, machip_esp_seeds); 10: MACHIP_ESP_MATRIX_FREE (GreedyESP on a chain without a dense Sigma, option esp_free_split); 9: the relaxation of GreedyESP's problem (machip_esp_relax_*); 8: GreedyEig handle (machip_eig_*); 7: GreedyESP handle (machip_esp_*); 6: machip_solve_stats.drift, machip_panel_plan fills 12 entries; 5: per-handle option table (machip_set_option), machip_comm_drop_ipc; 4: inter-process communicator */
 
 typedef enum machip_status {
     MACHIP_OK = 0,
@@ -369,7 +369,8 @@ typedef struct machip_esp machip_esp;
  * before anything is allocated.  Pick j streams 8 ld j bytes (about 4 ld K^2 over a run): the route is for K << n.  Same rule, tie
  * rule and per-entry arithmetic as the dense forms; the sums over the history run in a fixed order that depends on (ld, j, option
  * esp_free_split) alone, so runs repeat bit for bit and agree with the dense chain form to rounding.  machip_esp_relax_* (unless
- * the handle was made with MACHIP_ESP_EDGE_RELAX as well) and machip_eig_create answer MACHIP_BAD_ARG on this route. */
+ * the handle was made with MACHIP_ESP_EDGE_RELAX as well) and machip_eig_create (unless MACHIP_EIG_MATRIX_FREE is given as well)
+ * answer MACHIP_BAD_ARG on this route. */
 #define MACHIP_ESP_MATRIX_FREE 2
 /* flags, valid only together with MACHIP_ESP_MATRIX_FREE (MACHIP_BAD_ARG alone, with MACHIP_ESP_DENSE_INVERSE or with fold != 0):
  * the matrix-free route for ANY connected fixed graph (mac_amd/csrc/esp_tree.h).  Sigma0 is that of the spanning tree T that
@@ -522,9 +523,25 @@ int machip_esp_exchange_edge(machip_esp* h, int64_t k, const int32_t* sel_in, in
  * reduced Laplacian (the state of machip_esp), and takes the best by the reference's scan (candidate-index order, a candidate
  * replaces the running best only if it exceeds it by more than 1e-8).  Every reported lambda_2 satisfies the stop rule
  * ||L_e v - lambda v||_1 / ||L_e||_inf < 1e-8 (||v||_2 = 1), evaluated with the sparse Laplacian.  The fixed graph must be connected
- * (MACHIP_DISCONNECTED otherwise); size limits and flags as machip_esp_create. */
+ * (MACHIP_DISCONNECTED otherwise); size limits and flags as machip_esp_create, except that MACHIP_ESP_MATRIX_FREE is taken only together
+ * with MACHIP_EIG_MATRIX_FREE and MACHIP_ESP_SPANNING_TREE not at all (MACHIP_BAD_ARG). */
 typedef struct machip_eig machip_eig;
-/* fold: as machip_esp_create (0 = 16); batch: columns solved together (1..4096; 0 = 512).  Builds Sigma0 and the fixed graph's Fiedler pair. */
+/* flags of machip_eig_create only (machip_esp_create answers "unknown flags"), valid only as MACHIP_ESP_MATRIX_FREE |
+ * MACHIP_EIG_MATRIX_FREE: GreedyEig without a dense Sigma (mac_amd/csrc/eig_free.h).  The fixed edges must be exactly the connected
+ * chain (i, i+1), parallel links summed.  The preconditioner is applied as Sigma0 Q by two scans over the chain's prefix resistances
+ * minus the rank-j correction of the picks, which stay in the history of the MACHIP_ESP_MATRIX_FREE handle underneath (8 ld K bytes,
+ * sized by machip_eig_select for its budget; a K that does not fit in free device memory is MACHIP_BAD_ARG before anything is
+ * allocated, as are batch arrays -- about 8 (6 ldv + 3 ld) ldq bytes -- that do not fit, at create).  Nothing of size ld x ld exists:
+ * no limit on n but memory and int32 node ids.  One application costs 4 ld j B flop plus three passes over the batch instead of
+ * 2 ld^2 B.  Every lambda_2, stop rule and pick is decided by the sparse L_cur as on the dense route; the order of every sum depends on
+ * (ld, j, the batch, options eig_free_rows / eig_free_split) alone, so runs repeat bit for bit.  MACHIP_BAD_ARG, decided on the host
+ * before a device is touched: the flag alone, with MACHIP_ESP_DENSE_INVERSE, with fold != 0 (nothing is folded: an argument without
+ * a meaning is refused, not ignored), or a fixed graph that is not the chain.  machip_eig_exchange answers MACHIP_BAD_ARG on such a
+ * handle.  The stop rule is relative to ||L_e||_inf: on a long chain (lambda_2 / ||L||_inf ~ pi^2 / 4 n^2 < 1e-8 from n ~ 16 000 on) it
+ * certifies little more than the sign of lambda_2 -- on this route as on the dense one. */
+#define MACHIP_EIG_MATRIX_FREE 64
+/* fold: as machip_esp_create (0 = 16; must be 0 with MACHIP_EIG_MATRIX_FREE); batch: columns solved together (1..4096; 0 = 512).
+ * Builds Sigma0 (unless matrix-free) and the fixed graph's Fiedler pair. */
 int machip_eig_create(int device, int64_t n, int64_t n_fixed, const int32_t* fi, const int32_t* fj, const double* fw,
                       int64_t m, const int32_t* ci, const int32_t* cj, const double* cw, int fold, int batch, int flags, machip_eig** out);
 void machip_eig_destroy(machip_eig* h);
@@ -535,7 +552,8 @@ int machip_eig_select(machip_eig* h, int64_t k, int32_t* order_out, double* lamb
 int machip_eig_candidate_lambda2(machip_eig* h, double* out);
 /* the bounds u_e (m doubles; NaN for the selected) from the current Fiedler pair. */
 int machip_eig_candidate_bounds(machip_eig* h, double* out);
-/* info6 = {form (0 chain, 1 dense inverse), leading dimension of Sigma, fold, batch, pending updates, picks of the last run};
+/* info6 = {form (0 chain, 1 dense inverse, 2 chain without Sigma: MACHIP_EIG_MATRIX_FREE), leading dimension of Sigma, fold (form 2: 0),
+ * batch, pending updates (form 2: the history's columns), picks of the last run};
  * beta_lambda2 = {beta (always 0), current lambda_2}; per pick of the last run (at most cap entries): candidates solved exactly and
  * operator applications (summed over the columns). */
 int machip_eig_info(machip_eig* h, int32_t* info6, double* beta_lambda2, int64_t cap, int32_t* solved_out, int32_t* applies_out);
@@ -560,7 +578,7 @@ int machip_eig_info(machip_eig* h, int32_t* info6, double* beta_lambda2, int64_t
  * machip_eig_destroy.
  * MACHIP_BAD_ARG, decided on the host (machip_last_error names the reason): NULL handle or sel_in; k < 1 or k >= m; an index
  * outside [0, m); a repeated index; max_swaps < 0; min_gain < 0 or not finite; 8 k (ldv + ldm) bytes beyond the device's free
- * memory (or option eig_xch_max_mb, MiB).  MACHIP_NOT_CONVERGED: a Fiedler solve missed the stop rule (the handle is reset).
+ * memory (or option eig_xch_max_mb, MiB); a MACHIP_EIG_MATRIX_FREE handle (no Sigma to exchange on).  MACHIP_NOT_CONVERGED: a Fiedler solve missed the stop rule (the handle is reset).
  * Afterwards machip_eig_candidate_lambda2, machip_eig_candidate_bounds and machip_eig_info (its per-pick arrays: per round) refer
  * to the fixed graph plus sel_out; machip_eig_select resets as it always has. */
 int machip_eig_exchange(machip_eig* h, int64_t k, const int32_t* sel_in, int64_t max_swaps, double min_gain, int32_t* sel_out,

@@ -481,6 +481,7 @@ ESP_MATRIX_FREE = 2        # MACHIP_ESP_MATRIX_FREE
 ESP_SPANNING_TREE = 8      # MACHIP_ESP_SPANNING_TREE (only together with ESP_MATRIX_FREE)
 ESP_EDGE_RELAX = 16        # MACHIP_ESP_EDGE_RELAX (only together with ESP_MATRIX_FREE alone: the chain)
 ESP_EDGE_RELAX_TREE = 32   # MACHIP_ESP_EDGE_RELAX_TREE (only as ESP_MATRIX_FREE | ESP_SPANNING_TREE | ESP_EDGE_RELAX_TREE)
+EIG_MATRIX_FREE = 64       # MACHIP_EIG_MATRIX_FREE (machip_eig_create only, and only as ESP_MATRIX_FREE | EIG_MATRIX_FREE)
 
 
 def host_esp_tree(n, fi, fj, fw):
@@ -648,9 +649,16 @@ class Esp:
 
 class Eig:
     """Owns one ``machip_eig`` handle: GreedyEig's state on one GPU -- the dense inverse of the reduced Laplacian (shared with
-    GreedyESP's machinery) and the batched Fiedler solves against it (mac_amd/csrc/eig.h)."""
+    GreedyESP's machinery) and the batched Fiedler solves against it (mac_amd/csrc/eig.h).
+    matrix_free=True: chain-fixed graphs only -- no dense inverse; Sigma0 is applied by two scans and the picks stay in a history
+    that ``select`` sizes for its budget (MACHIP_ESP_MATRIX_FREE | MACHIP_EIG_MATRIX_FREE, mac_amd/csrc/eig_free.h; process options
+    "eig_free_rows", "eig_free_split").  Nothing is folded on that route: ``fold`` must stay None there (ValueError otherwise; the C
+    entry point gets 0); on the dense routes None is 16."""
 
-    def __init__(self, n, fi, fj, fw, ci, cj, cw, fold=16, batch=512, dense_inverse=False, device=0):
+    def __init__(self, n, fi, fj, fw, ci, cj, cw, fold=None, batch=512, dense_inverse=False, device=0, *, matrix_free=False):
+        if matrix_free and fold is not None:
+            raise ValueError(f"matrix_free=True never folds: fold has no meaning on this route (got fold={fold!r}); leave it at None")
+        fold = 16 if fold is None else fold
         lib = load()
         require_device()
         self.n = int(n)
@@ -659,8 +667,9 @@ class Eig:
         self.m = int(len(cw))
         h = C.c_void_p()
         check(lib.machip_eig_create(int(device), self.n, len(fw), p_i32(fi), p_i32(fj), p_f64(fw), self.m,
-                                    p_i32(ci), p_i32(cj), p_f64(cw), int(fold), int(batch),
-                                    ESP_DENSE_INVERSE if dense_inverse else 0, C.byref(h)))
+                                    p_i32(ci), p_i32(cj), p_f64(cw), 0 if matrix_free else int(fold), int(batch),
+                                    (ESP_DENSE_INVERSE if dense_inverse else 0) | (ESP_MATRIX_FREE | EIG_MATRIX_FREE if matrix_free else 0),
+                                    C.byref(h)))
         self._h = h
         self._lib = lib
 
@@ -721,7 +730,7 @@ class Eig:
         solved = np.zeros(max(k, 1), dtype=np.int32)
         applies = np.zeros(max(k, 1), dtype=np.int32)
         check(self._lib.machip_eig_info(self._h, p_i32(a), p_f64(b), k, p_i32(solved), p_i32(applies)))
-        return dict(form="chain" if a[0] == 0 else "dense", ld=int(a[1]), fold=int(a[2]), batch=int(a[3]), pending=int(a[4]),
+        return dict(form=("chain", "dense", "chain_free")[a[0]], ld=int(a[1]), fold=int(a[2]), batch=int(a[3]), pending=int(a[4]),
                     beta=float(b[0]), lambda2=float(b[1]), solved=solved[:k].copy(), applications=applies[:k].copy())
 
 

@@ -16,7 +16,8 @@
 // proposes search directions, so an inexact inverse costs iterations, never accuracy, and cannot certify itself.  A column retires
 // when  ||r||_1 / ||L_e||_inf < 1e-8  with ||x||_2 = 1 (the stop rule of the reference's CholeskyFiedlerSolver).  Every column
 // starts from the current Fiedler vector.  Per iteration three launches (k_eig_resid, k_eig_product, k_eig_rr) and one 4-byte
-// read (the number of columns still active).
+// read (the number of columns still active).  On a MACHIP_EIG_MATRIX_FREE handle (form 2 of the machip_esp underneath: no Sigma) k_eig_z
+// and k_eig_product are replaced by the scans and history products of eig_free.h; everything else here is shared.
 #pragma once
 #include <algorithm>
 #include <chrono>
@@ -325,7 +326,17 @@ __global__ __launch_bounds__(kBlock) void k_eig_rr(EigView E, const double* __re
 }
 
 struct EigXch;      // eig_exchange.h: the exchange's candidate arrays, removal pairs and bound matrix, made by its first call
+struct EigFree;     // eig_free.h: the scan chunks and projection buffers of the route without Sigma (form 2 of the machip_esp underneath)
 
+}  // namespace machip
+
+struct machip_eig;
+namespace machip {
+// eig_free.h -- form 2 only: z_e / c_e of the batch's columns, T = Sigma_cur Q, the winner's column into the history, its room
+int eig_free_columns(machip_eig* h, int count);
+int eig_free_apply(machip_eig* h, int count);
+int eig_free_push(machip_eig* h);
+int eig_free_reserve(machip_eig* h, int64_t K);
 }  // namespace machip
 
 // ---- the handle (include/machip.h: machip_eig) ----
@@ -348,6 +359,7 @@ struct machip_eig {
     std::vector<int> solved, applies;    // per pick of the last run
     std::vector<int> removal;            // per round of the last exchange: removal pairs solved (eig_exchange.h)
     machip::EigXch* xc = nullptr;
+    machip::EigFree* fr = nullptr;       // form 2 (MACHIP_EIG_MATRIX_FREE): no Sigma, the preconditioner of eig_free.h
     const int *xcu = nullptr, *xcv = nullptr;      // while an exchange runs: its own candidate arrays (the m candidates, then
     const double* xcw = nullptr;                   // the negated copies of the selected ones); NULL: the greedy's
     std::vector<int> h_bc, h_conv;
@@ -361,6 +373,8 @@ struct machip_eig {
         E.rbest = rbest; E.stall = stall; E.tol = tol;
         return E;
     }
+
+    bool matrix_free() const { return base->form == machip::kEspFormFree; }
 
     machip::EspView zview() const {      // what k_eig_z reads the candidates from
         machip::EspView V = base->view();
@@ -427,7 +441,9 @@ struct machip_eig {
         const EigView E = view();
         const EspView V = zview();
         const int zg = (base->ld + kBlock - 1) / kBlock;
-        k_eig_z<<<dim3(zg, count), kBlock, 0, st>>>(V, base->sig, base->pending, bc, Z, cc);
+        const bool mf = matrix_free();
+        if (mf) ST_TRY(eig_free_columns(this, count));
+        else k_eig_z<<<dim3(zg, count), kBlock, 0, st>>>(V, base->sig, base->pending, bc, Z, cc);
         k_eig_init<<<dim3((n + kBlock - 1) / kBlock, count), kBlock, 0, st>>>(E, vstart);
         const dim3 pg((count + kGjT - 1) / kGjT, base->ld / kGjT);
         for (int it = 0; it <= kEigMaxIter + 1; ++it) {
@@ -438,8 +454,13 @@ struct machip_eig {
             HIP_TRY(hipStreamSynchronize(st));
             if (act == 0) break;
             if (napp) *napp += act;
-            k_eig_product<<<pg, 256, 0, st>>>(base->sig, E, count);
-            k_eig_rr<<<count, kBlock, 0, st>>>(E, base->Zb, base->cb, base->pending);
+            if (mf) {       // the history's correction is in T already: only the column's own term is left for k_eig_rr
+                ST_TRY(eig_free_apply(this, count));
+                k_eig_rr<<<count, kBlock, 0, st>>>(E, nullptr, nullptr, 0);
+            } else {
+                k_eig_product<<<pg, 256, 0, st>>>(base->sig, E, count);
+                k_eig_rr<<<count, kBlock, 0, st>>>(E, base->Zb, base->cb, base->pending);
+            }
         }
         HIP_TRY(hipGetLastError());
         h_lam.resize((size_t)count); h_conv.resize((size_t)count);
@@ -456,7 +477,7 @@ struct machip_eig {
     // state <- the fixed graph (Sigma0, no pending columns, its Fiedler pair)
     int reset() {
         hipStream_t st = base->stream;
-        HIP_TRY(hipMemcpyAsync(base->sig, base->sig0, sizeof(double) * (size_t)base->ld * (size_t)base->ld, hipMemcpyDeviceToDevice, st));
+        if (!matrix_free()) HIP_TRY(hipMemcpyAsync(base->sig, base->sig0, sizeof(double) * (size_t)base->ld * (size_t)base->ld, hipMemcpyDeviceToDevice, st));
         base->pending = 0;
         adj = adj0; hdeg = hdeg0;
         std::fill(sel.begin(), sel.end(), 0);
@@ -515,6 +536,7 @@ struct machip_eig {
     int select(int K, int32_t* order_out, double* lambda2_out, double* t_ms_out) {
         using namespace machip;
         hipStream_t st = base->stream;
+        if (matrix_free()) ST_TRY(eig_free_reserve(this, K));      // (refused before the state is touched)
         ST_TRY(reset());
         const auto t0 = std::chrono::steady_clock::now();
         std::vector<double> u, l2((size_t)m);
@@ -555,13 +577,17 @@ struct machip_eig {
             best_l2 = h_lam[0];
             HIP_TRY(hipMemcpyAsync(vcur, X, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, st));
             lamcur = best_l2;
-            // its z joins the pending block; fold when due
-            HIP_TRY(hipMemcpyAsync(bc, &best, sizeof(int), hipMemcpyHostToDevice, st));
-            HIP_TRY(hipStreamSynchronize(st));
-            const int j = base->pending;
-            k_eig_z<<<dim3((base->ld + kBlock - 1) / kBlock, 1), kBlock, 0, st>>>(base->view(), base->sig, j, bc, base->Zb + (size_t)j * (size_t)base->ld, base->cb + j);
-            base->pending = j + 1;
-            if (base->pending == base->fold) { base->fold_into(base->sig, base->pending); base->pending = 0; }
+            // its z joins the pending block; fold when due (form 2: the history, never folded -- the polished solve left z, c in column 0)
+            if (matrix_free()) {
+                ST_TRY(eig_free_push(this));
+            } else {
+                HIP_TRY(hipMemcpyAsync(bc, &best, sizeof(int), hipMemcpyHostToDevice, st));
+                HIP_TRY(hipStreamSynchronize(st));
+                const int j = base->pending;
+                k_eig_z<<<dim3((base->ld + kBlock - 1) / kBlock, 1), kBlock, 0, st>>>(base->view(), base->sig, j, bc, base->Zb + (size_t)j * (size_t)base->ld, base->cb + j);
+                base->pending = j + 1;
+                if (base->pending == base->fold) { base->fold_into(base->sig, base->pending); base->pending = 0; }
+            }
             HIP_TRY(hipGetLastError());
             sel[(size_t)best] = 1;
             add_edge(hci[(size_t)best], hcj[(size_t)best], hcw[(size_t)best]);

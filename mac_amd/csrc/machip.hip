@@ -24,6 +24,7 @@
 #include "esp_exchange_edge.h"
 #include "eig.h"
 #include "eig_exchange.h"
+#include "eig_free.h"
 
 namespace machip {
 thread_local std::string g_err;
@@ -2225,15 +2226,28 @@ int machip_eig_create(int device, int64_t n, int64_t n_fixed, const int32_t* fi,
                       int64_t m, const int32_t* ci, const int32_t* cj, const double* cw, int fold, int batch, int flags, machip_eig** out) {
     if (!out) return fail(MACHIP_BAD_ARG, "out is NULL");
     *out = nullptr;
+    const int fold_given = fold;
     if (fold == 0) fold = kEigDefaultFold;
     if (batch == 0) batch = kEigDefaultBatch;
     if (batch < 1 || batch > kEigMaxBatch) return fail(MACHIP_BAD_ARG, "batch must be in [1, 4096]");
-    if (flags & MACHIP_ESP_MATRIX_FREE)
+    const bool efree = (flags & MACHIP_EIG_MATRIX_FREE) != 0;
+    if ((flags & MACHIP_ESP_MATRIX_FREE) && !efree)
         return fail(MACHIP_BAD_ARG, "GreedyEig solves against the dense inverse: MACHIP_ESP_MATRIX_FREE is not available here");
     if (flags & MACHIP_ESP_SPANNING_TREE)
         return fail(MACHIP_BAD_ARG, "GreedyEig solves against the dense inverse: MACHIP_ESP_SPANNING_TREE is not available here");
+    if (efree) {      // the route without Sigma (eig_free.h): every refusal here and in machip_esp_create is decided before a device is touched
+        if (!(flags & MACHIP_ESP_MATRIX_FREE))
+            return fail(MACHIP_BAD_ARG, "MACHIP_EIG_MATRIX_FREE puts GreedyEig on the chain-free handle: it is valid only as MACHIP_ESP_MATRIX_FREE | MACHIP_EIG_MATRIX_FREE");
+        if (flags & MACHIP_ESP_DENSE_INVERSE)
+            return fail(MACHIP_BAD_ARG, "MACHIP_EIG_MATRIX_FREE keeps no Sigma: it cannot be combined with MACHIP_ESP_DENSE_INVERSE");
+        if (flags & ~(MACHIP_ESP_MATRIX_FREE | MACHIP_EIG_MATRIX_FREE))
+            return fail(MACHIP_BAD_ARG, "unknown flags: MACHIP_EIG_MATRIX_FREE is valid only as MACHIP_ESP_MATRIX_FREE | MACHIP_EIG_MATRIX_FREE");
+        if (fold_given != 0)      // (an argument that would be ignored is refused, not dropped)
+            return fail(MACHIP_BAD_ARG, "MACHIP_EIG_MATRIX_FREE never folds: fold has no meaning on this route and must be 0");
+        fold = 0;
+    }
     machip_esp* base = nullptr;
-    ST_TRY(machip_esp_create(device, n, n_fixed, fi, fj, fw, m, ci, cj, cw, fold, flags, &base));
+    ST_TRY(machip_esp_create(device, n, n_fixed, fi, fj, fw, m, ci, cj, cw, fold, flags & ~MACHIP_EIG_MATRIX_FREE, &base));
     if (base->beta != 0.0) {
         machip_esp_destroy(base);
         return fail(MACHIP_DISCONNECTED, "GreedyEig needs a connected fixed graph (lambda_2 of the fixed graph is 0 otherwise)");
@@ -2251,10 +2265,11 @@ int machip_eig_create(int device, int64_t n, int64_t n_fixed, const int32_t* fi,
     h->hci.assign(ci, ci + m); h->hcj.assign(cj, cj + m); h->hcw.assign(cw, cw + m);
     h->sel.assign((size_t)m, 0);
     auto body = [&]() -> int {
+        if (efree) ST_TRY(eig_free_init(h));      // (its memory check comes before the batch arrays are allocated)
         ST_TRY(h->alloc());
         h->adj = h->adj0; h->hdeg = h->hdeg0;
         ST_TRY(h->upload_graph());
-        HIP_TRY(hipMemcpyAsync(base->sig, base->sig0, sizeof(double) * (size_t)base->ld * (size_t)base->ld, hipMemcpyDeviceToDevice, base->stream));
+        if (!efree) HIP_TRY(hipMemcpyAsync(base->sig, base->sig0, sizeof(double) * (size_t)base->ld * (size_t)base->ld, hipMemcpyDeviceToDevice, base->stream));
         base->pending = 0;
         ST_TRY(h->first_pair());
         return h->reset();
@@ -2270,6 +2285,7 @@ void machip_eig_destroy(machip_eig* h) {
     (void)hipSetDevice(h->base->device);
     if (h->base->stream) (void)hipStreamSynchronize(h->base->stream);
     eig_xch_release(h->xc);
+    eig_free_release(h->fr);
     h->release();
     machip_esp_destroy(h->base);
     delete h;
@@ -2285,6 +2301,8 @@ int machip_eig_select(machip_eig* h, int64_t k, int32_t* order_out, double* lamb
 int machip_eig_exchange(machip_eig* h, int64_t k, const int32_t* sel_in, int64_t max_swaps, double min_gain, int32_t* sel_out,
                         int32_t* out_idx, int32_t* in_idx, double* lambda2_out, int64_t* n_swaps, int32_t* converged, int32_t* counts, double* t_ms) {
     std::vector<int> rowe;
+    if (h && h->matrix_free())
+        return fail(MACHIP_BAD_ARG, "the exchange works on the dense inverse: it is not available on a MACHIP_EIG_MATRIX_FREE handle");
     ST_TRY(eig_xch_check(h, k, sel_in, max_swaps, min_gain, rowe));
     if (n_swaps) *n_swaps = 0;
     if (converged) *converged = 0;

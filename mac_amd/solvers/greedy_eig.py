@@ -12,6 +12,11 @@ per solver iteration.
 The fixed (odometry) graph must be connected: the reference factors L_odom with one diagonal entry pinned and no
 regularisation, which only means anything for a connected odometry graph; a disconnected one raises ``Disconnected`` here.
 Size limits as GreedyESP: 32 768 poses when the fixed edges are exactly the chain (i, i+1), 16 384 otherwise.
+
+``matrix_free=True`` (chain-fixed graphs only) keeps no inverse at all: the chain's inverse applied to a batch is two scans, the
+picks are a low-rank correction kept as a history of n x k doubles, and one solver iteration costs 4 n j B flop plus three passes
+over the batch instead of 2 n^2 B (mac_amd/csrc/eig_free.h).  No limit on the number of poses but memory; the
+picks obey the same rule and stop rule, decided by the sparse Laplacian.  ``exchange`` is not available on that route.
 """
 from __future__ import annotations
 
@@ -39,11 +44,17 @@ def selection_indices(selection, m):
 
 class GreedyEig:
     def __init__(self, odom_measurements: List[Edge], lc_measurements: List[Edge], num_poses: int, *, device: int = 0,
-                 batch: int = 512, fold: int = 16, dense_inverse: bool = False):
+                 batch: int = 512, fold: Optional[int] = None, dense_inverse: bool = False, matrix_free: bool = False):
         """Arguments as mac/solvers/greedy_eig.py of the reference, plus keyword-only ``device`` (GPU ordinal), ``batch``
         (candidates solved together, 1..4096), ``fold`` (picks kept as a low-rank block before they are folded into the
-        inverse, 1..256) and ``dense_inverse`` (build the inverse by dense Gauss-Jordan even for a chain: cross-checks).
+        inverse, 1..256; None: 16), ``dense_inverse`` (build the inverse by dense Gauss-Jordan even for a chain: cross-checks) and
+        ``matrix_free`` (no inverse: the fixed edges must be exactly the chain (i, i+1); nothing is folded, so ``fold`` must be
+        left at None -- any value is a ValueError: an argument without a meaning is refused, not ignored -- as is ``dense_inverse``).
         Raises Disconnected when the fixed graph is not connected."""
+        if matrix_free and fold is not None:
+            raise ValueError(f"matrix_free=True never folds: fold has no meaning on this route (got fold={fold!r}); leave it at None")
+        if matrix_free and dense_inverse:
+            raise ValueError("matrix_free=True keeps no inverse: it cannot be combined with dense_inverse=True")
         self.L_odom = weight_graph_lap_from_edge_list(odom_measurements, num_poses)
         self.num_poses = num_poses
         self.odom_measurements = odom_measurements
@@ -52,7 +63,8 @@ class GreedyEig:
         self.weights = cw
         self.edge_list = np.stack([ci, cj], axis=1).astype(np.int64).reshape(-1, 2)
         fi, fj, fw = edges_to_arrays(odom_measurements)
-        self._dev = _lib.Eig(num_poses, fi, fj, fw, ci, cj, cw, fold=fold, batch=batch, dense_inverse=dense_inverse, device=device)
+        self._dev = _lib.Eig(num_poses, fi, fj, fw, ci, cj, cw, fold=fold, batch=batch, dense_inverse=dense_inverse, device=device,
+                             matrix_free=bool(matrix_free))
         self.last_lambda2: Optional[np.ndarray] = None      # lambda_2 after every pick of the last run
         self.last_times: Optional[np.ndarray] = None        # seconds from the start of the last run until each pick
 
@@ -122,6 +134,6 @@ class GreedyEig:
         return self._dev.candidate_bounds()
 
     def info(self) -> dict:
-        """form ("chain" / "dense"), ld, fold, batch, pending, beta, lambda2 (current), and per pick of the last run:
+        """form ("chain" / "dense" / "chain_free"), ld, fold, batch, pending, beta, lambda2 (current), and per pick of the last run:
         ``solved`` (candidates solved exactly) and ``applications`` (operator applications summed over the columns)."""
         return self._dev.info()
