@@ -291,7 +291,7 @@ inline void eig_free_release(EigFree* F) {
     delete F;
 }
 
-// The history (esp_free_reserve: Zb, cb) and the projection buffers for K picks.  Grows, never shrinks; a K that does not fit is
+// The history (esp_history_reserve: Zb, cb) and the projection buffers for K picks.  Grows, never shrinks; a K that does not fit is
 // refused before anything is freed or allocated.
 inline int eig_free_reserve(machip_eig* h, int64_t K) {
     EigFree* F = h->fr;
@@ -310,7 +310,7 @@ inline int eig_free_reserve(machip_eig* h, int64_t K) {
                                             " bytes (ld = " + std::to_string(base->ld) + ") and " + std::to_string((unsigned long long)proj) +
                                             " bytes of projections, " + std::to_string((unsigned long long)fr) + " bytes are free");
     }
-    ST_TRY(esp_free_reserve(base, K));
+    ST_TRY(esp_history_reserve(base, 0, false, K));
     if (K64 <= F->k64) return MACHIP_OK;
     HIP_TRY(hipStreamSynchronize(base->stream));
     if (F->Y) (void)hipFree(F->Y);

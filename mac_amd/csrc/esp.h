@@ -18,10 +18,17 @@
 //     launches, ping-pong between the handle's two ld x ld buffers -- the second one is the working copy afterwards).
 // beta (mac/solvers/greedy_esp.py of the reference: Cholesky with beta = 0, else beta = 1e-4 unless a reduced row is all zero)
 // is decided on the host by a union-find over F: connected -> 0; some node other than 0 without a fixed edge -> error; else 1e-4.
+// Host side, after the handle: the greedy loop of every route (esp_select_run) and machip_esp_create's pieces.
 #pragma once
+#include <algorithm>
 #include <climits>
+#include <cmath>
+#include <numeric>
+#include <string>
+#include <utility>
 #include <vector>
 
+#include "plan.h"
 #include "woodbury.h"
 
 namespace machip {
@@ -29,6 +36,7 @@ namespace machip {
 constexpr int kEspChainMaxN = 32768;   // chain form: 2 x 8.6 GB of Sigma at the limit
 constexpr int kEspDenseMaxN = 16384;   // general form: 512 Gauss-Jordan launches over 2 x 2.1 GB (k_gj_step indexes with int: ld^2 < 2^31)
 constexpr int kEspFormFree = 2;        // machip_esp::form of MACHIP_ESP_MATRIX_FREE: no Sigma at all, no n limit (esp_free.h)
+constexpr int kEspFormTree = 3;        // machip_esp::form of MACHIP_ESP_MATRIX_FREE | MACHIP_ESP_SPANNING_TREE (esp_tree.h)
 constexpr int kEspMaxFold = 256;
 constexpr int kEspDefaultFold = 64;
 constexpr int kEspGrid = 256;          // workgroups of the score / update pass (= partials of the argmax)
@@ -272,6 +280,22 @@ struct machip_esp {
         return V;
     }
     int grid_m() const { return std::max(1, std::min(machip::kEspGrid, (m + machip::kBlock - 1) / machip::kBlock)); }
+    bool matrix_free() const { return form == machip::kEspFormFree || form == machip::kEspFormTree; }
+
+    // at least n events in ev (ev[0], ev[1 + b]: a run's start and its budgets; the exchange's clock takes those from ev[2] on)
+    int events(size_t n) {
+        while (ev.size() < n) {
+            hipEvent_t e;
+            HIP_TRY(hipEventCreate(&e));
+            ev.push_back(e);
+        }
+        return MACHIP_OK;
+    }
+    // the working copy back to Sigma0
+    int load_sigma0() {
+        HIP_TRY(hipMemcpyAsync(sig, sig0, sizeof(double) * (size_t)ld * (size_t)ld, hipMemcpyDeviceToDevice, stream));
+        return MACHIP_OK;
+    }
 
     // A^-1 of the ld x ld matrix in `src`: ld / 32 blocked Gauss-Jordan steps on the matrix cores, ping-pong between src and dst,
     // look-ahead pivot blocks from 1 024 rows on -- exactly as solver.h inverts the capacitance matrix (woodbury.h).  The result
@@ -302,3 +326,246 @@ struct machip_esp {
         machip::k_esp_fold<<<dim3(tiles, tiles), 256, 0, stream>>>(S, Zb, cb, ld, j);
     }
 };
+
+namespace machip {
+
+// a host callable of the launch-bound loops (a route's step, a space's hook): always expanded in the loop that calls it
+#define ESP_INLINE __attribute__((always_inline)) inline
+
+// workgroups of a kernel with one thread per row of an ld-row matrix or vector
+inline int esp_rows_grid(int ld) { return (ld + kBlock - 1) / kBlock; }
+
+// ---- the greedy loop of every route (esp_select.h supplies the routes) ----
+// One selection run (the caller has checked the budgets: m >= K >= 1).  start(V, P): the scores and the argmax partials of the
+// fixed graph; zstep(V, k): the z of pick k into the column it returns.  A handle that keeps Sigma restarts it from Sigma0 and
+// folds a full Zb into it; one that does not (fold = 0) keeps every pick pending.  Per pick: the route's z, k_esp_update and
+// k_esp_argmax unless it is the last, the budgets' events; then the results and the budgets' times to the host.
+template <class Start, class ZStep>
+inline int esp_select_run(machip_esp* h, int nb, const int64_t* ks, Start start, ZStep zstep, int32_t* order_out, double* gain_out,
+                          double* t_ms_out) {
+    const int K = (int)ks[nb - 1], B = h->fold, P = h->grid_m();
+    ST_TRY(h->events((size_t)nb + 1));
+    const EspView V = h->view();
+    hipStream_t st = h->stream;
+    h->live = false;
+    HIP_TRY(hipEventRecord(h->ev[0], st));
+    if (h->sig0) ST_TRY(h->load_sigma0());
+    HIP_TRY(hipMemsetAsync(h->sel, 0, sizeof(int) * (size_t)h->m, st));
+    HIP_TRY(hipMemsetAsync(h->bad, 0, sizeof(int), st));
+    start(V, P);
+    k_esp_argmax<<<1, kBlock, 0, st>>>(V, P);
+    for (int k = 0, b = 0; k < K; ++k) {
+        const int j = zstep(V, k);
+        if (k + 1 < K) {
+            k_esp_update<<<P, kBlock, 0, st>>>(V, j);
+            k_esp_argmax<<<1, kBlock, 0, st>>>(V, P);
+        }
+        if (j == B - 1) h->fold_into(h->sig, B);
+        while (b < nb && ks[b] == k + 1) HIP_TRY(hipEventRecord(h->ev[1 + b++], st));
+    }
+    HIP_TRY(hipGetLastError());
+    h->pending = B ? K % B : K;
+    int hbad = 0;
+    if (order_out) HIP_TRY(hipMemcpyAsync(order_out, h->order, sizeof(int) * (size_t)K, hipMemcpyDeviceToHost, st));
+    if (gain_out) HIP_TRY(hipMemcpyAsync(gain_out, h->gain, sizeof(double) * (size_t)K, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&hbad, h->bad, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (t_ms_out)
+        for (int i = 0; i < nb; ++i) {
+            float ms = 0.0f;
+            HIP_TRY(hipEventElapsedTime(&ms, h->ev[0], h->ev[1 + i]));
+            t_ms_out[i] = ms;
+        }
+    h->live = true;
+    if (hbad) return fail(MACHIP_NOT_CONVERGED, "no finite score among the unselected candidates");
+    return MACHIP_OK;
+}
+
+// ---- machip_esp_create in pieces ----
+
+// The refusals decided from the arguments alone, in the order the tests know.  fold: 0 becomes the default.
+inline int esp_create_check(int64_t n, int64_t n_fixed, const int32_t* fi, const int32_t* fj, const double* fw, int64_t m, const int32_t* ci,
+                            const int32_t* cj, const double* cw, int& fold, int flags) {
+    if (n < 2) return fail(MACHIP_BAD_ARG, "num_nodes must be at least 2");
+    if (n_fixed < 0 || m < 0 || m > 2000000000ll) return fail(MACHIP_BAD_ARG, "bad edge counts");
+    if ((n_fixed && (!fi || !fj || !fw)) || (m && (!ci || !cj || !cw))) return fail(MACHIP_BAD_ARG, "NULL edge array");
+    const int fold_given = fold;
+    if (fold == 0) fold = kEspDefaultFold;
+    if (fold < 1 || fold > kEspMaxFold) return fail(MACHIP_BAD_ARG, "fold must be in [1, 256]");
+    if (flags & ~(MACHIP_ESP_DENSE_INVERSE | MACHIP_ESP_MATRIX_FREE | MACHIP_ESP_SPANNING_TREE | MACHIP_ESP_EDGE_RELAX | MACHIP_ESP_EDGE_RELAX_TREE))
+        return fail(MACHIP_BAD_ARG, "unknown flags");
+    const bool mfree = (flags & MACHIP_ESP_MATRIX_FREE) != 0, tree = (flags & MACHIP_ESP_SPANNING_TREE) != 0;
+    const bool edge = (flags & MACHIP_ESP_EDGE_RELAX) != 0, etree = (flags & MACHIP_ESP_EDGE_RELAX_TREE) != 0;
+    if (etree && edge)
+        return fail(MACHIP_BAD_ARG, "MACHIP_ESP_EDGE_RELAX_TREE builds the Gram matrix from the spanning tree, MACHIP_ESP_EDGE_RELAX from the chain: the two cannot be combined");
+    if (etree && (flags & MACHIP_ESP_DENSE_INVERSE))
+        return fail(MACHIP_BAD_ARG, "MACHIP_ESP_EDGE_RELAX_TREE takes Sigma0 from the spanning tree's closed form: it cannot be combined with MACHIP_ESP_DENSE_INVERSE");
+    if (etree && !(mfree && tree))      // (without its partners the bit was an unknown flag before the route existed, and stays one)
+        return fail(MACHIP_BAD_ARG, "unknown flags: MACHIP_ESP_EDGE_RELAX_TREE puts the relaxation on the spanning-tree handle and is valid only together with MACHIP_ESP_MATRIX_FREE | MACHIP_ESP_SPANNING_TREE");
+    if (edge && !mfree)      // (alone the bit was an unknown flag before the route existed, and stays one: the message keeps saying so)
+        return fail(MACHIP_BAD_ARG, "unknown flags: MACHIP_ESP_EDGE_RELAX puts the relaxation on the chain-free handle and is valid only together with MACHIP_ESP_MATRIX_FREE");
+    if (edge && (flags & MACHIP_ESP_DENSE_INVERSE))
+        return fail(MACHIP_BAD_ARG, "MACHIP_ESP_EDGE_RELAX takes Sigma0 from the chain's closed form: it cannot be combined with MACHIP_ESP_DENSE_INVERSE");
+    if (edge && tree)
+        return fail(MACHIP_BAD_ARG, "MACHIP_ESP_EDGE_RELAX has the chain's closed form only: it cannot be combined with MACHIP_ESP_SPANNING_TREE");
+    if (tree && !mfree)
+        return fail(MACHIP_BAD_ARG, "MACHIP_ESP_SPANNING_TREE selects the spanning tree of the matrix-free route: it is valid only together with MACHIP_ESP_MATRIX_FREE");
+    if (mfree && fold_given != 0)      // (an argument that would be ignored is refused, not dropped: nothing is ever folded here)
+        return fail(MACHIP_BAD_ARG, "MACHIP_ESP_MATRIX_FREE never folds: fold has no meaning on this route and must be 0");
+    if (mfree && (flags & MACHIP_ESP_DENSE_INVERSE))
+        return fail(MACHIP_BAD_ARG, "MACHIP_ESP_MATRIX_FREE keeps no Sigma: it cannot be combined with MACHIP_ESP_DENSE_INVERSE");
+    if (mfree && n > (int64_t)INT_MAX - kGjT) return fail(MACHIP_BAD_ARG, "node ids are int32: num_nodes is too large");
+    if (!mfree && n > kEspChainMaxN) return fail(MACHIP_BAD_ARG, "GreedyESP keeps (L_red + beta I)^-1 dense: num_nodes must be <= 32768 (chain-fixed graphs), <= 16384 otherwise");
+    for (int64_t e = 0; e < n_fixed; ++e)
+        if (fi[e] < 0 || fi[e] >= n || fj[e] < 0 || fj[e] >= n || !std::isfinite(fw[e])) return fail(MACHIP_BAD_ARG, "fixed edge out of range or weight not finite");
+    for (int64_t e = 0; e < m; ++e)
+        if (ci[e] < 0 || ci[e] >= n || cj[e] < 0 || cj[e] >= n || !std::isfinite(cw[e])) return fail(MACHIP_BAD_ARG, "candidate edge out of range or weight not finite");
+    return MACHIP_OK;
+}
+
+// What the fixed graph is: beta, and the chain's links when F is exactly the path (i, i+1).
+struct EspFixedClass {
+    double beta = 0.0;
+    bool chain = false;
+    std::vector<double> link;      // chain: the summed weight of link (i, i+1)
+};
+
+// beta (the reference: Cholesky with beta = 0; on failure raise if a reduced row is all zero, else beta = 1e-4), decided by a
+// union-find over F; the chain form; and what the flags ask of the graph and it is not.
+inline int esp_classify_fixed(int64_t n, int64_t n_fixed, const int32_t* fi, const int32_t* fj, const double* fw, int flags, EspFixedClass& C) {
+    const bool mfree = (flags & MACHIP_ESP_MATRIX_FREE) != 0, tree = (flags & MACHIP_ESP_SPANNING_TREE) != 0;
+    const int N = (int)n, np = N - 1;
+    std::vector<int> par(N), has(N, 0);
+    std::iota(par.begin(), par.end(), 0);
+    auto root = [&](int a) { while (par[a] != a) { par[a] = par[par[a]]; a = par[a]; } return a; };
+    int comps = N;
+    for (int64_t e = 0; e < n_fixed; ++e) {
+        if (fi[e] == fj[e] || fw[e] == 0.0) continue;
+        has[fi[e]] = has[fj[e]] = 1;
+        const int a = root(fi[e]), b = root(fj[e]);
+        if (a != b) { par[a] = b; --comps; }
+    }
+    if (tree && comps > 1)
+        return fail(MACHIP_BAD_ARG, "the spanning-tree route needs a connected fixed graph: the fixed edges leave " + std::to_string(comps) + " components");
+    if (comps > 1) {
+        for (int i = 1; i < N; ++i)
+            if (!has[i]) return fail(MACHIP_DISCONNECTED, "node " + std::to_string(i) + " has no fixed edge: row " + std::to_string(i - 1) + " of L_fixed is all zeros");
+        C.beta = 1e-4;
+    }
+    // chain form: F is exactly the path (i, i+1), parallel links summed
+    C.link.assign((size_t)np, 0.0);
+    C.chain = !(flags & MACHIP_ESP_DENSE_INVERSE) && comps == 1 && !tree;
+    for (int64_t e = 0; C.chain && e < n_fixed; ++e) {
+        const int a = std::min(fi[e], fj[e]), b = std::max(fi[e], fj[e]);
+        if (b != a + 1) C.chain = false;
+        else C.link[(size_t)a] += fw[e];
+    }
+    for (int i = 0; C.chain && i < np; ++i) if (!(C.link[(size_t)i] > 0.0)) C.chain = false;
+    if (mfree && !tree && !C.chain)
+        return fail(MACHIP_BAD_ARG, std::string("the matrix-free route needs a chain: the fixed edges must be exactly the connected path (i, i+1), i = 0..n-2 (parallel links summed)") +
+                                        ((flags & MACHIP_ESP_EDGE_RELAX) ? "; MACHIP_ESP_EDGE_RELAX builds the candidates' Gram matrix from that chain's resistances" : ""));
+    if (!C.chain && !tree && n > kEspDenseMaxN)
+        return fail(MACHIP_BAD_ARG, "GreedyESP inverts L_red + beta I densely when the fixed edges are not exactly the chain (i, i+1): num_nodes must be <= 16384");
+    return MACHIP_OK;
+}
+
+// The stream and every array of a fresh handle (n, m, ld, fold, form and the host edge lists are set); the candidates go up.
+inline int esp_alloc(machip_esp* h) {
+    HIP_TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+    const bool mfree = h->matrix_free();
+    const int64_t m = h->m;
+    const size_t ld = (size_t)h->ld, ms = (size_t)std::max<int64_t>(m, 1), fold = (size_t)h->fold;
+    if (!mfree) { ST_TRY(dev_alloc(&h->bufA, ld * ld)); ST_TRY(dev_alloc(&h->bufB, ld * ld)); }
+    ST_TRY(dev_alloc(&h->cu, ms)); ST_TRY(dev_alloc(&h->cv, ms)); ST_TRY(dev_alloc(&h->cw, ms)); ST_TRY(dev_alloc(&h->s, ms));
+    ST_TRY(dev_alloc(&h->sel, ms)); ST_TRY(dev_alloc(&h->order, ms)); ST_TRY(dev_alloc(&h->gain, ms));
+    if (!mfree) { ST_TRY(dev_alloc(&h->Zb, ld * fold)); ST_TRY(dev_alloc(&h->cb, fold)); }      // (matrix-free: the select sizes the history)
+    ST_TRY(dev_alloc(&h->pv, (size_t)kEspGrid)); ST_TRY(dev_alloc(&h->pi, (size_t)kEspGrid)); ST_TRY(dev_alloc(&h->best, 1));
+    ST_TRY(dev_alloc(&h->bad, 1)); ST_TRY(dev_alloc(&h->piv, (size_t)2 * kGjB * kGjB));
+    if (!mfree) {
+        HIP_TRY(hipMemsetAsync(h->Zb, 0, sizeof(double) * ld * fold, h->stream));
+        HIP_TRY(hipMemsetAsync(h->cb, 0, sizeof(double) * fold, h->stream));
+    }
+    HIP_TRY(hipMemsetAsync(h->bad, 0, sizeof(int), h->stream));
+    if (m) {
+        std::vector<int> u((size_t)m), v((size_t)m);
+        for (int64_t e = 0; e < m; ++e) { u[(size_t)e] = h->hci[(size_t)e] - 1; v[(size_t)e] = h->hcj[(size_t)e] - 1; }
+        HIP_TRY(hipMemcpyAsync(h->cu, u.data(), sizeof(int) * (size_t)m, hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(hipMemcpyAsync(h->cv, v.data(), sizeof(int) * (size_t)m, hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(hipMemcpyAsync(h->cw, h->hcw.data(), sizeof(double) * (size_t)m, hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(hipStreamSynchronize(h->stream));     // (host staging goes out of scope)
+    }
+    return MACHIP_OK;
+}
+
+// Sigma0, chain form: R = the prefix sums of 1 / w_link.  A matrix-free handle keeps R and nothing else; a dense one fills bufA from it.
+inline int esp_sigma0_chain(machip_esp* h, const std::vector<double>& link) {
+    const int np = h->np;
+    std::vector<double> R((size_t)np);
+    double acc = 0.0;
+    for (int i = 0; i < np; ++i) { acc += 1.0 / link[(size_t)i]; R[(size_t)i] = acc; }
+    double* dR = nullptr;
+    ST_TRY(dev_alloc(&dR, (size_t)np));
+    HIP_TRY(hipMemcpyAsync(dR, R.data(), sizeof(double) * (size_t)np, hipMemcpyHostToDevice, h->stream));
+    if (h->matrix_free()) {                           // R is all of Sigma0 this route keeps
+        h->R = dR;
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        return MACHIP_OK;
+    }
+    k_esp_chain_fill<<<dim3((unsigned)esp_rows_grid(h->ld), (unsigned)h->ld), kBlock, 0, h->stream>>>(h->bufA, dR, np, h->ld);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    (void)hipFree(dR);
+    h->sig0 = h->bufA; h->sig = h->bufB;
+    return MACHIP_OK;
+}
+
+// Sigma0, general form: dense L_red + beta I (identity beyond n'), entries summed on the host in edge order, then inverted by
+// the blocked Gauss-Jordan elimination (gj_inverse).
+inline int esp_sigma0_dense(machip_esp* h) {
+    const int np = h->np;
+    const size_t ld = (size_t)h->ld;
+    std::vector<double> diag((size_t)np, h->beta);
+    std::vector<std::pair<int64_t, double>> off;
+    off.reserve(h->hfw.size());
+    for (size_t e = 0; e < h->hfw.size(); ++e) {
+        const int a = h->hfi[e] - 1, b = h->hfj[e] - 1;
+        const double w = h->hfw[e];
+        if (a == b) continue;
+        if (a >= 0) diag[(size_t)a] += w;
+        if (b >= 0) diag[(size_t)b] += w;
+        if (a >= 0 && b >= 0) off.emplace_back((int64_t)std::min(a, b) * (int64_t)ld + std::max(a, b), w);
+    }
+    std::stable_sort(off.begin(), off.end(), [](const std::pair<int64_t, double>& x, const std::pair<int64_t, double>& y) { return x.first < y.first; });
+    std::vector<int64_t> pos;
+    std::vector<double> val;
+    for (int i = 0; i < (int)ld; ++i) { pos.push_back((int64_t)i * (int64_t)ld + i); val.push_back(i < np ? diag[(size_t)i] : 1.0); }
+    for (size_t q = 0; q < off.size();) {
+        size_t r = q;
+        double w = 0.0;
+        for (; r < off.size() && off[r].first == off[q].first; ++r) w += off[r].second;
+        const int64_t a = off[q].first / (int64_t)ld, b = off[q].first % (int64_t)ld;
+        pos.push_back(a * (int64_t)ld + b); val.push_back(-w);
+        pos.push_back(b * (int64_t)ld + a); val.push_back(-w);
+        q = r;
+    }
+    int64_t* dpos = nullptr;
+    double* dval = nullptr;
+    ST_TRY(dev_alloc(&dpos, pos.size())); ST_TRY(dev_alloc(&dval, val.size()));
+    HIP_TRY(hipMemsetAsync(h->bufA, 0, sizeof(double) * ld * ld, h->stream));
+    HIP_TRY(hipMemcpyAsync(dpos, pos.data(), sizeof(int64_t) * pos.size(), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(dval, val.data(), sizeof(double) * val.size(), hipMemcpyHostToDevice, h->stream));
+    const int cnt = (int)pos.size();
+    k_esp_scatter<<<std::max(1, std::min(kMaxGrid, (cnt + kBlock - 1) / kBlock)), kBlock, 0, h->stream>>>(h->bufA, dpos, dval, cnt);
+    double *src = h->bufA, *dst = h->bufB;
+    h->gj_inverse<false>(src, dst);
+    HIP_TRY(hipGetLastError());
+    int hbad = 0;
+    HIP_TRY(hipMemcpyAsync(&hbad, h->bad, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    (void)hipFree(dpos); (void)hipFree(dval);
+    if (hbad) return fail(MACHIP_NOT_CONVERGED, "L_red + beta I is not positive definite numerically (a non-positive Gauss-Jordan pivot)");
+    h->sig0 = src; h->sig = dst;
+    return MACHIP_OK;
+}
+
+}  // namespace machip

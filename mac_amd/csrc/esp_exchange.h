@@ -17,6 +17,7 @@
 // removal is a pick of weight -w_e, c = -w_e / (1 - s_e); the insertion c = w_f / (1 + s_f'), s_f' the score after the removal.
 // Each appends its z to Zb, k_esp_update rescales all m scores, and Zb is folded into Sigma when it is full, as in machip_esp_select.
 // Per round the host reads one 24-byte record (the winner: it decides termination and names the edges of the two steps).
+// The load and the round loop are esp_xch_run, here for the dense handle (EspXchDense) and for esp_exchange_edge.h's space.
 #pragma once
 #include <cmath>
 #include <string>
@@ -272,6 +273,170 @@ inline int esp_xch_prepare(EspXch*& x, size_t K, size_t parts, size_t swaps, siz
     if (!x->scale) ST_TRY(dev_alloc(&x->scale, 1));
     if (!x->best) ST_TRY(dev_alloc(&x->best, 1));
     return MACHIP_OK;
+}
+
+// Device time per phase of the exchange (option esp_xch_profile): events between the phases, read after the round's own
+// synchronisation.  Interval q lies between marks q - 1 and q and belongs to the phase mark q names (-1: nobody's -- the host waited).
+enum { kXchLoad = 1, kXchPairs = 2, kXchTrows = 3, kXchSteps = 4, kXchFolds = 5 };
+struct XchClock {
+    machip_esp* h;
+    bool on;
+    size_t base, used = 0;
+    std::vector<int> tag;
+    double acc[6] = {0, 0, 0, 0, 0, 0};
+    int mark(int phase) {
+        if (!on) return MACHIP_OK;
+        ST_TRY(h->events(base + used + 1));
+        HIP_TRY(hipEventRecord(h->ev[base + used], h->stream));
+        tag.push_back(phase);
+        ++used;
+        return MACHIP_OK;
+    }
+    int collect() {      // (the stream is idle)
+        for (size_t q = 1; q < used; ++q) {
+            if (tag[q] < 0) continue;
+            float ms = 0.0f;
+            HIP_TRY(hipEventElapsedTime(&ms, h->ev[base + q - 1], h->ev[base + q]));
+            acc[tag[q]] += ms;
+        }
+        used = 0;
+        tag.clear();
+        return MACHIP_OK;
+    }
+};
+
+// What esp_xch_run works on: the dense handle's Sigma (EspXchDense) or the relaxation's R (esp_exchange_edge.h).  Next to these
+// fields a space has load(&S): the matrix at its start; pairs(): the round's pair pass; entered(e, j): after an insertion's
+// update; finish(j): the handle's own bookkeeping.
+struct EspXchSpace {
+    EspView V;                    // the candidates (and seeds) as the kernels see them
+    EspXch* X = nullptr;
+    int K = 0, P = 0, fold = 0;   // rows of T, workgroups of a score pass, columns of V.Zb
+    int chunks = 0, per = 0;      // the pair pass: slices of the candidates per row and their length
+    int sel_count = 0;            // entries of V.sel to clear
+    int seeds = 0;                // columns m .. m + seeds: forced picks ahead of the K given ones
+};
+
+// The exchange from the selection `rowe` (ascending): the load -- the matrix, the scores, the seeds and the K given edges as
+// forced picks, then T -- and the rounds.  Per round the pair pass, the 24-byte read-back, and the two steps of the winning swap.
+template <class Space>
+inline int esp_xch_run(machip_esp* h, Space& sp, std::vector<int>& rowe, int64_t max_swaps, double min_gain, int32_t* sel_out, int32_t* out_idx,
+                       int32_t* in_idx, double* ratio, int64_t* n_swaps, int32_t* converged, double* t_ms) {
+    const EspView& V = sp.V; EspXch* X = sp.X;
+    const int K = sp.K, m = h->m, B = sp.fold, P = sp.P, ld = V.ld, zg = esp_rows_grid(ld), tiles = ld / kGjT;
+    ST_TRY(h->events(2));
+    XchClock clk{h, default_options().get(kOpt_esp_xch_profile, 0) != 0, 2};
+    hipStream_t st = h->stream;
+    std::vector<char> in_sel((size_t)m, 0);
+    for (int e : rowe) in_sel[(size_t)e] = 1;
+    double* S = nullptr;
+    int j = 0;      // columns of Zb pending
+    // one rank-1 update: the z of e into Zb[:, j], all scores, T's rows (with_rows), the fold when Zb is full
+    auto step = [&](int e, int mode, double* rt, bool with_rows, int xrow, int f_in) -> int {
+        k_esp_xch_step<<<zg, kBlock, 0, st>>>(V, S, j, e, mode, rt, X->scale);
+        k_esp_update<<<P, kBlock, 0, st>>>(V, j);
+        if (mode > 0) sp.entered(e, j);
+        if (with_rows) ST_TRY(clk.mark(kXchSteps));      // (the load is one interval, marked at its end)
+        if (with_rows) {
+            k_esp_xch_tupdate<<<dim3((unsigned)K, (unsigned)zg), kBlock, 0, st>>>(V, X->T, X->rowe, j, xrow, f_in, X->scale);
+            ST_TRY(clk.mark(kXchTrows));
+        }
+        if (++j == B) {
+            k_esp_fold<<<dim3(tiles, tiles), 256, 0, st>>>(S, V.Zb, V.cb, ld, B);
+            j = 0;
+            if (with_rows) ST_TRY(clk.mark(kXchFolds));
+        }
+        return MACHIP_OK;
+    };
+    HIP_TRY(hipEventRecord(h->ev[0], st));
+    ST_TRY(clk.mark(-1));
+    ST_TRY(sp.load(&S));
+    HIP_TRY(hipMemsetAsync(V.sel, 0, sizeof(int) * (size_t)sp.sel_count, st));
+    HIP_TRY(hipMemsetAsync(V.bad, 0, sizeof(int), st));
+    HIP_TRY(hipMemcpyAsync(X->rowe, rowe.data(), sizeof(int) * (size_t)K, hipMemcpyHostToDevice, st));
+    k_esp_scores<<<P, kBlock, 0, st>>>(V, S, 0);
+    for (int q = 0; q < sp.seeds; ++q) ST_TRY(step(m + q, 1, nullptr, false, -1, -1));
+    for (int q = 0; q < K; ++q) ST_TRY(step(rowe[(size_t)q], 1, nullptr, false, -1, -1));
+    if (max_swaps > 0) k_esp_xch_tbuild<<<dim3((unsigned)K, (unsigned)zg), kBlock, 0, st>>>(V, S, j, X->rowe, X->T);
+    HIP_TRY(hipGetLastError());
+    ST_TRY(clk.mark(kXchLoad));
+    int64_t t = 0;
+    int hbad = 0;
+    for (; t < max_swaps; ++t) {
+        sp.pairs();
+        k_esp_xch_argmax<<<1, kBlock, 0, st>>>(V, X->rowe, X->pv, X->pf, K * sp.chunks, sp.chunks, X->best);
+        HIP_TRY(hipGetLastError());
+        ST_TRY(clk.mark(kXchPairs));
+        EspXchBest b;
+        HIP_TRY(hipMemcpyAsync(&b, X->best, sizeof(b), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(&hbad, V.bad, sizeof(int), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        ST_TRY(clk.collect());
+        if (hbad) break;
+        if (b.val - 1.0 <= min_gain) { *converged = 1; break; }
+        ST_TRY(esp_xch_apply(rowe, in_sel, b.row, b.e, b.f));
+        out_idx[t] = b.e;
+        in_idx[t] = b.f;
+        ST_TRY(clk.mark(-1));
+        ST_TRY(step(b.e, -1, X->ratio + t, true, b.row, -1));
+        ST_TRY(step(b.f, +1, X->ratio + t, true, b.row, b.f));
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipEventRecord(h->ev[1], st));
+    if (t > 0) HIP_TRY(hipMemcpyAsync(ratio, X->ratio, sizeof(double) * (size_t)t, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&hbad, V.bad, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    ST_TRY(clk.collect());
+    sp.finish(j);
+    if (hbad)
+        return fail(MACHIP_NOT_CONVERGED, "exchange: 1 - s_e of a removal or 1 + s_f of an insertion is not positive, or no finite Delta (the selection holds a bridge of the graph, or lost numerically)");
+    *n_swaps = t;
+    for (int e = 0, q = 0; e < m; ++e) if (in_sel[(size_t)e]) sel_out[q++] = e;
+    if (t_ms) {
+        float ms = 0.0f;
+        HIP_TRY(hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
+        t_ms[0] = ms;
+        for (int q = 1; q < 6; ++q) t_ms[q] = clk.acc[q];
+    }
+    return MACHIP_OK;
+}
+
+// the dense handle's space: Sigma from Sigma0; a row of T in LDS while the runtime grants it, from global memory otherwise
+struct EspXchDense : EspXchSpace {
+    machip_esp* h;
+    size_t row_bytes;
+    bool lds;
+    ESP_INLINE int load(double** S) { h->live = false; h->pending = 0; *S = h->sig; return h->load_sigma0(); }      // (the handle's state: after the events exist)
+    ESP_INLINE void pairs() {
+        const dim3 grid((unsigned)K, (unsigned)chunks);
+        if (lds) {
+            k_esp_xch_pairs<true><<<grid, kBlock, row_bytes, h->stream>>>(V, X->T, X->rowe, per, X->pv, X->pf);
+            if (hipGetLastError() != hipSuccess) lds = false;      // (the launch was refused, nothing ran: global-memory rows from here on)
+        }
+        if (!lds) k_esp_xch_pairs<false><<<grid, kBlock, 0, h->stream>>>(V, X->T, X->rowe, per, X->pv, X->pf);
+    }
+    ESP_INLINE void entered(int, int) {}
+    ESP_INLINE void finish(int j) { h->pending = j; h->live = true; }
+};
+
+// machip_esp_exchange after its checks: T and the partials, the LDS decision, the space, the rounds
+inline int esp_exchange(machip_esp* h, int64_t k, std::vector<int>& rowe, int64_t max_swaps, double min_gain, int32_t* sel_out, int32_t* out_idx,
+                        int32_t* in_idx, double* ratio, int64_t* n_swaps, int32_t* converged, double* t_ms) {
+    EspXchDense sp;
+    sp.h = h; sp.K = (int)k; sp.P = h->grid_m(); sp.fold = h->fold; sp.sel_count = h->m;
+    sp.chunks = std::max(1, std::min((h->m + kBlock - 1) / kBlock, (kEspXchTargetGroups + sp.K - 1) / sp.K));
+    sp.per = (h->m + sp.chunks - 1) / sp.chunks;
+    const long lds_kb = std::max(0l, std::min<long>(default_options().get(kOpt_esp_xch_lds_kb, kEspXchLdsDefaultKb), kEspXchLdsMaxKb));
+    sp.row_bytes = sizeof(double) * (size_t)h->ld;
+    sp.lds = sp.row_bytes <= (size_t)lds_kb * 1024;
+    ST_TRY(esp_xch_prepare(h->xc, (size_t)sp.K, (size_t)sp.K * (size_t)sp.chunks, (size_t)std::max<int64_t>(max_swaps, 1), (size_t)h->ld));
+    if (sp.lds && sp.row_bytes > 48 * 1024 &&
+        hipFuncSetAttribute(reinterpret_cast<const void*>(&k_esp_xch_pairs<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sp.row_bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        sp.lds = false;      // (the runtime does not grant the row: the global-memory rows give the same bits)
+    }
+    sp.X = h->xc; sp.V = h->view();
+    return esp_xch_run(h, sp, rowe, max_swaps, min_gain, sel_out, out_idx, in_idx, ratio, n_swaps, converged, t_ms);
 }
 
 }  // namespace machip

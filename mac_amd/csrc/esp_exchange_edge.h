@@ -125,11 +125,6 @@ inline void esp_xe_release(EspXchEdge*& e) {
     e = nullptr;
 }
 
-// The leading dimension the relaxation of an edge handle inverts at, from the handle alone (machip_esp_relax_info's).
-inline int esp_xe_ld(const machip_esp* h) {
-    return h->edge_tree ? esp_edge_tree_ld((int64_t)h->m + h->tr->seeds) : (std::max(h->m, 1) + kGjT - 1) / kGjT * kGjT;
-}
-
 // The view's own arrays, once per handle (the relaxation's state exists: its ld is the view's).
 inline int esp_xe_prepare(machip_esp* h, EspXchEdge* e) {
     if (e->cu) return MACHIP_OK;
@@ -164,6 +159,36 @@ inline int esp_xe_load_gram(machip_esp* h, const EspXchEdge* e, double** Rm) {
         HIP_TRY(hipGetLastError());
     }
     return MACHIP_OK;
+}
+
+// the edge handles' space: R from G in the relaxation's N buffer, the seeds ahead of the selection, the entering column's closed form
+struct EspXchEdgeSpace : EspXchSpace {
+    machip_esp* h;
+    const EspXchEdge* E;
+    ESP_INLINE int load(double** S) { return esp_xe_load_gram(h, E, S); }
+    ESP_INLINE void pairs() { k_esp_xch_pairs_edge<<<dim3((unsigned)K, (unsigned)chunks), kBlock, 0, h->stream>>>(V, h->m, X->T, X->rowe, per, X->pv, X->pf); }
+    ESP_INLINE void entered(int e, int j) { k_esp_xe_entered<<<1, kBlock, 0, h->stream>>>(V, e, j, X->scale); }      // (s_e / (1 + s_e) without the cancellation)
+    ESP_INLINE void finish(int) {}
+};
+
+// machip_esp_exchange_edge after its checks: T (refused before G is built), the relaxation's state, the view, the space, the rounds
+inline int esp_exchange_edge(machip_esp* h, int64_t k, std::vector<int>& rowe, int64_t max_swaps, double min_gain, int32_t* sel_out,
+                             int32_t* out_idx, int32_t* in_idx, double* ratio, int64_t* n_swaps, int32_t* converged, double* t_ms) {
+    EspXchEdgeSpace sp; sp.h = h;
+    const int m = h->m, ld = esp_relax_ld(h);
+    sp.K = (int)k; sp.fold = kEspDefaultFold; sp.sel_count = ld;
+    sp.chunks = std::max(1, std::min((m + kBlock - 1) / kBlock, (kEspXchTargetGroups + sp.K - 1) / sp.K));
+    sp.per = ((m + sp.chunks - 1) / sp.chunks + 1) & ~1;      // (even: a chunk starts on a 16-byte boundary of its rows)
+    if (!h->xe) h->xe = new EspXchEdge();
+    EspXchEdge* E = h->xe;
+    ST_TRY(esp_xch_prepare(E->x, (size_t)sp.K, (size_t)sp.K * (size_t)sp.chunks, (size_t)std::max<int64_t>(max_swaps, 1), (size_t)ld));
+    ST_TRY(esp_relax_prepare(h));
+    if (const int stp = esp_xe_prepare(h, E)) {      // (nothing half-made stays on the handle)
+        esp_xe_release(h->xe);
+        return stp;
+    }
+    sp.E = E; sp.X = E->x; sp.V = E->view(); sp.P = E->grid(); sp.seeds = E->M - m;
+    return esp_xch_run(h, sp, rowe, max_swaps, min_gain, sel_out, out_idx, in_idx, ratio, n_swaps, converged, t_ms);
 }
 
 }  // namespace machip

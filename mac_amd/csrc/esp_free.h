@@ -16,6 +16,7 @@
 // arithmetic per entry is that of the dense chain form with fold > K.
 // Scores and updates: k_esp_free_scores is k_esp_scores with Sigma0's three entries read from R (the same three-term sum, the same
 // bits); k_esp_update and k_esp_argmax are reused as they are.  k_esp_free_resist rescores every candidate from R and the history.
+// Host side: esp_free_z (the sliced / unsliced launch) and esp_history_reserve, both shared with esp_tree.h; the loop is esp.h's.
 #pragma once
 #include <string>
 
@@ -165,63 +166,70 @@ inline int esp_free_slices(const machip_esp* h, int j) {
     return std::max(S, 1);
 }
 
-// The history for K picks: Zb (ld x K), cb (K) and the slices' partial sums.  Grows, never shrinks.  Refuses, before anything is
-// freed or allocated, a K whose history does not fit in the device's free memory (plus what the present history gives back).
-inline int esp_free_reserve(machip_esp* h, int64_t K) {
-    if ((size_t)K <= h->zcap) return MACHIP_OK;
+// The z of a pick through the history's first j columns into column j, recorded as pick k: k_esp_free_z, and k_esp_free_zsum
+// when the columns are sliced.  LOADED = false: src = the chain's R; true (esp_tree.h): src = the Sigma0 row difference itself.
+template <bool LOADED>
+ESP_INLINE void esp_free_z(machip_esp* h, const EspView& V, const double* src, int j, int k) {
+    const int zg = (h->ld + kEspFreeRows - 1) / kEspFreeRows;
+    const int S = esp_free_slices(h, j);
+    if (S == 1) {
+        k_esp_free_z<false, LOADED><<<zg, kBlock, 0, h->stream>>>(V, src, nullptr, j, k, 0);
+    } else {
+        const int per = ((j + S - 1) / S + kEspFreeUnroll - 1) / kEspFreeUnroll * kEspFreeUnroll;
+        k_esp_free_z<true, LOADED><<<dim3((unsigned)zg, (unsigned)S), kBlock, 0, h->stream>>>(V, src, h->part, j, k, per);
+        k_esp_free_zsum<<<zg, kBlock, 0, h->stream>>>(V, h->part, S, j, k);
+    }
+}
+
+// The history for `seeds` leading columns and K picks: Zb (ld x (seeds + K)), cb and the slices' partial sums.  Grows, never
+// shrinks.  Refuses, before anything is freed or allocated, what does not fit in the device's free memory (plus what the present
+// history gives back).  keep: columns [0, seeds) hold a tree handle's seeds (esp_tree.h) and are copied into the new history,
+// allocated beside the old one -- which then gives nothing back, and stays (with the seeds in it) if the new one cannot be made.
+// keep is apart from seeds because the columns count from the handle's creation but hold something only once the seeds have run.
+// The refusal's text names the seeds on a tree handle (h->tr), r = 0 included; cols > INT_MAX can be true only there (K <= m <= 2e9).
+inline int esp_history_reserve(machip_esp* h, int seeds, bool keep, int64_t K) {
+    const int64_t cols = (int64_t)seeds + K;
+    if ((size_t)cols <= h->zcap) return MACHIP_OK;
     const size_t ld = (size_t)h->ld;
-    const double need = 8.0 * (double)ld * (double)K;
+    const double need = 8.0 * (double)ld * (double)cols;
     size_t fr = 0, tot = 0;
     HIP_TRY(hipMemGetInfo(&fr, &tot));
     // headroom: the partial sums, the c's, and 256 MiB for what the runtime and the candidate arrays of other handles take
-    const double room = (double)fr + 8.0 * (double)ld * (double)h->zcap - 8.0 * (double)ld * kEspFreeMaxSplit - 8.0 * (double)K - 268435456.0;
-    if (need > room)
-        return fail(MACHIP_BAD_ARG, "the matrix-free history does not fit in device memory: n = " + std::to_string(h->n) + ", K = " +
-                                        std::to_string((long long)K) + " asks for 8 ld K = " + std::to_string((unsigned long long)need) +
-                                        " bytes (ld = " + std::to_string(h->ld) + "), " + std::to_string((unsigned long long)fr) +
-                                        " bytes are free");
+    const double room = (double)fr + (keep ? 0.0 : 8.0 * (double)ld * (double)h->zcap) - 8.0 * (double)ld * kEspFreeMaxSplit - 8.0 * (double)cols - 268435456.0;
+    if (need > room || cols > (int64_t)INT_MAX)
+        return fail(MACHIP_BAD_ARG, "the matrix-free history does not fit in device memory: n = " + std::to_string(h->n) + ", K = " + std::to_string((long long)K) +
+                                        (h->tr ? " and " + std::to_string(seeds) + " seeds ask for 8 ld (seeds + K) = " : " asks for 8 ld K = ") +
+                                        std::to_string((unsigned long long)need) + " bytes (ld = " + std::to_string(h->ld) + "), " +
+                                        std::to_string((unsigned long long)fr) + " bytes are free");
     HIP_TRY(hipStreamSynchronize(h->stream));
     h->live = false;
-    if (h->Zb) (void)hipFree(h->Zb);
-    if (h->cb) (void)hipFree(h->cb);
+    double *oldZ = h->Zb, *oldc = h->cb;
+    if (!keep) {
+        if (oldZ) (void)hipFree(oldZ);
+        if (oldc) (void)hipFree(oldc);
+        oldZ = oldc = nullptr;
+    }
     h->Zb = nullptr; h->cb = nullptr; h->zcap = 0;
     if (!h->part) ST_TRY(dev_alloc(&h->part, ld * (size_t)kEspFreeMaxSplit));
-    ST_TRY(dev_alloc(&h->Zb, ld * (size_t)K));
-    ST_TRY(dev_alloc(&h->cb, (size_t)K));
-    h->zcap = (size_t)K;
-    return MACHIP_OK;
-}
-
-// The picks of machip_esp_select on a matrix-free handle (the caller has checked the budgets and made the events): per pick
-// k_esp_free_z (+ k_esp_free_zsum when the columns are sliced), k_esp_update, k_esp_argmax.
-inline int esp_free_select(machip_esp* h, int nb, const int64_t* ks) {
-    const int K = (int)ks[nb - 1], P = h->grid_m(), zg = (h->ld + kEspFreeRows - 1) / kEspFreeRows;
-    ST_TRY(esp_free_reserve(h, K));
-    const EspView V = h->view();
-    hipStream_t st = h->stream;
-    h->live = false;
-    HIP_TRY(hipEventRecord(h->ev[0], st));
-    HIP_TRY(hipMemsetAsync(h->sel, 0, sizeof(int) * (size_t)std::max(h->m, 1), st));
-    HIP_TRY(hipMemsetAsync(h->bad, 0, sizeof(int), st));
-    k_esp_free_scores<<<P, kBlock, 0, st>>>(V, h->R, 1);
-    k_esp_argmax<<<1, kBlock, 0, st>>>(V, P);
-    for (int k = 0, b = 0; k < K; ++k) {
-        const int S = esp_free_slices(h, k);
-        if (S == 1) {
-            k_esp_free_z<false><<<zg, kBlock, 0, st>>>(V, h->R, nullptr, k, k, 0);
-        } else {
-            const int per = ((k + S - 1) / S + kEspFreeUnroll - 1) / kEspFreeUnroll * kEspFreeUnroll;
-            k_esp_free_z<true><<<dim3((unsigned)zg, (unsigned)S), kBlock, 0, st>>>(V, h->R, h->part, k, k, per);
-            k_esp_free_zsum<<<zg, kBlock, 0, st>>>(V, h->part, S, k, k);
-        }
-        if (k + 1 < K) {
-            k_esp_update<<<P, kBlock, 0, st>>>(V, k);
-            k_esp_argmax<<<1, kBlock, 0, st>>>(V, P);
-        }
-        while (b < nb && ks[b] == k + 1) HIP_TRY(hipEventRecord(h->ev[1 + b++], st));
+    int st = dev_alloc(&h->Zb, ld * (size_t)cols);
+    if (st == MACHIP_OK) st = dev_alloc(&h->cb, (size_t)cols);
+    if (st == MACHIP_OK && keep) {
+        hipError_t e = hipMemcpyAsync(h->Zb, oldZ, sizeof(double) * ld * (size_t)seeds, hipMemcpyDeviceToDevice, h->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(h->cb, oldc, sizeof(double) * (size_t)seeds, hipMemcpyDeviceToDevice, h->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+        if (e != hipSuccess) st = fail(MACHIP_HIP_ERROR, std::string("copying the seeds' columns: ") + hipGetErrorString(e));
     }
-    HIP_TRY(hipGetLastError());
-    h->pending = K;
+    if (st != MACHIP_OK) {
+        if (keep) {
+            if (h->Zb) (void)hipFree(h->Zb);
+            if (h->cb) (void)hipFree(h->cb);
+            h->Zb = oldZ; h->cb = oldc; h->zcap = (size_t)seeds;
+        }
+        return st;
+    }
+    if (oldZ) (void)hipFree(oldZ);
+    if (oldc) (void)hipFree(oldc);
+    h->zcap = (size_t)cols;
     return MACHIP_OK;
 }
 

@@ -206,24 +206,33 @@ inline int esp_relax_read(machip_esp* h, int np, double* out3) {
     return MACHIP_OK;
 }
 
+// The leading dimension an edge handle's relaxation inverts at, from the handle alone (node space: 0 -- machip_esp_relax_info's).
+inline int esp_relax_ld(const machip_esp* h) {
+    return h->edge_tree ? esp_edge_tree_ld((int64_t)h->m + h->tr->seeds) : h->edge_relax ? (std::max(h->m, 1) + kGjT - 1) / kGjT * kGjT : 0;
+}
+
+// the matrix an evaluation would invert is beyond the dense limit (the one statement of the three limits)
+inline bool esp_relax_oversize(const machip_esp* h) {
+    return h->edge_tree ? (int64_t)h->m + h->tr->seeds > kEspDenseMaxN : h->edge_relax ? h->m > kEspDenseMaxN : h->n > kEspDenseMaxN;
+}
+
 // What the relaxation cannot do on this handle, decided from the handle alone (nothing is allocated before it is asked).
 inline int esp_relax_limits(const machip_esp* h) {
     if (h->edge_tree) {
-        const int64_t m = h->m, sd = h->tr->seeds;
-        if (m + sd > kEspDenseMaxN)
+        if (esp_relax_oversize(h))
             return fail(MACHIP_BAD_ARG, "MACHIP_ESP_EDGE_RELAX_TREE inverts the dense (m + r) x (m + r) N(x): candidates plus seeds must be <= 16384 (m = " +
-                                            std::to_string(m) + ", r = " + std::to_string(sd) + ")");
+                                            std::to_string((int64_t)h->m) + ", r = " + std::to_string((int64_t)h->tr->seeds) + ")");
         return MACHIP_OK;
     }
     if (h->edge_relax) {
-        if (h->m > kEspDenseMaxN)
+        if (esp_relax_oversize(h))
             return fail(MACHIP_BAD_ARG, "MACHIP_ESP_EDGE_RELAX inverts the dense m x m N(x): the number of candidates must be <= 16384 (m = " +
                                             std::to_string(h->m) + ")");
         return MACHIP_OK;
     }
     if (h->form == kEspFormFree || h->tr)      // (tr: a MACHIP_ESP_MATRIX_FREE | MACHIP_ESP_SPANNING_TREE handle, esp_tree.h)
         return fail(MACHIP_BAD_ARG, "the relaxation inverts the dense M(x): not available on a MACHIP_ESP_MATRIX_FREE handle");
-    if (h->n > kEspDenseMaxN)
+    if (esp_relax_oversize(h))
         return fail(MACHIP_BAD_ARG, "the relaxation inverts the dense M(x) (no chain closed form): num_nodes must be <= 16384");
     return MACHIP_OK;
 }
@@ -278,6 +287,76 @@ inline int esp_relax_check_x(const machip_esp* h, const double* x) {
     for (int e = 0; e < h->m; ++e)
         if (!(x[e] >= 0.0 && x[e] <= 1.0))
             return fail(MACHIP_BAD_ARG, "x[" + std::to_string(e) + "] is not in [0, 1] (or not finite)");
+    return MACHIP_OK;
+}
+
+// workgroups of k_fw_final and k_relax_inner over the m candidates: their partials are summed in this grid's order
+inline int esp_relax_grid(const machip_esp* h) { return std::max(1, std::min(kMaxGrid, (h->m + kBlock - 1) / kBlock)); }
+
+// machip_esp_relax_eval after its NULL checks: F(x), and the gradient when asked
+inline int esp_relax_eval(machip_esp* h, const double* x, double* F_out, double* grad_out) {
+    ST_TRY(esp_relax_check_x(h, x));
+    ST_TRY(esp_relax_prepare(h));
+    EspRelax* r = h->rx;
+    if (h->m) HIP_TRY(hipMemcpyAsync(r->xa, x, sizeof(double) * (size_t)h->m, hipMemcpyHostToDevice, h->stream));
+    ST_TRY(esp_relax_eval_on(h, r->xa, grad_out != nullptr));
+    if (grad_out && h->m) HIP_TRY(hipMemcpyAsync(grad_out, h->s, sizeof(double) * (size_t)h->m, hipMemcpyDeviceToHost, h->stream));
+    double s3[3];
+    ST_TRY(esp_relax_read(h, 0, s3));
+    *F_out = s3[0];
+    return MACHIP_OK;
+}
+
+// machip_esp_relax_run after its NULL checks: Frank-Wolfe from x_inout, steps 1-6 and three scalars to the host per iteration
+inline int esp_relax_run(machip_esp* h, int64_t k, int max_iters, double gap_tol, double grad_tol, double* x_inout, double* f_traj,
+                         double* dual_traj, double* gnorm_traj, int* iters_out, double* upper_out) {
+    if (esp_relax_oversize(h)) return esp_relax_prepare(h);      // (the limit's message, nothing allocated)
+    if (k <= 0 || k > h->m) return fail(MACHIP_BAD_ARG, "k must be in [1, m] (m = " + std::to_string(h->m) + " candidates)");
+    ST_TRY(esp_relax_check_x(h, x_inout));
+    ST_TRY(esp_relax_prepare(h));
+    EspRelax* r = h->rx;
+    hipStream_t st = h->stream;
+    const size_t mb = sizeof(double) * (size_t)h->m;
+    const int grid = esp_relax_grid(h);
+    HIP_TRY(hipMemcpyAsync(r->xa, x_inout, mb, hipMemcpyHostToDevice, st));
+    double u = INFINITY;
+    for (int it = 0; it < max_iters; ++it) {
+        const double gamma = 2.0 / ((double)it + 2.0);
+        ST_TRY(esp_relax_eval_on(h, r->xa, true));
+        ST_TRY(esp_relax_select(h, (long)k));
+        k_fw_final<<<grid, kBlock, 0, st>>>(h->s, r->xa, h->m, r->st, gamma, r->xb, nullptr, r->part);
+        double s3[3];
+        ST_TRY(esp_relax_read(h, grid, s3));
+        u = std::min(u, s3[1]);
+        if (f_traj) f_traj[it] = s3[0];
+        if (dual_traj) dual_traj[it] = s3[1];
+        if (gnorm_traj) gnorm_traj[it] = s3[2];
+        *iters_out = it + 1;
+        *upper_out = u;
+        if (s3[2] < grad_tol) break;                                  // (x stays the iterate the test was evaluated at)
+        if ((u - s3[0]) < gap_tol * std::fabs(s3[0])) break;          // (F >= 0; at F = 0 the test cannot fire)
+        std::swap(r->xa, r->xb);
+    }
+    HIP_TRY(hipMemcpyAsync(x_inout, r->xa, mb, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return MACHIP_OK;
+}
+
+// machip_esp_relax_inner after its NULL checks: a . b through k_relax_inner and k_relax_scalars, in esp_relax_run's grid
+inline int esp_relax_inner(machip_esp* h, const double* a, const double* b, double* out) {
+    ST_TRY(esp_relax_prepare(h));
+    EspRelax* r = h->rx;
+    const size_t mb = sizeof(double) * (size_t)h->m;
+    const int grid = esp_relax_grid(h);
+    if (h->m) {
+        HIP_TRY(hipMemcpyAsync(r->xa, a, mb, hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(hipMemcpyAsync(r->xb, b, mb, hipMemcpyHostToDevice, h->stream));
+    }
+    k_relax_inner<<<grid, kBlock, 0, h->stream>>>(r->xa, r->xb, h->m, r->part);
+    k_relax_scalars<<<1, kBlock, 0, h->stream>>>(r->ldet, r->ld / kGjB, r->logdet0, r->part, grid, r->scal);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(out, r->scal + 3, sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
     return MACHIP_OK;
 }
 

@@ -32,8 +32,6 @@
 
 namespace machip {
 
-constexpr int kEspFormTree = 3;        // machip_esp::form of MACHIP_ESP_MATRIX_FREE | MACHIP_ESP_SPANNING_TREE
-
 // ---- host: the spanning tree and the seeds ----
 struct EspTreePlan {
     std::vector<int32_t> parent, pre, end, depth;      // by node; parent[0] = -1
@@ -298,79 +296,16 @@ inline int esp_tree_upload(machip_esp* h, const EspTreePlan& P) {
     return MACHIP_OK;
 }
 
-// The history for the r seeds and K picks: esp_free_reserve's rule on r + K columns.  The seeds' columns survive a regrowth: the
-// new history is allocated beside the old one and columns [0, r) are copied, so here the old history gives nothing back.
-// Refuses, before anything is freed or allocated, what does not fit.
-inline int esp_tree_reserve(machip_esp* h, int64_t K) {
-    EspTreeState* t = h->tr;
-    const int64_t cols = (int64_t)t->seeds + K;
-    if ((size_t)cols <= h->zcap) return MACHIP_OK;
-    const size_t ld = (size_t)h->ld;
-    const double need = 8.0 * (double)ld * (double)cols;
-    size_t fr = 0, tot = 0;
-    HIP_TRY(hipMemGetInfo(&fr, &tot));
-    const bool keep = t->seeded && t->seeds > 0;      // seeded columns to carry over
-    const double room = (double)fr + (keep ? 0.0 : 8.0 * (double)ld * (double)h->zcap) - 8.0 * (double)ld * kEspFreeMaxSplit - 8.0 * (double)cols - 268435456.0;
-    if (need > room || cols > (int64_t)INT_MAX)
-        return fail(MACHIP_BAD_ARG, "the matrix-free history does not fit in device memory: n = " + std::to_string(h->n) + ", K = " +
-                                        std::to_string((long long)K) + " and " + std::to_string(t->seeds) + " seeds ask for 8 ld (seeds + K) = " +
-                                        std::to_string((unsigned long long)need) + " bytes (ld = " + std::to_string(h->ld) + "), " +
-                                        std::to_string((unsigned long long)fr) + " bytes are free");
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    h->live = false;
-    double *oldZ = h->Zb, *oldc = h->cb;
-    if (!keep) {
-        if (oldZ) (void)hipFree(oldZ);
-        if (oldc) (void)hipFree(oldc);
-        oldZ = oldc = nullptr;
-    }
-    h->Zb = nullptr; h->cb = nullptr; h->zcap = 0;
-    if (!h->part) ST_TRY(dev_alloc(&h->part, ld * (size_t)kEspFreeMaxSplit));
-    int st = dev_alloc(&h->Zb, ld * (size_t)cols);
-    if (st == MACHIP_OK) st = dev_alloc(&h->cb, (size_t)cols);
-    if (st == MACHIP_OK && keep) {
-        hipError_t e = hipMemcpyAsync(h->Zb, oldZ, sizeof(double) * ld * (size_t)t->seeds, hipMemcpyDeviceToDevice, h->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(h->cb, oldc, sizeof(double) * (size_t)t->seeds, hipMemcpyDeviceToDevice, h->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-        if (e != hipSuccess) st = fail(MACHIP_HIP_ERROR, std::string("copying the seeds' columns: ") + hipGetErrorString(e));
-    }
-    if (st != MACHIP_OK) {          // keep the old history (and the seeds in it) if the new one could not be made
-        if (keep) {
-            if (h->Zb) (void)hipFree(h->Zb);
-            if (h->cb) (void)hipFree(h->cb);
-            h->Zb = oldZ; h->cb = oldc; h->zcap = (size_t)t->seeds;
-        }
-        return st;
-    }
-    if (oldZ) (void)hipFree(oldZ);
-    if (oldc) (void)hipFree(oldc);
-    h->zcap = (size_t)cols;
-    return MACHIP_OK;
-}
-
-// one z through the history's first j columns, started from zrow: k_esp_free_z<., true> (+ k_esp_free_zsum when sliced)
-inline void esp_tree_z(machip_esp* h, const EspView& V, int j, int k) {
-    const int zg = (h->ld + kEspFreeRows - 1) / kEspFreeRows;
-    const int S = esp_free_slices(h, j);
-    if (S == 1) {
-        k_esp_free_z<false, true><<<zg, kBlock, 0, h->stream>>>(V, h->tr->zrow, nullptr, j, k, 0);
-    } else {
-        const int per = ((j + S - 1) / S + kEspFreeUnroll - 1) / kEspFreeUnroll * kEspFreeUnroll;
-        k_esp_free_z<true, true><<<dim3((unsigned)zg, (unsigned)S), kBlock, 0, h->stream>>>(V, h->tr->zrow, h->part, j, k, per);
-        k_esp_free_zsum<<<zg, kBlock, 0, h->stream>>>(V, h->part, S, j, k);
-    }
-}
-
 // The history sized for K picks and, once per handle, the seeds run through it: tree scores, then per seed k_esp_tree_row,
 // the z product, its c, and k_esp_update over the candidates; the scores after the last seed are kept in s0.
 inline int esp_tree_prepare(machip_esp* h, int64_t K) {
     EspTreeState* t = h->tr;
-    ST_TRY(esp_tree_reserve(h, K));
+    ST_TRY(esp_history_reserve(h, t->seeds, t->seeded && t->seeds > 0, K));
     if (t->seeded) return MACHIP_OK;
     const EspView V = h->view();
     const EspTreeView T = t->view(h->n);
     hipStream_t st = h->stream;
-    const int P = h->grid_m(), rg = (h->ld + kBlock - 1) / kBlock;
+    const int P = h->grid_m(), rg = esp_rows_grid(h->ld);
     h->live = false;
     HIP_TRY(hipMemsetAsync(h->sel, 0, sizeof(int) * (size_t)std::max(h->m, 1), st));
     k_esp_tree_scores<<<P, kBlock, 0, st>>>(V, T);
@@ -379,7 +314,7 @@ inline int esp_tree_prepare(machip_esp* h, int64_t K) {
     Vs.gain = t->sgain; Vs.best = t->sbest;
     for (int q = 0; q < t->seeds; ++q) {
         k_esp_tree_row<true><<<rg, kBlock, 0, st>>>(Vs, T, t->zrow, q);
-        esp_tree_z(h, Vs, q, q);
+        esp_free_z<true>(h, Vs, t->zrow, q, q);
         k_esp_tree_seed_c<<<1, 1, 0, st>>>(Vs, q);
         k_esp_update<<<P, kBlock, 0, st>>>(V, q);
     }
@@ -387,42 +322,6 @@ inline int esp_tree_prepare(machip_esp* h, int64_t K) {
     HIP_TRY(hipMemcpyAsync(t->s0, h->s, sizeof(double) * (size_t)std::max(h->m, 1), hipMemcpyDeviceToDevice, st));
     HIP_TRY(hipStreamSynchronize(st));
     t->seeded = true;
-    return MACHIP_OK;
-}
-
-// The picks of machip_esp_select on a spanning-tree handle: per pick k_esp_tree_row, the z product over r + k columns,
-// k_esp_update, k_esp_argmax.
-inline int esp_tree_select(machip_esp* h, int nb, const int64_t* ks) {
-    EspTreeState* t = h->tr;
-    const int K = (int)ks[nb - 1], P = h->grid_m(), rg = (h->ld + kBlock - 1) / kBlock, r = t->seeds;
-    ST_TRY(esp_tree_prepare(h, K));
-    const EspView V = h->view();
-    const EspTreeView T = t->view(h->n);
-    hipStream_t st = h->stream;
-    h->live = false;
-    HIP_TRY(hipEventRecord(h->ev[0], st));
-    HIP_TRY(hipMemsetAsync(h->sel, 0, sizeof(int) * (size_t)std::max(h->m, 1), st));
-    HIP_TRY(hipMemsetAsync(h->bad, 0, sizeof(int), st));
-    k_esp_tree_restart<<<P, kBlock, 0, st>>>(V, t->s0);
-    k_esp_argmax<<<1, kBlock, 0, st>>>(V, P);
-    for (int k = 0, b = 0; k < K; ++k) {
-        k_esp_tree_row<false><<<rg, kBlock, 0, st>>>(V, T, t->zrow, 0);
-        esp_tree_z(h, V, r + k, k);
-        if (k + 1 < K) {
-            k_esp_update<<<P, kBlock, 0, st>>>(V, r + k);
-            k_esp_argmax<<<1, kBlock, 0, st>>>(V, P);
-        }
-        while (b < nb && ks[b] == k + 1) HIP_TRY(hipEventRecord(h->ev[1 + b++], st));
-    }
-    HIP_TRY(hipGetLastError());
-    h->pending = K;
-    return MACHIP_OK;
-}
-
-// w_e r_e of every candidate: the tree term and all r + j columns
-inline int esp_tree_resist(machip_esp* h) {
-    ST_TRY(esp_tree_prepare(h, 0));
-    k_esp_tree_resist<<<h->grid_m(), kBlock, 0, h->stream>>>(h->view(), h->tr->view(h->n), h->tr->seeds + (h->live ? h->pending : 0));
     return MACHIP_OK;
 }
 

@@ -19,6 +19,7 @@
 #include "esp.h"
 #include "esp_free.h"
 #include "esp_tree.h"
+#include "esp_select.h"
 #include "esp_relax.h"
 #include "esp_exchange.h"
 #include "esp_exchange_edge.h"
@@ -1565,180 +1566,32 @@ int machip_host_follow_records(const double* tri3, int J, int n, double e_target
     return MACHIP_OK;
 }
 
-// ---- GreedyESP (esp.h) ----
+// ---- GreedyESP (esp.h; the routes without Sigma: esp_free.h, esp_tree.h; the three together: esp_select.h) ----
 
 int machip_esp_create(int device, int64_t n, int64_t n_fixed, const int32_t* fi, const int32_t* fj, const double* fw,
                       int64_t m, const int32_t* ci, const int32_t* cj, const double* cw, int fold, int flags, machip_esp** out) {
     if (!out) return fail(MACHIP_BAD_ARG, "out is NULL");
     *out = nullptr;
-    if (n < 2) return fail(MACHIP_BAD_ARG, "num_nodes must be at least 2");
-    if (n_fixed < 0 || m < 0 || m > 2000000000ll) return fail(MACHIP_BAD_ARG, "bad edge counts");
-    if ((n_fixed && (!fi || !fj || !fw)) || (m && (!ci || !cj || !cw))) return fail(MACHIP_BAD_ARG, "NULL edge array");
-    const int fold_given = fold;
-    if (fold == 0) fold = kEspDefaultFold;
-    if (fold < 1 || fold > kEspMaxFold) return fail(MACHIP_BAD_ARG, "fold must be in [1, 256]");
-    if (flags & ~(MACHIP_ESP_DENSE_INVERSE | MACHIP_ESP_MATRIX_FREE | MACHIP_ESP_SPANNING_TREE | MACHIP_ESP_EDGE_RELAX | MACHIP_ESP_EDGE_RELAX_TREE))
-        return fail(MACHIP_BAD_ARG, "unknown flags");
+    ST_TRY(esp_create_check(n, n_fixed, fi, fj, fw, m, ci, cj, cw, fold, flags));
     const bool mfree = (flags & MACHIP_ESP_MATRIX_FREE) != 0, tree = (flags & MACHIP_ESP_SPANNING_TREE) != 0;
-    const bool edge = (flags & MACHIP_ESP_EDGE_RELAX) != 0, etree = (flags & MACHIP_ESP_EDGE_RELAX_TREE) != 0;
-    if (etree && edge)
-        return fail(MACHIP_BAD_ARG, "MACHIP_ESP_EDGE_RELAX_TREE builds the Gram matrix from the spanning tree, MACHIP_ESP_EDGE_RELAX from the chain: the two cannot be combined");
-    if (etree && (flags & MACHIP_ESP_DENSE_INVERSE))
-        return fail(MACHIP_BAD_ARG, "MACHIP_ESP_EDGE_RELAX_TREE takes Sigma0 from the spanning tree's closed form: it cannot be combined with MACHIP_ESP_DENSE_INVERSE");
-    if (etree && !(mfree && tree))      // (without its partners the bit was an unknown flag before the route existed, and stays one)
-        return fail(MACHIP_BAD_ARG, "unknown flags: MACHIP_ESP_EDGE_RELAX_TREE puts the relaxation on the spanning-tree handle and is valid only together with MACHIP_ESP_MATRIX_FREE | MACHIP_ESP_SPANNING_TREE");
-    if (edge && !mfree)      // (alone the bit was an unknown flag before the route existed, and stays one: the message keeps saying so)
-        return fail(MACHIP_BAD_ARG, "unknown flags: MACHIP_ESP_EDGE_RELAX puts the relaxation on the chain-free handle and is valid only together with MACHIP_ESP_MATRIX_FREE");
-    if (edge && (flags & MACHIP_ESP_DENSE_INVERSE))
-        return fail(MACHIP_BAD_ARG, "MACHIP_ESP_EDGE_RELAX takes Sigma0 from the chain's closed form: it cannot be combined with MACHIP_ESP_DENSE_INVERSE");
-    if (edge && tree)
-        return fail(MACHIP_BAD_ARG, "MACHIP_ESP_EDGE_RELAX has the chain's closed form only: it cannot be combined with MACHIP_ESP_SPANNING_TREE");
-    if (tree && !mfree)
-        return fail(MACHIP_BAD_ARG, "MACHIP_ESP_SPANNING_TREE selects the spanning tree of the matrix-free route: it is valid only together with MACHIP_ESP_MATRIX_FREE");
-    if (mfree && fold_given != 0)      // (an argument that would be ignored is refused, not dropped: nothing is ever folded here)
-        return fail(MACHIP_BAD_ARG, "MACHIP_ESP_MATRIX_FREE never folds: fold has no meaning on this route and must be 0");
-    if (mfree && (flags & MACHIP_ESP_DENSE_INVERSE))
-        return fail(MACHIP_BAD_ARG, "MACHIP_ESP_MATRIX_FREE keeps no Sigma: it cannot be combined with MACHIP_ESP_DENSE_INVERSE");
-    if (mfree && n > (int64_t)INT_MAX - kGjT) return fail(MACHIP_BAD_ARG, "node ids are int32: num_nodes is too large");
-    if (!mfree && n > kEspChainMaxN) return fail(MACHIP_BAD_ARG, "GreedyESP keeps (L_red + beta I)^-1 dense: num_nodes must be <= 32768 (chain-fixed graphs), <= 16384 otherwise");
-    for (int64_t e = 0; e < n_fixed; ++e)
-        if (fi[e] < 0 || fi[e] >= n || fj[e] < 0 || fj[e] >= n || !std::isfinite(fw[e])) return fail(MACHIP_BAD_ARG, "fixed edge out of range or weight not finite");
-    for (int64_t e = 0; e < m; ++e)
-        if (ci[e] < 0 || ci[e] >= n || cj[e] < 0 || cj[e] >= n || !std::isfinite(cw[e])) return fail(MACHIP_BAD_ARG, "candidate edge out of range or weight not finite");
-    // beta (the reference: Cholesky with beta = 0; on failure raise if a reduced row is all zero, else beta = 1e-4), decided by a
-    // union-find over F
-    const int N = (int)n, np = N - 1;
-    std::vector<int> par(N), has(N, 0);
-    std::iota(par.begin(), par.end(), 0);
-    auto root = [&](int a) { while (par[a] != a) { par[a] = par[par[a]]; a = par[a]; } return a; };
-    int comps = N;
-    for (int64_t e = 0; e < n_fixed; ++e) {
-        if (fi[e] == fj[e] || fw[e] == 0.0) continue;
-        has[fi[e]] = has[fj[e]] = 1;
-        const int a = root(fi[e]), b = root(fj[e]);
-        if (a != b) { par[a] = b; --comps; }
-    }
-    if (tree && comps > 1)
-        return fail(MACHIP_BAD_ARG, "the spanning-tree route needs a connected fixed graph: the fixed edges leave " + std::to_string(comps) + " components");
-    double beta = 0.0;
-    if (comps > 1) {
-        for (int i = 1; i < N; ++i)
-            if (!has[i]) return fail(MACHIP_DISCONNECTED, "node " + std::to_string(i) + " has no fixed edge: row " + std::to_string(i - 1) + " of L_fixed is all zeros");
-        beta = 1e-4;
-    }
-    // chain form: F is exactly the path (i, i+1), parallel links summed
-    std::vector<double> link((size_t)np, 0.0);
-    bool chain = !(flags & MACHIP_ESP_DENSE_INVERSE) && comps == 1 && !tree;
-    for (int64_t e = 0; chain && e < n_fixed; ++e) {
-        const int a = std::min(fi[e], fj[e]), b = std::max(fi[e], fj[e]);
-        if (b != a + 1) chain = false;
-        else link[(size_t)a] += fw[e];
-    }
-    for (int i = 0; chain && i < np; ++i) if (!(link[(size_t)i] > 0.0)) chain = false;
+    EspFixedClass fixed;
+    ST_TRY(esp_classify_fixed(n, n_fixed, fi, fj, fw, flags, fixed));
     EspTreePlan tplan;
     if (tree) ST_TRY(esp_tree_plan(n, n_fixed, fi, fj, fw, tplan));
-    if (mfree && !tree && !chain)
-        return fail(MACHIP_BAD_ARG, std::string("the matrix-free route needs a chain: the fixed edges must be exactly the connected path (i, i+1), i = 0..n-2 (parallel links summed)") +
-                                        (edge ? "; MACHIP_ESP_EDGE_RELAX builds the candidates' Gram matrix from that chain's resistances" : ""));
-    if (!chain && !tree && n > kEspDenseMaxN)
-        return fail(MACHIP_BAD_ARG, "GreedyESP inverts L_red + beta I densely when the fixed edges are not exactly the chain (i, i+1): num_nodes must be <= 16384");
     if (machip_device_count() <= 0) return fail(MACHIP_NO_DEVICE, "no HIP device visible");
     HIP_TRY(hipSetDevice(device));
     machip_esp* h = new machip_esp();
-    h->device = device; h->n = N; h->np = np; h->m = (int)m; h->fold = mfree ? 0 : fold; h->beta = beta; h->form = tree ? kEspFormTree : mfree ? kEspFormFree : chain ? 0 : 1;
-    h->edge_relax = edge;
-    h->edge_tree = etree;
+    h->device = device; h->n = (int)n; h->np = (int)n - 1; h->m = (int)m; h->fold = mfree ? 0 : fold; h->beta = fixed.beta;
+    h->form = tree ? kEspFormTree : mfree ? kEspFormFree : fixed.chain ? 0 : 1;
+    h->edge_relax = (flags & MACHIP_ESP_EDGE_RELAX) != 0;
+    h->edge_tree = (flags & MACHIP_ESP_EDGE_RELAX_TREE) != 0;
     h->free_split = (int)std::max(0l, std::min<long>(default_options().get(kOpt_esp_free_split, 0), kEspFreeMaxSplit));
-    h->ld = (np + kGjT - 1) / kGjT * kGjT;
+    h->ld = (h->np + kGjT - 1) / kGjT * kGjT;
     h->hfi.assign(fi, fi + n_fixed); h->hfj.assign(fj, fj + n_fixed); h->hfw.assign(fw, fw + n_fixed);
     h->hci.assign(ci, ci + m); h->hcj.assign(cj, cj + m); h->hcw.assign(cw, cw + m);
-    auto body = [&]() -> int {
-        HIP_TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-        const size_t ld = (size_t)h->ld, ms = (size_t)std::max<int64_t>(m, 1);
-        if (!mfree) { ST_TRY(dev_alloc(&h->bufA, ld * ld)); ST_TRY(dev_alloc(&h->bufB, ld * ld)); }
-        ST_TRY(dev_alloc(&h->cu, ms)); ST_TRY(dev_alloc(&h->cv, ms)); ST_TRY(dev_alloc(&h->cw, ms)); ST_TRY(dev_alloc(&h->s, ms));
-        ST_TRY(dev_alloc(&h->sel, ms)); ST_TRY(dev_alloc(&h->order, ms)); ST_TRY(dev_alloc(&h->gain, ms));
-        if (!mfree) { ST_TRY(dev_alloc(&h->Zb, ld * (size_t)fold)); ST_TRY(dev_alloc(&h->cb, (size_t)fold)); }      // (matrix-free: machip_esp_select sizes the history)
-        ST_TRY(dev_alloc(&h->pv, (size_t)kEspGrid)); ST_TRY(dev_alloc(&h->pi, (size_t)kEspGrid)); ST_TRY(dev_alloc(&h->best, 1));
-        ST_TRY(dev_alloc(&h->bad, 1)); ST_TRY(dev_alloc(&h->piv, (size_t)2 * kGjB * kGjB));
-        if (!mfree) {
-            HIP_TRY(hipMemsetAsync(h->Zb, 0, sizeof(double) * ld * (size_t)fold, h->stream));
-            HIP_TRY(hipMemsetAsync(h->cb, 0, sizeof(double) * (size_t)fold, h->stream));
-        }
-        HIP_TRY(hipMemsetAsync(h->bad, 0, sizeof(int), h->stream));
-        if (m) {
-            std::vector<int> u((size_t)m), v((size_t)m);
-            for (int64_t e = 0; e < m; ++e) { u[(size_t)e] = ci[e] - 1; v[(size_t)e] = cj[e] - 1; }
-            HIP_TRY(hipMemcpyAsync(h->cu, u.data(), sizeof(int) * (size_t)m, hipMemcpyHostToDevice, h->stream));
-            HIP_TRY(hipMemcpyAsync(h->cv, v.data(), sizeof(int) * (size_t)m, hipMemcpyHostToDevice, h->stream));
-            HIP_TRY(hipMemcpyAsync(h->cw, cw, sizeof(double) * (size_t)m, hipMemcpyHostToDevice, h->stream));
-            HIP_TRY(hipStreamSynchronize(h->stream));     // (host staging goes out of scope)
-        }
-        if (tree) return esp_tree_upload(h, tplan);      // the tables are all of Sigma0 this route keeps; the seeds run at the first use
-        if (chain) {
-            std::vector<double> R((size_t)np);
-            double acc = 0.0;
-            for (int i = 0; i < np; ++i) { acc += 1.0 / link[(size_t)i]; R[(size_t)i] = acc; }
-            double* dR = nullptr;
-            ST_TRY(dev_alloc(&dR, (size_t)np));
-            HIP_TRY(hipMemcpyAsync(dR, R.data(), sizeof(double) * (size_t)np, hipMemcpyHostToDevice, h->stream));
-            if (mfree) {                                  // R is all of Sigma0 this route keeps
-                h->R = dR;
-                HIP_TRY(hipStreamSynchronize(h->stream));
-                return MACHIP_OK;
-            }
-            k_esp_chain_fill<<<dim3((unsigned)((ld + kBlock - 1) / kBlock), (unsigned)ld), kBlock, 0, h->stream>>>(h->bufA, dR, np, (int)ld);
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipStreamSynchronize(h->stream));
-            (void)hipFree(dR);
-            h->sig0 = h->bufA; h->sig = h->bufB;
-            return MACHIP_OK;
-        }
-        // general form: dense L_red + beta I (identity beyond n'), entries summed on the host in edge order, then inverted
-        std::vector<double> diag((size_t)np, beta);
-        std::vector<std::pair<int64_t, double>> off;
-        off.reserve((size_t)n_fixed);
-        for (int64_t e = 0; e < n_fixed; ++e) {
-            const int a = fi[e] - 1, b = fj[e] - 1;
-            if (a == b) continue;
-            if (a >= 0) diag[(size_t)a] += fw[e];
-            if (b >= 0) diag[(size_t)b] += fw[e];
-            if (a >= 0 && b >= 0) off.emplace_back((int64_t)std::min(a, b) * (int64_t)ld + std::max(a, b), fw[e]);
-        }
-        std::stable_sort(off.begin(), off.end(), [](const std::pair<int64_t, double>& x, const std::pair<int64_t, double>& y) { return x.first < y.first; });
-        std::vector<int64_t> pos;
-        std::vector<double> val;
-        for (int i = 0; i < (int)ld; ++i) { pos.push_back((int64_t)i * (int64_t)ld + i); val.push_back(i < np ? diag[(size_t)i] : 1.0); }
-        for (size_t q = 0; q < off.size();) {
-            size_t r = q;
-            double w = 0.0;
-            for (; r < off.size() && off[r].first == off[q].first; ++r) w += off[r].second;
-            const int64_t a = off[q].first / (int64_t)ld, b = off[q].first % (int64_t)ld;
-            pos.push_back(a * (int64_t)ld + b); val.push_back(-w);
-            pos.push_back(b * (int64_t)ld + a); val.push_back(-w);
-            q = r;
-        }
-        int64_t* dpos = nullptr;
-        double* dval = nullptr;
-        ST_TRY(dev_alloc(&dpos, pos.size())); ST_TRY(dev_alloc(&dval, val.size()));
-        HIP_TRY(hipMemsetAsync(h->bufA, 0, sizeof(double) * ld * ld, h->stream));
-        HIP_TRY(hipMemcpyAsync(dpos, pos.data(), sizeof(int64_t) * pos.size(), hipMemcpyHostToDevice, h->stream));
-        HIP_TRY(hipMemcpyAsync(dval, val.data(), sizeof(double) * val.size(), hipMemcpyHostToDevice, h->stream));
-        const int cnt = (int)pos.size();
-        k_esp_scatter<<<std::max(1, std::min(kMaxGrid, (cnt + kBlock - 1) / kBlock)), kBlock, 0, h->stream>>>(h->bufA, dpos, dval, cnt);
-        // (L_red + beta I)^-1 by the blocked Gauss-Jordan elimination (esp.h: gj_inverse)
-        double *src = h->bufA, *dst = h->bufB;
-        h->gj_inverse<false>(src, dst);
-        HIP_TRY(hipGetLastError());
-        int hbad = 0;
-        HIP_TRY(hipMemcpyAsync(&hbad, h->bad, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(hipStreamSynchronize(h->stream));
-        (void)hipFree(dpos); (void)hipFree(dval);
-        if (hbad) return fail(MACHIP_NOT_CONVERGED, "L_red + beta I is not positive definite numerically (a non-positive Gauss-Jordan pivot)");
-        h->sig0 = src; h->sig = dst;
-        return MACHIP_OK;
-    };
-    const int st = body();
+    int st = esp_alloc(h);
+    if (st == MACHIP_OK)      // Sigma0: the tree's tables (the seeds run at the first use), the chain's closed form, the dense inverse
+        st = tree ? esp_tree_upload(h, tplan) : fixed.chain ? esp_sigma0_chain(h, fixed.link) : esp_sigma0_dense(h);
     if (st != MACHIP_OK) { machip_esp_destroy(h); return st; }
     *out = h;
     return MACHIP_OK;
@@ -1788,126 +1641,22 @@ int machip_esp_info(machip_esp* h, int32_t* info4, double* beta) {
     return MACHIP_OK;
 }
 
-static int esp_select_finish(machip_esp* h, int nb, int K, int32_t* order_out, double* gain_out, double* t_ms_out);
-
 int machip_esp_select(machip_esp* h, int nb, const int64_t* ks, int32_t* order_out, double* gain_out, double* t_ms_out) {
     if (!h || nb < 1 || !ks) return fail(MACHIP_BAD_ARG, "NULL handle, no budgets or ks is NULL");
     if (ks[0] <= 0) return fail(MACHIP_BAD_ARG, "budgets must be positive");
     for (int i = 0; i + 1 < nb; ++i) if (ks[i] > ks[i + 1]) return fail(MACHIP_BAD_ARG, "budgets must be monotonically increasing");
     if (ks[nb - 1] > h->m) return fail(MACHIP_BAD_ARG, "not enough candidate edges to satisfy the largest budget");
     HIP_TRY(hipSetDevice(h->device));
-    while ((int)h->ev.size() < nb + 1) {
-        hipEvent_t e;
-        HIP_TRY(hipEventCreate(&e));
-        h->ev.push_back(e);
-    }
-    const int K = (int)ks[nb - 1], B = h->fold, P = h->grid_m(), zg = (h->ld + kBlock - 1) / kBlock;
-    hipStream_t st = h->stream;
-    if (h->form == kEspFormFree || h->form == kEspFormTree) {
-        ST_TRY(h->form == kEspFormTree ? esp_tree_select(h, nb, ks) : esp_free_select(h, nb, ks));
-        return esp_select_finish(h, nb, K, order_out, gain_out, t_ms_out);
-    }
-    const EspView V = h->view();
-    h->live = false;
-    HIP_TRY(hipEventRecord(h->ev[0], st));
-    HIP_TRY(hipMemcpyAsync(h->sig, h->sig0, sizeof(double) * (size_t)h->ld * (size_t)h->ld, hipMemcpyDeviceToDevice, st));
-    HIP_TRY(hipMemsetAsync(h->sel, 0, sizeof(int) * (size_t)h->m, st));
-    HIP_TRY(hipMemsetAsync(h->bad, 0, sizeof(int), st));
-    k_esp_scores<<<P, kBlock, 0, st>>>(V, h->sig, 1);
-    k_esp_argmax<<<1, kBlock, 0, st>>>(V, P);
-    for (int k = 0, b = 0; k < K; ++k) {
-        const int j = k % B;
-        k_esp_z<<<zg, kBlock, 0, st>>>(V, h->sig, j, k);
-        if (k + 1 < K) {
-            k_esp_update<<<P, kBlock, 0, st>>>(V, j);
-            k_esp_argmax<<<1, kBlock, 0, st>>>(V, P);
-        }
-        if (j == B - 1) h->fold_into(h->sig, B);
-        while (b < nb && ks[b] == k + 1) HIP_TRY(hipEventRecord(h->ev[1 + b++], st));
-    }
-    HIP_TRY(hipGetLastError());
-    h->pending = K % B;
-    return esp_select_finish(h, nb, K, order_out, gain_out, t_ms_out);
-}
-
-// the end of a selection run, either route: the results and the budgets' times to the host
-static int esp_select_finish(machip_esp* h, int nb, int K, int32_t* order_out, double* gain_out, double* t_ms_out) {
-    hipStream_t st = h->stream;
-    int hbad = 0;
-    if (order_out) HIP_TRY(hipMemcpyAsync(order_out, h->order, sizeof(int) * (size_t)K, hipMemcpyDeviceToHost, st));
-    if (gain_out) HIP_TRY(hipMemcpyAsync(gain_out, h->gain, sizeof(double) * (size_t)K, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(&hbad, h->bad, sizeof(int), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (t_ms_out)
-        for (int i = 0; i < nb; ++i) {
-            float ms = 0.0f;
-            HIP_TRY(hipEventElapsedTime(&ms, h->ev[0], h->ev[1 + i]));
-            t_ms_out[i] = ms;
-        }
-    h->live = true;
-    if (hbad) return fail(MACHIP_NOT_CONVERGED, "no finite score among the unselected candidates");
-    return MACHIP_OK;
+    return esp_select(h, nb, ks, order_out, gain_out, t_ms_out);
 }
 
 int machip_esp_weighted_resistances(machip_esp* h, double* r_out) {
     if (!h || (!r_out && h->m)) return fail(MACHIP_BAD_ARG, "NULL handle or output");
     HIP_TRY(hipSetDevice(h->device));
-    if (h->form == kEspFormTree) {
-        ST_TRY(esp_tree_resist(h));
-        HIP_TRY(hipGetLastError());
-        if (h->m) HIP_TRY(hipMemcpyAsync(r_out, h->s, sizeof(double) * (size_t)h->m, hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(hipStreamSynchronize(h->stream));
-        return MACHIP_OK;
-    }
-    double* S = h->live ? h->sig : h->sig0;
-    if (h->form != kEspFormFree && h->live && h->pending) { h->fold_into(S, h->pending); h->pending = 0; }
-    if (h->m) {
-        if (h->form != kEspFormFree) k_esp_scores<<<h->grid_m(), kBlock, 0, h->stream>>>(h->view(), S, 0);
-        else if (h->live) k_esp_free_resist<<<h->grid_m(), kBlock, 0, h->stream>>>(h->view(), h->R, h->pending);
-        else k_esp_free_scores<<<h->grid_m(), kBlock, 0, h->stream>>>(h->view(), h->R, 0);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(r_out, h->s, sizeof(double) * (size_t)h->m, hipMemcpyDeviceToHost, h->stream));
-    }
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    return MACHIP_OK;
+    return esp_resistances(h, r_out);
 }
 
-// ---- the exchange on GreedyESP's handle (esp_exchange.h) ----
-
-namespace {
-// Device time per phase of the exchange (option esp_xch_profile): events between the phases, read after the round's own
-// synchronisation.  Interval q lies between marks q - 1 and q and belongs to the phase mark q names (-1: nobody's -- the host waited).
-struct XchClock {
-    machip_esp* h;
-    bool on;
-    size_t base, used = 0;
-    std::vector<int> tag;
-    double acc[6] = {0, 0, 0, 0, 0, 0};
-    int mark(int phase) {
-        if (!on) return MACHIP_OK;
-        while (h->ev.size() <= base + used) {
-            hipEvent_t e;
-            HIP_TRY(hipEventCreate(&e));
-            h->ev.push_back(e);
-        }
-        HIP_TRY(hipEventRecord(h->ev[base + used], h->stream));
-        tag.push_back(phase);
-        ++used;
-        return MACHIP_OK;
-    }
-    int collect() {      // (the stream is idle)
-        for (size_t q = 1; q < used; ++q) {
-            if (tag[q] < 0) continue;
-            float ms = 0.0f;
-            HIP_TRY(hipEventElapsedTime(&ms, h->ev[base + q - 1], h->ev[base + q]));
-            acc[tag[q]] += ms;
-        }
-        used = 0;
-        tag.clear();
-        return MACHIP_OK;
-    }
-};
-}  // namespace
+// ---- the exchange on GreedyESP's handle (esp_exchange.h) and in the candidates' space (esp_exchange_edge.h) ----
 
 int machip_esp_exchange(machip_esp* h, int64_t k, const int32_t* sel_in, int64_t max_swaps, double min_gain, int32_t* sel_out,
                         int32_t* out_idx, int32_t* in_idx, double* ratio, int64_t* n_swaps, int32_t* converged, double* t_ms) {
@@ -1916,109 +1665,8 @@ int machip_esp_exchange(machip_esp* h, int64_t k, const int32_t* sel_in, int64_t
     *n_swaps = 0;
     *converged = 0;
     HIP_TRY(hipSetDevice(h->device));
-    const Options& O = default_options();
-    const int K = (int)k, m = h->m, B = h->fold, P = h->grid_m(), zg = (h->ld + kBlock - 1) / kBlock;
-    const int chunks = std::max(1, std::min((m + kBlock - 1) / kBlock, (kEspXchTargetGroups + K - 1) / K));
-    const int per = (m + chunks - 1) / chunks;
-    const long lds_kb = std::max(0l, std::min<long>(O.get(kOpt_esp_xch_lds_kb, kEspXchLdsDefaultKb), kEspXchLdsMaxKb));
-    const size_t row_bytes = sizeof(double) * (size_t)h->ld;
-    bool lds = row_bytes <= (size_t)lds_kb * 1024;
-    ST_TRY(esp_xch_prepare(h->xc, (size_t)K, (size_t)K * (size_t)chunks, (size_t)std::max<int64_t>(max_swaps, 1), (size_t)h->ld));
-    EspXch* X = h->xc;
-    if (lds && row_bytes > 48 * 1024 &&
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&k_esp_xch_pairs<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)row_bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        lds = false;      // (the runtime does not grant the row: the global-memory rows give the same bits)
-    }
-    while (h->ev.size() < 2) {
-        hipEvent_t e;
-        HIP_TRY(hipEventCreate(&e));
-        h->ev.push_back(e);
-    }
-    XchClock clk{h, O.get(kOpt_esp_xch_profile, 0) != 0, 2};
-    enum { kLoad = 1, kPairs = 2, kTrows = 3, kSteps = 4, kFolds = 5 };
-    hipStream_t st = h->stream;
-    const EspView V = h->view();
-    std::vector<char> in_sel((size_t)m, 0);
-    for (int e : rowe) in_sel[(size_t)e] = 1;
-    int j = 0;      // columns of Zb pending
-    // one rank-1 update of Sigma: the z of e into Zb[:, j], all m scores, T's rows (with_rows), the fold when Zb is full
-    auto step = [&](int e, int mode, double* rt, bool with_rows, int xrow, int f_in) -> int {
-        k_esp_xch_step<<<zg, kBlock, 0, st>>>(V, h->sig, j, e, mode, rt, X->scale);
-        k_esp_update<<<P, kBlock, 0, st>>>(V, j);
-        if (with_rows) ST_TRY(clk.mark(kSteps));      // (the load is one interval, marked at its end)
-        if (with_rows) {
-            k_esp_xch_tupdate<<<dim3((unsigned)K, (unsigned)zg), kBlock, 0, st>>>(V, X->T, X->rowe, j, xrow, f_in, X->scale);
-            ST_TRY(clk.mark(kTrows));
-        }
-        if (++j == B) {
-            h->fold_into(h->sig, B);
-            j = 0;
-            if (with_rows) ST_TRY(clk.mark(kFolds));
-        }
-        return MACHIP_OK;
-    };
-    // the load: Sigma0, the scores, the K given edges as forced picks in ascending index order, then T
-    h->live = false;
-    h->pending = 0;
-    HIP_TRY(hipEventRecord(h->ev[0], st));
-    ST_TRY(clk.mark(-1));
-    HIP_TRY(hipMemcpyAsync(h->sig, h->sig0, sizeof(double) * (size_t)h->ld * (size_t)h->ld, hipMemcpyDeviceToDevice, st));
-    HIP_TRY(hipMemsetAsync(h->sel, 0, sizeof(int) * (size_t)m, st));
-    HIP_TRY(hipMemsetAsync(h->bad, 0, sizeof(int), st));
-    HIP_TRY(hipMemcpyAsync(X->rowe, rowe.data(), sizeof(int) * (size_t)K, hipMemcpyHostToDevice, st));
-    k_esp_scores<<<P, kBlock, 0, st>>>(V, h->sig, 0);
-    for (int q = 0; q < K; ++q) ST_TRY(step(rowe[(size_t)q], 1, nullptr, false, -1, -1));
-    if (max_swaps > 0) k_esp_xch_tbuild<<<dim3((unsigned)K, (unsigned)zg), kBlock, 0, st>>>(V, h->sig, j, X->rowe, X->T);
-    HIP_TRY(hipGetLastError());
-    ST_TRY(clk.mark(kLoad));
-    int64_t t = 0;
-    int hbad = 0;
-    for (; t < max_swaps; ++t) {
-        if (lds) {
-            k_esp_xch_pairs<true><<<dim3((unsigned)K, (unsigned)chunks), kBlock, row_bytes, st>>>(V, X->T, X->rowe, per, X->pv, X->pf);
-            if (hipGetLastError() != hipSuccess) lds = false;      // (the launch was refused, nothing ran: global-memory rows from here on)
-        }
-        if (!lds) k_esp_xch_pairs<false><<<dim3((unsigned)K, (unsigned)chunks), kBlock, 0, st>>>(V, X->T, X->rowe, per, X->pv, X->pf);
-        k_esp_xch_argmax<<<1, kBlock, 0, st>>>(V, X->rowe, X->pv, X->pf, K * chunks, chunks, X->best);
-        HIP_TRY(hipGetLastError());
-        ST_TRY(clk.mark(kPairs));
-        EspXchBest b;
-        HIP_TRY(hipMemcpyAsync(&b, X->best, sizeof(b), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(&hbad, h->bad, sizeof(int), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        ST_TRY(clk.collect());
-        if (hbad) break;
-        if (b.val - 1.0 <= min_gain) { *converged = 1; break; }
-        ST_TRY(esp_xch_apply(rowe, in_sel, b.row, b.e, b.f));
-        out_idx[t] = b.e;
-        in_idx[t] = b.f;
-        ST_TRY(clk.mark(-1));
-        ST_TRY(step(b.e, -1, X->ratio + t, true, b.row, -1));
-        ST_TRY(step(b.f, +1, X->ratio + t, true, b.row, b.f));
-        HIP_TRY(hipGetLastError());
-    }
-    HIP_TRY(hipEventRecord(h->ev[1], st));
-    if (t > 0) HIP_TRY(hipMemcpyAsync(ratio, X->ratio, sizeof(double) * (size_t)t, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(&hbad, h->bad, sizeof(int), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    ST_TRY(clk.collect());
-    h->pending = j;
-    h->live = true;
-    if (hbad)
-        return fail(MACHIP_NOT_CONVERGED, "exchange: 1 - s_e of a removal or 1 + s_f of an insertion is not positive, or no finite Delta (the selection holds a bridge of the graph, or lost numerically)");
-    *n_swaps = t;
-    for (int e = 0, q = 0; e < m; ++e) if (in_sel[(size_t)e]) sel_out[q++] = e;
-    if (t_ms) {
-        float ms = 0.0f;
-        HIP_TRY(hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
-        t_ms[0] = ms;
-        for (int q = 1; q < 6; ++q) t_ms[q] = clk.acc[q];
-    }
-    return MACHIP_OK;
+    return esp_exchange(h, k, rowe, max_swaps, min_gain, sel_out, out_idx, in_idx, ratio, n_swaps, converged, t_ms);
 }
-
-// ---- the exchange in the candidates' space, on the edge-space relaxation's handles (esp_exchange_edge.h) ----
 
 int machip_esp_exchange_edge(machip_esp* h, int64_t k, const int32_t* sel_in, int64_t max_swaps, double min_gain, int32_t* sel_out,
                              int32_t* out_idx, int32_t* in_idx, double* ratio, int64_t* n_swaps, int32_t* converged, double* t_ms) {
@@ -2028,117 +1676,14 @@ int machip_esp_exchange_edge(machip_esp* h, int64_t k, const int32_t* sel_in, in
     *converged = 0;
     ST_TRY(esp_relax_limits(h));
     HIP_TRY(hipSetDevice(h->device));
-    const Options& O = default_options();
-    const int K = (int)k, m = h->m, B = kEspDefaultFold, ld = esp_xe_ld(h), zg = (ld + kBlock - 1) / kBlock;
-    const int chunks = std::max(1, std::min((m + kBlock - 1) / kBlock, (kEspXchTargetGroups + K - 1) / K));
-    const int per = ((m + chunks - 1) / chunks + 1) & ~1;      // (even: a chunk starts on a 16-byte boundary of its rows)
-    if (!h->xe) h->xe = new EspXchEdge();
-    EspXchEdge* E = h->xe;
-    ST_TRY(esp_xch_prepare(E->x, (size_t)K, (size_t)K * (size_t)chunks, (size_t)std::max<int64_t>(max_swaps, 1), (size_t)ld));      // (T is refused before G is built)
-    ST_TRY(esp_relax_prepare(h));
-    if (const int stp = esp_xe_prepare(h, E)) {      // (nothing half-made stays on the handle)
-        esp_xe_release(h->xe);
-        return stp;
-    }
-    EspXch* X = E->x;
-    while (h->ev.size() < 2) {
-        hipEvent_t e;
-        HIP_TRY(hipEventCreate(&e));
-        h->ev.push_back(e);
-    }
-    XchClock clk{h, O.get(kOpt_esp_xch_profile, 0) != 0, 2};
-    enum { kLoad = 1, kPairs = 2, kTrows = 3, kSteps = 4, kFolds = 5 };
-    hipStream_t st = h->stream;
-    const EspView V = E->view();
-    const int M = E->M, P = E->grid(), tiles = ld / kGjT;
-    std::vector<char> in_sel((size_t)m, 0);
-    for (int e : rowe) in_sel[(size_t)e] = 1;
-    double* Rm = nullptr;
-    int j = 0;      // columns of Zb pending
-    // one rank-1 update of R: row e less the pending columns into Zb[:, j], all M scores, T's rows (with_rows), the fold when Zb is full
-    auto step = [&](int e, int mode, double* rt, bool with_rows, int xrow, int f_in) -> int {
-        k_esp_xch_step<<<zg, kBlock, 0, st>>>(V, Rm, j, e, mode, rt, X->scale);
-        k_esp_update<<<P, kBlock, 0, st>>>(V, j);
-        if (mode > 0) k_esp_xe_entered<<<1, kBlock, 0, st>>>(V, e, j, X->scale);      // (s_e / (1 + s_e) without the cancellation)
-        if (with_rows) ST_TRY(clk.mark(kSteps));      // (the load is one interval, marked at its end)
-        if (with_rows) {
-            k_esp_xch_tupdate<<<dim3((unsigned)K, (unsigned)zg), kBlock, 0, st>>>(V, X->T, X->rowe, j, xrow, f_in, X->scale);
-            ST_TRY(clk.mark(kTrows));
-        }
-        if (++j == B) {
-            k_esp_fold<<<dim3(tiles, tiles), 256, 0, st>>>(Rm, E->Zb, E->cb, ld, B);
-            j = 0;
-            if (with_rows) ST_TRY(clk.mark(kFolds));
-        }
-        return MACHIP_OK;
-    };
-    // the load: R <- G, the scores, the seeds and then the K given candidates (ascending) as forced picks, then T
-    HIP_TRY(hipEventRecord(h->ev[0], st));
-    ST_TRY(clk.mark(-1));
-    ST_TRY(esp_xe_load_gram(h, E, &Rm));
-    HIP_TRY(hipMemsetAsync(E->sel, 0, sizeof(int) * (size_t)ld, st));
-    HIP_TRY(hipMemsetAsync(E->bad, 0, sizeof(int), st));
-    HIP_TRY(hipMemcpyAsync(X->rowe, rowe.data(), sizeof(int) * (size_t)K, hipMemcpyHostToDevice, st));
-    k_esp_scores<<<P, kBlock, 0, st>>>(V, Rm, 0);
-    for (int q = m; q < M; ++q) ST_TRY(step(q, 1, nullptr, false, -1, -1));
-    for (int q = 0; q < K; ++q) ST_TRY(step(rowe[(size_t)q], 1, nullptr, false, -1, -1));
-    if (max_swaps > 0) k_esp_xch_tbuild<<<dim3((unsigned)K, (unsigned)zg), kBlock, 0, st>>>(V, Rm, j, X->rowe, X->T);
-    HIP_TRY(hipGetLastError());
-    ST_TRY(clk.mark(kLoad));
-    int64_t t = 0;
-    int hbad = 0;
-    for (; t < max_swaps; ++t) {
-        k_esp_xch_pairs_edge<<<dim3((unsigned)K, (unsigned)chunks), kBlock, 0, st>>>(V, m, X->T, X->rowe, per, X->pv, X->pf);
-        k_esp_xch_argmax<<<1, kBlock, 0, st>>>(V, X->rowe, X->pv, X->pf, K * chunks, chunks, X->best);
-        HIP_TRY(hipGetLastError());
-        ST_TRY(clk.mark(kPairs));
-        EspXchBest b;
-        HIP_TRY(hipMemcpyAsync(&b, X->best, sizeof(b), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(&hbad, E->bad, sizeof(int), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        ST_TRY(clk.collect());
-        if (hbad) break;
-        if (b.val - 1.0 <= min_gain) { *converged = 1; break; }
-        ST_TRY(esp_xch_apply(rowe, in_sel, b.row, b.e, b.f));
-        out_idx[t] = b.e;
-        in_idx[t] = b.f;
-        ST_TRY(clk.mark(-1));
-        ST_TRY(step(b.e, -1, X->ratio + t, true, b.row, -1));
-        ST_TRY(step(b.f, +1, X->ratio + t, true, b.row, b.f));
-        HIP_TRY(hipGetLastError());
-    }
-    HIP_TRY(hipEventRecord(h->ev[1], st));
-    if (t > 0) HIP_TRY(hipMemcpyAsync(ratio, X->ratio, sizeof(double) * (size_t)t, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(&hbad, E->bad, sizeof(int), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    ST_TRY(clk.collect());
-    if (hbad)
-        return fail(MACHIP_NOT_CONVERGED, "exchange: 1 - s_e of a removal or 1 + s_f of an insertion is not positive, or no finite Delta (the selection holds a bridge of the graph, or lost numerically)");
-    *n_swaps = t;
-    for (int e = 0, q = 0; e < m; ++e) if (in_sel[(size_t)e]) sel_out[q++] = e;
-    if (t_ms) {
-        float ms = 0.0f;
-        HIP_TRY(hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
-        t_ms[0] = ms;
-        for (int q = 1; q < 6; ++q) t_ms[q] = clk.acc[q];
-    }
-    return MACHIP_OK;
+    return esp_exchange_edge(h, k, rowe, max_swaps, min_gain, sel_out, out_idx, in_idx, ratio, n_swaps, converged, t_ms);
 }
 
-// ---- the relaxation of GreedyESP's problem (esp_relax.h) ----
+// ---- the relaxation of GreedyESP's problem (esp_relax.h; its first call sets the device) ----
 
 int machip_esp_relax_eval(machip_esp* h, const double* x, double* F_out, double* grad_out) {
     if (!h || !F_out) return fail(MACHIP_BAD_ARG, "NULL handle or F_out");
-    ST_TRY(esp_relax_check_x(h, x));
-    ST_TRY(esp_relax_prepare(h));
-    EspRelax* r = h->rx;
-    if (h->m) HIP_TRY(hipMemcpyAsync(r->xa, x, sizeof(double) * (size_t)h->m, hipMemcpyHostToDevice, h->stream));
-    ST_TRY(esp_relax_eval_on(h, r->xa, grad_out != nullptr));
-    if (grad_out && h->m) HIP_TRY(hipMemcpyAsync(grad_out, h->s, sizeof(double) * (size_t)h->m, hipMemcpyDeviceToHost, h->stream));
-    double s3[3];
-    ST_TRY(esp_relax_read(h, 0, s3));
-    *F_out = s3[0];
-    return MACHIP_OK;
+    return esp_relax_eval(h, x, F_out, grad_out);
 }
 
 int machip_esp_relax_run(machip_esp* h, int64_t k, int max_iters, double gap_tol, double grad_tol, double* x_inout,
@@ -2146,61 +1691,18 @@ int machip_esp_relax_run(machip_esp* h, int64_t k, int max_iters, double gap_tol
     if (!h || !iters_out || !upper_out || max_iters < 0) return fail(MACHIP_BAD_ARG, "NULL handle or output, or max_iters < 0");
     *iters_out = 0;
     *upper_out = INFINITY;
-    if (h->edge_tree ? (int64_t)h->m + h->tr->seeds > kEspDenseMaxN : h->edge_relax ? h->m > kEspDenseMaxN : h->n > kEspDenseMaxN)
-        return esp_relax_prepare(h);      // (the limit's message, nothing allocated)
-    if (k <= 0 || k > h->m) return fail(MACHIP_BAD_ARG, "k must be in [1, m] (m = " + std::to_string(h->m) + " candidates)");
-    ST_TRY(esp_relax_check_x(h, x_inout));
-    ST_TRY(esp_relax_prepare(h));
-    EspRelax* r = h->rx;
-    hipStream_t st = h->stream;
-    const size_t mb = sizeof(double) * (size_t)h->m;
-    const int grid = std::max(1, std::min(kMaxGrid, (h->m + kBlock - 1) / kBlock));
-    HIP_TRY(hipMemcpyAsync(r->xa, x_inout, mb, hipMemcpyHostToDevice, st));
-    double u = INFINITY;
-    for (int it = 0; it < max_iters; ++it) {
-        const double gamma = 2.0 / ((double)it + 2.0);
-        ST_TRY(esp_relax_eval_on(h, r->xa, true));
-        ST_TRY(esp_relax_select(h, (long)k));
-        k_fw_final<<<grid, kBlock, 0, st>>>(h->s, r->xa, h->m, r->st, gamma, r->xb, nullptr, r->part);
-        double s3[3];
-        ST_TRY(esp_relax_read(h, grid, s3));
-        u = std::min(u, s3[1]);
-        if (f_traj) f_traj[it] = s3[0];
-        if (dual_traj) dual_traj[it] = s3[1];
-        if (gnorm_traj) gnorm_traj[it] = s3[2];
-        *iters_out = it + 1;
-        *upper_out = u;
-        if (s3[2] < grad_tol) break;                                  // (x stays the iterate the test was evaluated at)
-        if ((u - s3[0]) < gap_tol * std::fabs(s3[0])) break;          // (F >= 0; at F = 0 the test cannot fire)
-        std::swap(r->xa, r->xb);
-    }
-    HIP_TRY(hipMemcpyAsync(x_inout, r->xa, mb, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return MACHIP_OK;
+    return esp_relax_run(h, k, max_iters, gap_tol, grad_tol, x_inout, f_traj, dual_traj, gnorm_traj, iters_out, upper_out);
 }
 
 int machip_esp_relax_inner(machip_esp* h, const double* a, const double* b, double* out) {
     if (!h || !out || (h->m && (!a || !b))) return fail(MACHIP_BAD_ARG, "NULL handle, vector or output");
-    ST_TRY(esp_relax_prepare(h));
-    EspRelax* r = h->rx;
-    const size_t mb = sizeof(double) * (size_t)h->m;
-    const int grid = std::max(1, std::min(kMaxGrid, (h->m + kBlock - 1) / kBlock));      // (the grid of k_fw_final in machip_esp_relax_run)
-    if (h->m) {
-        HIP_TRY(hipMemcpyAsync(r->xa, a, mb, hipMemcpyHostToDevice, h->stream));
-        HIP_TRY(hipMemcpyAsync(r->xb, b, mb, hipMemcpyHostToDevice, h->stream));
-    }
-    k_relax_inner<<<grid, kBlock, 0, h->stream>>>(r->xa, r->xb, h->m, r->part);
-    k_relax_scalars<<<1, kBlock, 0, h->stream>>>(r->ldet, r->ld / kGjB, r->logdet0, r->part, grid, r->scal);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(out, r->scal + 3, sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    return MACHIP_OK;
+    return esp_relax_inner(h, a, b, out);
 }
 
 int machip_esp_relax_info(machip_esp* h, int32_t* info2) {
     if (!h || !info2) return fail(MACHIP_BAD_ARG, "NULL handle or output");
     info2[0] = h->edge_tree ? 2 : h->edge_relax ? 1 : 0;
-    info2[1] = h->rx ? h->rx->ld : h->edge_tree ? esp_edge_tree_ld((int64_t)h->m + h->tr->seeds) : h->edge_relax ? (std::max(h->m, 1) + kGjT - 1) / kGjT * kGjT : 0;
+    info2[1] = h->rx ? h->rx->ld : esp_relax_ld(h);
     return MACHIP_OK;
 }
 
@@ -2269,7 +1771,7 @@ int machip_eig_create(int device, int64_t n, int64_t n_fixed, const int32_t* fi,
         ST_TRY(h->alloc());
         h->adj = h->adj0; h->hdeg = h->hdeg0;
         ST_TRY(h->upload_graph());
-        if (!efree) HIP_TRY(hipMemcpyAsync(base->sig, base->sig0, sizeof(double) * (size_t)base->ld * (size_t)base->ld, hipMemcpyDeviceToDevice, base->stream));
+        if (!efree) ST_TRY(base->load_sigma0());
         base->pending = 0;
         ST_TRY(h->first_pair());
         return h->reset();

@@ -1,0 +1,130 @@
+"""Same-box A/B of two builds of the library on the GreedyESP family's OUTPUTS (tools/ab_lib.sh compares rates): every array the
+cases below return, bit for bit.
+
+    python tools/esp_ab_bits.py LIB_A LIB_B      (two builds, MACHIP_BUILD_OUT=; ESP_AB_BITS_OUT=DIR keeps A.npz and B.npz there)
+
+Each library runs the cases once in a fresh child process of its own (MACHIP_LIB is read at import), one child after the other,
+and saves what it got; the parent opens no device, compares with np.array_equal, and exits 1 at the first difference with the
+case and the array named.  Times (t_ms) are left out.  The cases are the smallest shapes at which each shared host driver can go
+wrong: the dense greedy (chain form at ld = 192 with 63 padding rows, fold 4, budgets [3, 11] and a restart; Gauss-Jordan form at
+ld = 128), the chain-free greedy (K = 40: one slice up to pick 31, two from 32 on; esp_free_split = 2; a grown history at K = 60),
+the tree greedy (5 seeds, carried over when the history grows), the dense exchange (folds inside rounds, LDS and global rows,
+max_swaps = 0), the edge-space exchange (chain; tree with the seeds as forced picks) and five Frank-Wolfe iterations in the three
+spaces, with relax_inner as a handle's first call."""
+import os
+import subprocess
+import sys
+import tempfile
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def cases():
+    sys.path.insert(0, ROOT)
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from esp_edge_tree_restatement import random_tree
+    from esp_exchange_restatement import naive_start
+    from esp_relax_restatement import chain_er
+    from mac_amd import _lib
+
+    out = {}
+
+    def put(case, **arrays):
+        for k, v in arrays.items():
+            out[f"{case}/{k}"] = np.asarray(v)
+
+    def put_select(case, r):
+        put(case, order=r[0], gain=r[1])
+
+    def put_xch(case, r):
+        put(case, **{k: r[k] for k in ("selection", "out", "in", "ratios", "swaps", "converged")})
+
+    chain, tree, chain60 = chain_er(130, 0.05, 1), random_tree(70, 5, 123, 7), chain_er(60, 0.05, 1)
+
+    h = _lib.Esp(*chain, fold=4)
+    assert h.info()["form"] == "chain" and h.info()["ld"] == 192
+    put_select("dense_chain/select_3_11", h.select([3, 11]))
+    assert h.info()["pending"] == 3
+    put("dense_chain", resist_after_11=h.weighted_resistances())
+    put_select("dense_chain/select_5", h.select([5]))
+
+    h = _lib.Esp(*tree, fold=4)
+    assert h.info()["form"] == "dense" and h.info()["ld"] == 128
+    put_select("dense_general/select_11", h.select([11]))
+
+    for tag, split in (("default", None), ("split2", 2)):
+        with _lib.default_options(esp_free_split=split):
+            h = _lib.Esp(*chain, matrix_free=True)
+        put_select(f"chain_free_{tag}/select_40", h.select([40]))
+        put(f"chain_free_{tag}", resist_after_40=h.weighted_resistances())
+        put_select(f"chain_free_{tag}/select_60", h.select([60]))
+
+    h = _lib.Esp(*tree, matrix_free="tree")
+    assert h.info()["seeds"] == 5
+    put("tree", resist_before=h.weighted_resistances())
+    put_select("tree/select_40", h.select([40]))
+    put("tree", resist_after_40=h.weighted_resistances())
+    put_select("tree/select_60", h.select([60]))
+
+    K = 28
+    start = naive_start(chain60, K)
+    h = _lib.Esp(*chain60, fold=4)
+    assert h.info()["ld"] == 64
+    put_xch("dense_exchange/lds", h.exchange(start, 10 * K))
+    with _lib.default_options(esp_xch_lds_kb=0):
+        put_xch("dense_exchange/global", h.exchange(start, 10 * K))
+    put_xch("dense_exchange/max_swaps_0", h.exchange(start, 0))
+    put("dense_exchange", resist_after=h.weighted_resistances())
+
+    h = _lib.Esp(*chain60, matrix_free=True, edge_relax=True)
+    put_xch("edge_exchange/chain", h.exchange_edge(start, 10 * K))
+    h = _lib.Esp(*tree, matrix_free="tree", edge_relax="tree")
+    Kt = len(tree[6]) // 3
+    put_xch("edge_exchange/tree", h.exchange_edge(naive_start(tree, Kt), 10 * Kt))
+
+    rng = np.random.default_rng(5)
+    for tag, g, kw in (("node", chain, {}), ("edge", chain, dict(matrix_free=True, edge_relax=True)),
+                       ("edge_tree", tree, dict(matrix_free="tree", edge_relax="tree"))):
+        m = len(g[6])
+        k = m // 3
+        a, b = rng.random(m), rng.random(m)
+        put(f"relax_{tag}", inner_first_call=_lib.Esp(*g, **kw).relax_inner(a, b))
+        h = _lib.Esp(*g, **kw)
+        r = h.relax_run(k, np.full(m, k / m), max_iters=5, gap_tol=0.0, grad_tol=0.0)
+        put(f"relax_{tag}/run", **r)
+        put(f"relax_{tag}", inner_after_run=h.relax_inner(a, b))
+    return out
+
+
+def main(argv):
+    if len(argv) == 3 and argv[1] == "--child":
+        np.savez(argv[2], **cases())
+        return 0
+    if len(argv) != 3:
+        print(__doc__)
+        return 2
+    got = []
+    keep = os.environ.get("ESP_AB_BITS_OUT") or tempfile.mkdtemp(prefix="esp_ab_bits_")      # (the saved arrays: A.npz, B.npz)
+    os.makedirs(keep, exist_ok=True)
+    for i, lib in enumerate(argv[1:]):
+        path = os.path.join(keep, f"{'AB'[i]}.npz")
+        env = dict(os.environ, MACHIP_LIB=os.path.abspath(lib))
+        subprocess.run([sys.executable, os.path.abspath(__file__), "--child", path], env=env, check=True)      # (one child at a time)
+        got.append(np.load(path))
+    A, B = got
+    if sorted(A.files) != sorted(B.files):
+        print("DIFFERENT: the two runs did not return the same arrays", sorted(set(A.files) ^ set(B.files)))
+        return 1
+    for name in A.files:
+        if A[name].shape != B[name].shape or not np.array_equal(A[name], B[name]):
+            print(f"DIFFERENT: case {name.rsplit('/', 1)[0]}, array {name.rsplit('/', 1)[1]}\n A = {A[name]}\n B = {B[name]}")
+            return 1
+        print(f"same  {name}  {A[name].dtype}{list(A[name].shape)}")
+    print(f"esp_ab_bits: {len(A.files)} arrays bit-identical between {argv[1]} and {argv[2]}")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main(sys.argv))
