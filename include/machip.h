@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define MACHIP_ABI_VERSION 16   /* 16: MACHIP_EIG_MATRIX_FREE (GreedyEig on a chain without a dense Sigma; options eig_free_rows, eig_free_split); 15: machip_eig_exchange (best-swap local search on lambda_2; option eig_xch_max_mb); 14: machip_esp_exchange_edge (the exchange in the candidates' space on MACHIP_ESP_EDGE_RELAX / MACHIP_ESP_EDGE_RELAX_TREE handles); 13: machip_esp_exchange (best-swap local search on the log tree count; options esp_xch_lds_kb, esp_xch_max_mb, esp_xch_profile); 12: MACHIP_ESP_EDGE_RELAX (the relaxation in the candidates' space on a chain-fixed graph; machip_esp_relax_info); 11: MACHIP_ESP_SPANNING_TREE (the matrix-free route of GreedyESP for any connected fixed graph; machip_esp_tree_plan, machip_esp_seeds); 10: MACHIP_ESP_MATRIX_FREE (GreedyESP on a chain without a dense Sigma, option esp_free_split); 9: the relaxation of GreedyESP's problem (machip_esp_relax_*); 8: GreedyEig handle (machip_eig_*); 7: GreedyESP handle (machip_esp_*); 6: machip_solve_stats.drift, machip_panel_plan fills 12 entries; 5: per-handle option table (machip_set_option), machip_comm_drop_ipc; 4: inter-process communicator */
+#define MACHIP_ABI_VERSION 17   /* 17: MACHIP_EIG_MATRIX_FREE_TREE (GreedyEig on any connected fixed graph without a dense Sigma; machip_eig_seeds); 16: MACHIP_EIG_MATRIX_FREE (GreedyEig on a chain without a dense Sigma; options eig_free_rows, eig_free_split); 15: machip_eig_exchange (best-swap local search on lambda_2; option eig_xch_max_mb); 14: machip_esp_exchange_edge (the exchange in the candidates' space on MACHIP_ESP_EDGE_RELAX / MACHIP_ESP_EDGE_RELAX_TREE handles); 13: machip_esp_exchange (best-swap local search on the log tree count; options esp_xch_lds_kb, esp_xch_max_mb, esp_xch_profile); 12: MACHIP_ESP_EDGE_RELAX (the relaxation in the candidates' space on a chain-fixed graph; machip_esp_relax_info); 11: MACHIP_ESP_SPANNING_TREE (the matrix-free route of GreedyESP for any connected fixed graph; machip_esp_tree_plan, machip_esp_seeds); 10: MACHIP_ESP_MATRIX_FREE (GreedyESP on a chain without a dense Sigma, option esp_free_split); 9: the relaxation of GreedyESP's problem (machip_esp_relax_*); 8: GreedyEig handle (machip_eig_*); 7: GreedyESP handle (machip_esp_*); 6: machip_solve_stats.drift, machip_panel_plan fills 12 entries; 5: per-handle option table (machip_set_option), machip_comm_drop_ipc; 4: inter-process communicator */
 
 typedef enum machip_status {
     MACHIP_OK = 0,
@@ -524,7 +524,8 @@ int machip_esp_exchange_edge(machip_esp* h, int64_t k, const int32_t* sel_in, in
  * replaces the running best only if it exceeds it by more than 1e-8).  Every reported lambda_2 satisfies the stop rule
  * ||L_e v - lambda v||_1 / ||L_e||_inf < 1e-8 (||v||_2 = 1), evaluated with the sparse Laplacian.  The fixed graph must be connected
  * (MACHIP_DISCONNECTED otherwise); size limits and flags as machip_esp_create, except that MACHIP_ESP_MATRIX_FREE is taken only together
- * with MACHIP_EIG_MATRIX_FREE and MACHIP_ESP_SPANNING_TREE not at all (MACHIP_BAD_ARG). */
+ * with MACHIP_EIG_MATRIX_FREE and MACHIP_ESP_SPANNING_TREE not at all (MACHIP_BAD_ARG; the spanning-tree route of GreedyEig has a flag of
+ * its own, MACHIP_EIG_MATRIX_FREE_TREE, and no size limit but memory). */
 typedef struct machip_eig machip_eig;
 /* flags of machip_eig_create only (machip_esp_create answers "unknown flags"), valid only as MACHIP_ESP_MATRIX_FREE |
  * MACHIP_EIG_MATRIX_FREE: GreedyEig without a dense Sigma (mac_amd/csrc/eig_free.h).  The fixed edges must be exactly the connected
@@ -540,6 +541,19 @@ typedef struct machip_eig machip_eig;
  * handle.  The stop rule is relative to ||L_e||_inf: on a long chain (lambda_2 / ||L||_inf ~ pi^2 / 4 n^2 < 1e-8 from n ~ 16 000 on) it
  * certifies little more than the sign of lambda_2 -- on this route as on the dense one. */
 #define MACHIP_EIG_MATRIX_FREE 64
+/* flag of machip_eig_create only (machip_esp_create answers "unknown flags"), valid only as MACHIP_ESP_MATRIX_FREE |
+ * MACHIP_EIG_MATRIX_FREE | MACHIP_EIG_MATRIX_FREE_TREE with fold = 0: the route above for ANY connected fixed graph
+ * (mac_amd/csrc/eig_free_tree.h).  machip_eig_create takes the spanning tree T and the r seeds of MACHIP_ESP_SPANNING_TREE itself (a
+ * caller's MACHIP_ESP_SPANNING_TREE stays refused): Sigma0(T)_ab = Rt[lca(a, b)] is applied to a batch by four sweeps over T in preorder
+ * (suffix sums, then a prefix along the Euler tour) -- a fixed number of launches whatever the depth of T --, the r fixed links outside
+ * T are the history's columns [0, r) before the first pick, and the picks follow: the history takes 8 ld (r + K) bytes, the batch
+ * arrays about 8 (6 ldv + 4 ld) ldq.  Both refusals of the chain route apply, with r named in the message; the spanning-tree plan's own
+ * arrive with their messages (a fixed graph that is not connected, links whose summed weight is not positive), all before a device is
+ * touched.  Nothing of size ld x ld exists.  The difference of suffix sums in the sweeps loses about n eps: it costs the
+ * preconditioner nothing that decides (every lambda_2 and pick is the sparse L_cur's).  The order of every sum depends on (ld, the
+ * tree, j, the batch, options eig_free_rows / eig_free_split) alone.  machip_eig_exchange answers MACHIP_BAD_ARG.  The stop rule's caveat
+ * above holds for chain-like trees. */
+#define MACHIP_EIG_MATRIX_FREE_TREE 128
 /* fold: as machip_esp_create (0 = 16; must be 0 with MACHIP_EIG_MATRIX_FREE); batch: columns solved together (1..4096; 0 = 512).
  * Builds Sigma0 (unless matrix-free) and the fixed graph's Fiedler pair. */
 int machip_eig_create(int device, int64_t n, int64_t n_fixed, const int32_t* fi, const int32_t* fj, const double* fw,
@@ -552,11 +566,14 @@ int machip_eig_select(machip_eig* h, int64_t k, int32_t* order_out, double* lamb
 int machip_eig_candidate_lambda2(machip_eig* h, double* out);
 /* the bounds u_e (m doubles; NaN for the selected) from the current Fiedler pair. */
 int machip_eig_candidate_bounds(machip_eig* h, double* out);
-/* info6 = {form (0 chain, 1 dense inverse, 2 chain without Sigma: MACHIP_EIG_MATRIX_FREE), leading dimension of Sigma, fold (form 2: 0),
- * batch, pending updates (form 2: the history's columns), picks of the last run};
+/* info6 = {form (0 chain, 1 dense inverse, 2 chain without Sigma: MACHIP_EIG_MATRIX_FREE, 3 spanning tree without Sigma:
+ * MACHIP_EIG_MATRIX_FREE_TREE), leading dimension of Sigma, fold (forms 2, 3: 0), batch, pending updates (form 2: the history's
+ * columns; form 3: r seeds + picks), picks of the last run};
  * beta_lambda2 = {beta (always 0), current lambda_2}; per pick of the last run (at most cap entries): candidates solved exactly and
  * operator applications (summed over the columns). */
 int machip_eig_info(machip_eig* h, int32_t* info6, double* beta_lambda2, int64_t cap, int32_t* solved_out, int32_t* applies_out);
+/* *seeds_out = the seeds r of a MACHIP_EIG_MATRIX_FREE_TREE handle (distinct fixed links - (n - 1)); 0 on every other handle. */
+int machip_eig_seeds(machip_eig* h, int64_t* seeds_out);
 /* Best-swap local search on lambda_2 (mac_amd/csrc/eig_exchange.h) from the k-edge selection sel_in (k distinct candidate
  * indices, any order).  With S the selection and L_S the fixed graph plus S, a round
  *   1. solves the K removal pairs (lambda_2(S \ e), v^-e), e in S, as columns of the batch solver (a removal is the candidate with

@@ -126,6 +126,7 @@ SIGNATURES = {
     "machip_eig_candidate_lambda2": (C.c_int, [C.c_void_p, _f64p]),
     "machip_eig_candidate_bounds": (C.c_int, [C.c_void_p, _f64p]),
     "machip_eig_info": (C.c_int, [C.c_void_p, _i32p, _f64p, C.c_int64, _i32p, _i32p]),
+    "machip_eig_seeds": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     "machip_eig_exchange": (C.c_int, [C.c_void_p, C.c_int64, _i32p, C.c_int64, C.c_double, _i32p, _i32p, _i32p, _f64p,
                                       C.POINTER(C.c_int64), C.POINTER(C.c_int32), _i32p, _f64p]),
 }
@@ -482,6 +483,7 @@ ESP_SPANNING_TREE = 8      # MACHIP_ESP_SPANNING_TREE (only together with ESP_MA
 ESP_EDGE_RELAX = 16        # MACHIP_ESP_EDGE_RELAX (only together with ESP_MATRIX_FREE alone: the chain)
 ESP_EDGE_RELAX_TREE = 32   # MACHIP_ESP_EDGE_RELAX_TREE (only as ESP_MATRIX_FREE | ESP_SPANNING_TREE | ESP_EDGE_RELAX_TREE)
 EIG_MATRIX_FREE = 64       # MACHIP_EIG_MATRIX_FREE (machip_eig_create only, and only as ESP_MATRIX_FREE | EIG_MATRIX_FREE)
+EIG_MATRIX_FREE_TREE = 128 # MACHIP_EIG_MATRIX_FREE_TREE (machip_eig_create only: ESP_MATRIX_FREE | EIG_MATRIX_FREE | EIG_MATRIX_FREE_TREE)
 
 
 def host_esp_tree(n, fi, fj, fw):
@@ -653,11 +655,18 @@ class Eig:
     matrix_free=True: chain-fixed graphs only -- no dense inverse; Sigma0 is applied by two scans and the picks stay in a history
     that ``select`` sizes for its budget (MACHIP_ESP_MATRIX_FREE | MACHIP_EIG_MATRIX_FREE, mac_amd/csrc/eig_free.h; process options
     "eig_free_rows", "eig_free_split").  Nothing is folded on that route: ``fold`` must stay None there (ValueError otherwise; the C
-    entry point gets 0); on the dense routes None is 16."""
+    entry point gets 0); on the dense routes None is 16.
+    matrix_free="tree": the same for any connected fixed graph -- Sigma0 of a spanning tree is applied by four sweeps over the tree,
+    the r fixed links outside it are the history's first r columns (MACHIP_EIG_MATRIX_FREE_TREE, mac_amd/csrc/eig_free_tree.h);
+    ``fold`` and ``dense_inverse`` are refused as on True."""
 
     def __init__(self, n, fi, fj, fw, ci, cj, cw, fold=None, batch=512, dense_inverse=False, device=0, *, matrix_free=False):
+        if not isinstance(matrix_free, (bool, np.bool_)) and not (isinstance(matrix_free, str) and matrix_free == "tree"):
+            raise ValueError(f'matrix_free must be False, True or "tree", not {matrix_free!r}')
         if matrix_free and fold is not None:
-            raise ValueError(f"matrix_free=True never folds: fold has no meaning on this route (got fold={fold!r}); leave it at None")
+            raise ValueError(f"matrix_free={matrix_free!r} never folds: fold has no meaning on this route (got fold={fold!r}); leave it at None")
+        if matrix_free and dense_inverse:
+            raise ValueError(f"matrix_free={matrix_free!r} keeps no inverse: it cannot be combined with dense_inverse=True")
         fold = 16 if fold is None else fold
         lib = load()
         require_device()
@@ -668,8 +677,8 @@ class Eig:
         h = C.c_void_p()
         check(lib.machip_eig_create(int(device), self.n, len(fw), p_i32(fi), p_i32(fj), p_f64(fw), self.m,
                                     p_i32(ci), p_i32(cj), p_f64(cw), 0 if matrix_free else int(fold), int(batch),
-                                    (ESP_DENSE_INVERSE if dense_inverse else 0) | (ESP_MATRIX_FREE | EIG_MATRIX_FREE if matrix_free else 0),
-                                    C.byref(h)))
+                                    (ESP_DENSE_INVERSE if dense_inverse else 0) | (ESP_MATRIX_FREE | EIG_MATRIX_FREE if matrix_free else 0)
+                                    | (EIG_MATRIX_FREE_TREE if isinstance(matrix_free, str) else 0), C.byref(h)))
         self._h = h
         self._lib = lib
 
@@ -722,16 +731,19 @@ class Eig:
                 "removal_solves": c[:, 2].copy(), "t_ms": t}
 
     def info(self):
-        """dict(form, ld, fold, batch, pending, beta, lambda2, solved[picks], applications[picks])."""
+        """dict(form = "chain" | "dense" | "chain_free" | "tree_free", ld, fold, batch, pending (tree_free: seeds + picks), seeds, beta,
+        lambda2, solved[picks], applications[picks])."""
         a = np.zeros(6, dtype=np.int32)
         b = np.zeros(2)
+        r = C.c_int64(0)
+        check(self._lib.machip_eig_seeds(self._h, C.byref(r)))
         check(self._lib.machip_eig_info(self._h, p_i32(a), p_f64(b), 0, None, None))
         k = int(a[5])
         solved = np.zeros(max(k, 1), dtype=np.int32)
         applies = np.zeros(max(k, 1), dtype=np.int32)
         check(self._lib.machip_eig_info(self._h, p_i32(a), p_f64(b), k, p_i32(solved), p_i32(applies)))
-        return dict(form=("chain", "dense", "chain_free")[a[0]], ld=int(a[1]), fold=int(a[2]), batch=int(a[3]), pending=int(a[4]),
-                    beta=float(b[0]), lambda2=float(b[1]), solved=solved[:k].copy(), applications=applies[:k].copy())
+        return dict(form=("chain", "dense", "chain_free", "tree_free")[a[0]], ld=int(a[1]), fold=int(a[2]), batch=int(a[3]), pending=int(a[4]),
+                    seeds=int(r.value), beta=float(b[0]), lambda2=float(b[1]), solved=solved[:k].copy(), applications=applies[:k].copy())
 
 
 class _stdout_to_stderr:

@@ -17,7 +17,8 @@
 // when  ||r||_1 / ||L_e||_inf < 1e-8  with ||x||_2 = 1 (the stop rule of the reference's CholeskyFiedlerSolver).  Every column
 // starts from the current Fiedler vector.  Per iteration three launches (k_eig_resid, k_eig_product, k_eig_rr) and one 4-byte
 // read (the number of columns still active).  On a MACHIP_EIG_MATRIX_FREE handle (form 2 of the machip_esp underneath: no Sigma) k_eig_z
-// and k_eig_product are replaced by the scans and history products of eig_free.h; everything else here is shared.
+// and k_eig_product are replaced by the scans and history products of eig_free.h (form 3, MACHIP_EIG_MATRIX_FREE_TREE: the sweeps over a
+// spanning tree of eig_free_tree.h in the place of the scans); everything else here is shared.
 #pragma once
 #include <algorithm>
 #include <chrono>
@@ -326,13 +327,13 @@ __global__ __launch_bounds__(kBlock) void k_eig_rr(EigView E, const double* __re
 }
 
 struct EigXch;      // eig_exchange.h: the exchange's candidate arrays, removal pairs and bound matrix, made by its first call
-struct EigFree;     // eig_free.h: the scan chunks and projection buffers of the route without Sigma (form 2 of the machip_esp underneath)
+struct EigFree;     // eig_free.h: the scan chunks and projection buffers of the routes without Sigma (forms 2, 3 of the machip_esp underneath)
 
 }  // namespace machip
 
 struct machip_eig;
 namespace machip {
-// eig_free.h -- form 2 only: z_e / c_e of the batch's columns, T = Sigma_cur Q, the winner's column into the history, its room
+// eig_free.h -- forms 2, 3 only: z_e / c_e of the batch's columns, T = Sigma_cur Q, the winner's column into the history, its room
 int eig_free_columns(machip_eig* h, int count);
 int eig_free_apply(machip_eig* h, int count);
 int eig_free_push(machip_eig* h);
@@ -359,7 +360,8 @@ struct machip_eig {
     std::vector<int> solved, applies;    // per pick of the last run
     std::vector<int> removal;            // per round of the last exchange: removal pairs solved (eig_exchange.h)
     machip::EigXch* xc = nullptr;
-    machip::EigFree* fr = nullptr;       // form 2 (MACHIP_EIG_MATRIX_FREE): no Sigma, the preconditioner of eig_free.h
+    machip::EigFree* fr = nullptr;       // forms 2, 3 (MACHIP_EIG_MATRIX_FREE): no Sigma, the preconditioner of eig_free.h / eig_free_tree.h
+    int seeds = 0;                       // form 3 (MACHIP_EIG_MATRIX_FREE_TREE): the history's leading columns, the fixed links outside the spanning tree
     const int *xcu = nullptr, *xcv = nullptr;      // while an exchange runs: its own candidate arrays (the m candidates, then
     const double* xcw = nullptr;                   // the negated copies of the selected ones); NULL: the greedy's
     std::vector<int> h_bc, h_conv;
@@ -374,7 +376,7 @@ struct machip_eig {
         return E;
     }
 
-    bool matrix_free() const { return base->form == machip::kEspFormFree; }
+    bool matrix_free() const { return base->form == machip::kEspFormFree || base->form == machip::kEspFormTree; }
 
     machip::EspView zview() const {      // what k_eig_z reads the candidates from
         machip::EspView V = base->view();
@@ -474,11 +476,11 @@ struct machip_eig {
         return MACHIP_OK;
     }
 
-    // state <- the fixed graph (Sigma0, no pending columns, its Fiedler pair)
+    // state <- the fixed graph (Sigma0, no pending columns -- form 3: the seeds' --, its Fiedler pair)
     int reset() {
         hipStream_t st = base->stream;
         if (!matrix_free()) HIP_TRY(hipMemcpyAsync(base->sig, base->sig0, sizeof(double) * (size_t)base->ld * (size_t)base->ld, hipMemcpyDeviceToDevice, st));
-        base->pending = 0;
+        base->pending = seeds;
         adj = adj0; hdeg = hdeg0;
         std::fill(sel.begin(), sel.end(), 0);
         ST_TRY(upload_graph());

@@ -16,11 +16,13 @@
 // same back-substitution in its second output form: base R[min(u, i)] - R[min(v, i)], Y = alpha[q, b] = cb[q] (Zb[u_b, q] - Zb[v_b, q])
 // (k_eigf_alpha), written column-major into Z; k_eigf_cc makes c_e.  No atomics; the order of every sum is a function of
 // (ld, j, the batch, options eig_free_rows / eig_free_split) alone.
+// On a spanning-tree handle (form 3, eig_free_tree.h) pass 1 is that file's four sweeps over the tree, the history starts with the r
+// seeds of esp_tree.h (j = r + picks) and the batch's z_e take their base from the same sweeps; passes 2 and 3 are shared.
 #pragma once
 #include <string>
 
 #include "eig.h"
-#include "esp_free.h"
+#include "esp_tree.h"
 
 namespace machip {
 
@@ -164,8 +166,9 @@ __global__ __launch_bounds__(kBlock) void k_eigf_alpha(EigView E, const double* 
 // ---- pass 3: C = base - Zb Y.  grid = (column groups, ld / 64); tile, quadrants and operands as k_eig_product with Zb in the place of
 // Sigma: A[i][k] = Zb[row i, column k] (16 consecutive doubles per k), B[k][j] = Y[k, col j].  Columns of Zb from j on are zeros, not
 // read.  ZFORM = false: T -= Zb Y (row-major; base = pass 1's T), groups whose columns have all retired skipped.  ZFORM = true: the
-// batch's z_e, column-major into Z, base R[min(u, i)] - R[min(v, i)] (node-0 terms 0).  Rows n'..ld are written as 0. ----
-template <bool ZFORM>
+// batch's z_e, column-major into Z, base R[min(u, i)] - R[min(v, i)] (node-0 terms 0), or with FROM_T (eig_free_tree.h) read from T,
+// where the sweeps over the spanning tree have left Sigma0 a_e.  Rows n'..ld are written as 0. ----
+template <bool ZFORM, bool FROM_T = false>
 __global__ __launch_bounds__(256) void k_eigf_back(EigView E, const double* __restrict__ R, const double* __restrict__ Zb, const double* __restrict__ Y,
                                                    int j, int count) {
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -206,7 +209,8 @@ __global__ __launch_bounds__(256) void k_eigf_back(EigView E, const double* __re
                     if (cl >= count) continue;
                     const int e = E.bc[cl];
                     double z = 0.0;
-                    if (e >= 0 && row < E.np) z = esp_free_sig0(R, E.cu[e], row) - esp_free_sig0(R, E.cv2[e], row) - acc[bi][bj][q];
+                    if (e >= 0 && row < E.np)
+                        z = (FROM_T ? E.T[(size_t)row * ldq + cl] : esp_free_sig0(R, E.cu[e], row) - esp_free_sig0(R, E.cv2[e], row)) - acc[bi][bj][q];
                     E.Z[(size_t)cl * ld + row] = z;
                 } else {
                     const size_t at = (size_t)row * ldq + cl;
@@ -251,12 +255,19 @@ inline size_t eig_free_part_elems(int K64, int ldq, int opt) {
     return std::max(y, (size_t)kEigFreeWgs * kGjT * kGjT);
 }
 
+// eig_free_tree.h -- form 3 only: the tables and S of the sweeps over the spanning tree, T = Sigma0(T) Q, the batch's z_e / c_e
+struct EigFreeTree;
+void eig_tree_release(EigFreeTree* G);
+int eig_tree_sweeps(machip_eig* h, int count, bool all);
+int eig_tree_columns(machip_eig* h, int count);
+
 // what the route keeps beside the batch arrays of machip_eig
 struct EigFree {
     int rows = 0, nchunks = 0, split = 0;      // scan chunks; option eig_free_split when the handle was made (0 = automatic)
     double *cs = nullptr, *cu = nullptr;       // the chunks' sums (nchunks x ldq each)
     double *Y = nullptr, *part = nullptr;      // the projection (K64 x ldq) and the slices' partial tiles
     int k64 = 0;                               // history columns Y / part are sized for
+    EigFreeTree* tree = nullptr;               // form 3: the spanning tree in the place of the chain (cs / cu: its row and tour chunks' sums)
 };
 
 // Bytes of the batch arrays of a form-2 handle (machip_eig::alloc plus the chunks' sums), refused at create when they do not fit.
@@ -286,31 +297,38 @@ inline int eig_free_init(machip_eig* h) {
 
 inline void eig_free_release(EigFree* F) {
     if (!F) return;
+    eig_tree_release(F->tree);
     void* bufs[] = {F->cs, F->cu, F->Y, F->part};
     for (void* q : bufs) if (q) (void)hipFree(q);
     delete F;
 }
 
-// The history (esp_history_reserve: Zb, cb) and the projection buffers for K picks.  Grows, never shrinks; a K that does not fit is
-// refused before anything is freed or allocated.
+// The history (esp_history_reserve: Zb, cb) and the projection buffers for K picks after the handle's r seeds (form 3; r = 0 on the
+// chain).  Grows, never shrinks; a K that does not fit is refused before anything is freed or allocated.  Form 3: esp_tree_prepare
+// runs the seeds through the history at its first call and copies their columns when the history grows.
 inline int eig_free_reserve(machip_eig* h, int64_t K) {
     EigFree* F = h->fr;
     machip_esp* base = h->base;
-    const int64_t K64 = (K + kGjT - 1) / kGjT * kGjT;
+    const EspTreeState* t = F->tree ? base->tr : nullptr;
+    const int64_t cols = (int64_t)h->seeds + K;
+    const int64_t K64 = (cols + kGjT - 1) / kGjT * kGjT;
     if (K64 > F->k64) {
         const double ld = (double)base->ld;
-        const double hist = (size_t)K > base->zcap ? 8.0 * ld * (double)K : 0.0;
+        const bool grow = (size_t)cols > base->zcap;
+        const double hist = grow ? 8.0 * ld * (double)cols : 0.0;
         const double proj = 8.0 * ((double)K64 * h->ldq + (double)eig_free_part_elems((int)std::min<int64_t>(K64, INT_MAX), h->ldq, F->split));
-        const double back = (size_t)K > base->zcap ? 8.0 * ld * (double)base->zcap : 0.0;
+        const double back = grow && !(t && t->seeded && t->seeds > 0) ? 8.0 * ld * (double)base->zcap : 0.0;      // (seeded columns are copied: old and new coexist)
         size_t fr = 0, tot = 0;
         HIP_TRY(hipMemGetInfo(&fr, &tot));
         if (hist + proj > (double)fr + back - 8.0 * ld * kEspFreeMaxSplit - 268435456.0)
-            return fail(MACHIP_BAD_ARG, "the matrix-free history does not fit in device memory: n = " + std::to_string(h->n) + ", K = " +
-                                            std::to_string((long long)K) + " asks for 8 ld K = " + std::to_string((unsigned long long)(8.0 * ld * (double)K)) +
-                                            " bytes (ld = " + std::to_string(base->ld) + ") and " + std::to_string((unsigned long long)proj) +
-                                            " bytes of projections, " + std::to_string((unsigned long long)fr) + " bytes are free");
+            return fail(MACHIP_BAD_ARG, "the matrix-free history does not fit in device memory: n = " + std::to_string(h->n) + ", K = " + std::to_string((long long)K) +
+                                            (t ? " and r = " + std::to_string(h->seeds) + " seeds ask for 8 ld (r + K) = " : " asks for 8 ld K = ") +
+                                            std::to_string((unsigned long long)(8.0 * ld * (double)cols)) + " bytes (ld = " + std::to_string(base->ld) + ") and " +
+                                            std::to_string((unsigned long long)proj) + " bytes of projections, " + std::to_string((unsigned long long)fr) +
+                                            " bytes are free");
     }
-    ST_TRY(esp_history_reserve(base, 0, false, K));
+    if (t) ST_TRY(esp_tree_prepare(base, K));
+    else ST_TRY(esp_history_reserve(base, 0, false, K));
     if (K64 <= F->k64) return MACHIP_OK;
     HIP_TRY(hipStreamSynchronize(base->stream));
     if (F->Y) (void)hipFree(F->Y);
@@ -325,6 +343,7 @@ inline int eig_free_reserve(machip_eig* h, int64_t K) {
 // z_e = Sigma_cur a_e and c_e of the columns bc[0..count) into Z / cc
 inline int eig_free_columns(machip_eig* h, int count) {
     const EigFree* F = h->fr;
+    if (F->tree) return eig_tree_columns(h, count);
     const machip_esp* base = h->base;
     const EigView E = h->view();
     hipStream_t st = base->stream;
@@ -345,10 +364,14 @@ inline int eig_free_apply(machip_eig* h, int count) {
     const EigView E = h->view();
     hipStream_t st = base->stream;
     const int cg = (count + kGjT - 1) / kGjT;
-    const dim3 sg(cg, F->nchunks);
-    k_eigf_scan<0><<<sg, kWave, 0, st>>>(E, base->R, F->cs, F->cu, F->rows, count);
-    k_eigf_scan<1><<<sg, kWave, 0, st>>>(E, base->R, F->cs, F->cu, F->rows, count);
-    k_eigf_scan<2><<<sg, kWave, 0, st>>>(E, base->R, F->cs, F->cu, F->rows, count);
+    if (F->tree) {
+        ST_TRY(eig_tree_sweeps(h, count, false));
+    } else {
+        const dim3 sg(cg, F->nchunks);
+        k_eigf_scan<0><<<sg, kWave, 0, st>>>(E, base->R, F->cs, F->cu, F->rows, count);
+        k_eigf_scan<1><<<sg, kWave, 0, st>>>(E, base->R, F->cs, F->cu, F->rows, count);
+        k_eigf_scan<2><<<sg, kWave, 0, st>>>(E, base->R, F->cs, F->cu, F->rows, count);
+    }
     const int j = base->pending;
     if (j == 0) return MACHIP_OK;
     const int jt = (j + kGjT - 1) / kGjT, j64 = jt * kGjT, ldp = cg * kGjT;

@@ -26,6 +26,7 @@
 #include "eig.h"
 #include "eig_exchange.h"
 #include "eig_free.h"
+#include "eig_free_tree.h"
 
 namespace machip {
 thread_local std::string g_err;
@@ -1732,24 +1733,28 @@ int machip_eig_create(int device, int64_t n, int64_t n_fixed, const int32_t* fi,
     if (fold == 0) fold = kEigDefaultFold;
     if (batch == 0) batch = kEigDefaultBatch;
     if (batch < 1 || batch > kEigMaxBatch) return fail(MACHIP_BAD_ARG, "batch must be in [1, 4096]");
-    const bool efree = (flags & MACHIP_EIG_MATRIX_FREE) != 0;
+    const bool efree = (flags & MACHIP_EIG_MATRIX_FREE) != 0, etree = (flags & MACHIP_EIG_MATRIX_FREE_TREE) != 0;
     if ((flags & MACHIP_ESP_MATRIX_FREE) && !efree)
         return fail(MACHIP_BAD_ARG, "GreedyEig solves against the dense inverse: MACHIP_ESP_MATRIX_FREE is not available here");
     if (flags & MACHIP_ESP_SPANNING_TREE)
         return fail(MACHIP_BAD_ARG, "GreedyEig solves against the dense inverse: MACHIP_ESP_SPANNING_TREE is not available here");
-    if (efree) {      // the route without Sigma (eig_free.h): every refusal here and in machip_esp_create is decided before a device is touched
+    if (etree && !(efree && (flags & MACHIP_ESP_MATRIX_FREE)))
+        return fail(MACHIP_BAD_ARG, "MACHIP_EIG_MATRIX_FREE_TREE puts GreedyEig on the spanning-tree handle: it is valid only as MACHIP_ESP_MATRIX_FREE | MACHIP_EIG_MATRIX_FREE | MACHIP_EIG_MATRIX_FREE_TREE");
+    if (efree) {      // the routes without Sigma (eig_free.h, eig_free_tree.h): every refusal here and in machip_esp_create is decided before a device is touched
         if (!(flags & MACHIP_ESP_MATRIX_FREE))
             return fail(MACHIP_BAD_ARG, "MACHIP_EIG_MATRIX_FREE puts GreedyEig on the chain-free handle: it is valid only as MACHIP_ESP_MATRIX_FREE | MACHIP_EIG_MATRIX_FREE");
         if (flags & MACHIP_ESP_DENSE_INVERSE)
             return fail(MACHIP_BAD_ARG, "MACHIP_EIG_MATRIX_FREE keeps no Sigma: it cannot be combined with MACHIP_ESP_DENSE_INVERSE");
-        if (flags & ~(MACHIP_ESP_MATRIX_FREE | MACHIP_EIG_MATRIX_FREE))
+        if (flags & ~(MACHIP_ESP_MATRIX_FREE | MACHIP_EIG_MATRIX_FREE | MACHIP_EIG_MATRIX_FREE_TREE))
             return fail(MACHIP_BAD_ARG, "unknown flags: MACHIP_EIG_MATRIX_FREE is valid only as MACHIP_ESP_MATRIX_FREE | MACHIP_EIG_MATRIX_FREE");
         if (fold_given != 0)      // (an argument that would be ignored is refused, not dropped)
             return fail(MACHIP_BAD_ARG, "MACHIP_EIG_MATRIX_FREE never folds: fold has no meaning on this route and must be 0");
         fold = 0;
     }
     machip_esp* base = nullptr;
-    ST_TRY(machip_esp_create(device, n, n_fixed, fi, fj, fw, m, ci, cj, cw, fold, flags & ~MACHIP_EIG_MATRIX_FREE, &base));
+    // (the tree route asks for the spanning-tree handle itself: a caller's MACHIP_ESP_SPANNING_TREE stays refused above)
+    ST_TRY(machip_esp_create(device, n, n_fixed, fi, fj, fw, m, ci, cj, cw, fold,
+                             (flags & ~(MACHIP_EIG_MATRIX_FREE | MACHIP_EIG_MATRIX_FREE_TREE)) | (etree ? MACHIP_ESP_SPANNING_TREE : 0), &base));
     if (base->beta != 0.0) {
         machip_esp_destroy(base);
         return fail(MACHIP_DISCONNECTED, "GreedyEig needs a connected fixed graph (lambda_2 of the fixed graph is 0 otherwise)");
@@ -1766,13 +1771,21 @@ int machip_eig_create(int device, int64_t n, int64_t n_fixed, const int32_t* fi,
     }
     h->hci.assign(ci, ci + m); h->hcj.assign(cj, cj + m); h->hcw.assign(cw, cw + m);
     h->sel.assign((size_t)m, 0);
+    h->seeds = etree ? base->tr->seeds : 0;
     auto body = [&]() -> int {
-        if (efree) ST_TRY(eig_free_init(h));      // (its memory check comes before the batch arrays are allocated)
+        if (etree) {      // the plan machip_esp_create has just made its tables from: the same arguments, the same plan
+            EspTreePlan tplan;
+            ST_TRY(esp_tree_plan(n, n_fixed, fi, fj, fw, tplan));
+            ST_TRY(eig_tree_init(h, tplan));
+        } else if (efree) {
+            ST_TRY(eig_free_init(h));      // (its memory check comes before the batch arrays are allocated)
+        }
         ST_TRY(h->alloc());
         h->adj = h->adj0; h->hdeg = h->hdeg0;
         ST_TRY(h->upload_graph());
         if (!efree) ST_TRY(base->load_sigma0());
-        base->pending = 0;
+        if (etree) ST_TRY(eig_free_reserve(h, 0));      // the seeds into the history: the fixed graph's own pair needs them
+        base->pending = h->seeds;
         ST_TRY(h->first_pair());
         return h->reset();
     };
@@ -1830,6 +1843,12 @@ int machip_eig_candidate_bounds(machip_eig* h, double* out) {
     std::vector<double> u;
     ST_TRY(h->bounds(u));
     for (int e = 0; e < h->m; ++e) out[e] = h->sel[(size_t)e] ? NAN : u[(size_t)e];
+    return MACHIP_OK;
+}
+
+int machip_eig_seeds(machip_eig* h, int64_t* seeds_out) {
+    if (!h || !seeds_out) return fail(MACHIP_BAD_ARG, "NULL handle or output");
+    *seeds_out = h->seeds;
     return MACHIP_OK;
 }
 

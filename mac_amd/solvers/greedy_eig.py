@@ -17,6 +17,13 @@ Size limits as GreedyESP: 32 768 poses when the fixed edges are exactly the chai
 picks are a low-rank correction kept as a history of n x k doubles, and one solver iteration costs 4 n j B flop plus three passes
 over the batch instead of 2 n^2 B (mac_amd/csrc/eig_free.h).  No limit on the number of poses but memory; the
 picks obey the same rule and stop rule, decided by the sparse Laplacian.  ``exchange`` is not available on that route.
+
+``matrix_free="tree"`` is that route for ANY connected fixed graph -- a chain plus kept closures, odometry whose indices are not
+consecutive, a landmark spur, merged sessions: a spanning tree T of the fixed graph takes the chain's place (its inverse applied to
+a batch is four sweeps over T in preorder, a fixed number of launches whatever its depth), and the r fixed links outside T enter the
+history as its first r columns before the first pick (mac_amd/csrc/eig_free_tree.h).  Nothing of size n x n
+exists, so the 16 384-pose limit of the dense route is gone; ``info()`` reports ``form="tree_free"``, ``seeds=r`` and
+``pending = r + picks``.  Worth it while r + picks stays well below n.
 """
 from __future__ import annotations
 
@@ -44,17 +51,21 @@ def selection_indices(selection, m):
 
 class GreedyEig:
     def __init__(self, odom_measurements: List[Edge], lc_measurements: List[Edge], num_poses: int, *, device: int = 0,
-                 batch: int = 512, fold: Optional[int] = None, dense_inverse: bool = False, matrix_free: bool = False):
+                 batch: int = 512, fold: Optional[int] = None, dense_inverse: bool = False, matrix_free=False):
         """Arguments as mac/solvers/greedy_eig.py of the reference, plus keyword-only ``device`` (GPU ordinal), ``batch``
         (candidates solved together, 1..4096), ``fold`` (picks kept as a low-rank block before they are folded into the
         inverse, 1..256; None: 16), ``dense_inverse`` (build the inverse by dense Gauss-Jordan even for a chain: cross-checks) and
         ``matrix_free`` (no inverse: the fixed edges must be exactly the chain (i, i+1); nothing is folded, so ``fold`` must be
-        left at None -- any value is a ValueError: an argument without a meaning is refused, not ignored -- as is ``dense_inverse``).
-        Raises Disconnected when the fixed graph is not connected."""
+        left at None -- any value is a ValueError: an argument without a meaning is refused, not ignored -- as is ``dense_inverse``;
+        ``matrix_free="tree"``: the same for any connected fixed graph, over a spanning tree and its seeds; any other value that is
+        not a bool is a ValueError).
+        Raises Disconnected when the fixed graph is not connected (``matrix_free="tree"``: the spanning-tree plan's own refusal)."""
+        if not isinstance(matrix_free, (bool, np.bool_)) and not (isinstance(matrix_free, str) and matrix_free == "tree"):
+            raise ValueError(f'matrix_free must be False, True or "tree", not {matrix_free!r}')
         if matrix_free and fold is not None:
-            raise ValueError(f"matrix_free=True never folds: fold has no meaning on this route (got fold={fold!r}); leave it at None")
+            raise ValueError(f"matrix_free={matrix_free!r} never folds: fold has no meaning on this route (got fold={fold!r}); leave it at None")
         if matrix_free and dense_inverse:
-            raise ValueError("matrix_free=True keeps no inverse: it cannot be combined with dense_inverse=True")
+            raise ValueError(f"matrix_free={matrix_free!r} keeps no inverse: it cannot be combined with dense_inverse=True")
         self.L_odom = weight_graph_lap_from_edge_list(odom_measurements, num_poses)
         self.num_poses = num_poses
         self.odom_measurements = odom_measurements
@@ -64,7 +75,7 @@ class GreedyEig:
         self.edge_list = np.stack([ci, cj], axis=1).astype(np.int64).reshape(-1, 2)
         fi, fj, fw = edges_to_arrays(odom_measurements)
         self._dev = _lib.Eig(num_poses, fi, fj, fw, ci, cj, cw, fold=fold, batch=batch, dense_inverse=dense_inverse, device=device,
-                             matrix_free=bool(matrix_free))
+                             matrix_free=matrix_free if isinstance(matrix_free, str) else bool(matrix_free))
         self.last_lambda2: Optional[np.ndarray] = None      # lambda_2 after every pick of the last run
         self.last_times: Optional[np.ndarray] = None        # seconds from the start of the last run until each pick
 
@@ -134,6 +145,6 @@ class GreedyEig:
         return self._dev.candidate_bounds()
 
     def info(self) -> dict:
-        """form ("chain" / "dense" / "chain_free"), ld, fold, batch, pending, beta, lambda2 (current), and per pick of the last run:
+        """form ("chain" / "dense" / "chain_free" / "tree_free"), ld, fold, batch, pending, seeds, beta, lambda2 (current), and per pick of the last run:
         ``solved`` (candidates solved exactly) and ``applications`` (operator applications summed over the columns)."""
         return self._dev.info()

@@ -1,10 +1,12 @@
 """GreedyEig, dense chain form against the matrix-free route (mac_amd/csrc/eig_free.h): one JSON line per route
 and one per pair, both routes of a pair in this one process.
 
-    python tools/eig_free_time.py [case ...]      cases: intel10 intel50 city20 (default: all three)
+    python tools/eig_free_time.py [case ...]      cases: intel10 intel50 city20 (default: all three); intel_kept50 city_kept50
 
 intel10 / intel50: subset(k) on the intel pose graph with k = 10 % / 50 % of the candidates.  city20: the first 20 picks of
-city10000.  Per route: build_ms = wall time of the constructor, select_ms = wall time of subset(k), ms per pick, candidates solved
+city10000.  intel_kept50 / city_kept50 (the spanning-tree route, mac_amd/csrc/eig_free_tree.h, DESIGN section 22, against the dense
+general form): the same graphs with their first 50 closures moved to the fixed list, k = 10 % of the remaining candidates / 20.
+Per route: build_ms = wall time of the constructor, select_ms = wall time of subset(k), ms per pick, candidates solved
 exactly and operator applications per solved candidate as GreedyEig.info() reports them.  Per pair: the speedup of the matrix-free
 route, whether the picks are the same, and the largest difference of lambda_2 after a pick.
 """
@@ -51,19 +53,20 @@ def one(case, n, fixed, cand, K, matrix_free):
     return row, np.nonzero(sol)[0], lam
 
 
-def pair(case, name, k_of):
+def pair(case, name, k_of, kept=0):
     n, fixed, cand = pose_graph(name)
+    fixed, cand = fixed + cand[:kept], cand[kept:]
     K = k_of(len(cand))
     d, sd, ld_ = one(case, n, fixed, cand, K, False)
-    f, sf, lf = one(case, n, fixed, cand, K, True)
-    print(json.dumps(dict(case=case, pair="dense / matrix_free", picks=K, history_over_ld=round(K / d["ld"], 3),
+    f, sf, lf = one(case, n, fixed, cand, K, "tree" if kept else True)
+    print(json.dumps(dict(case=case, pair="dense / matrix_free", picks=K, history_over_ld=round((kept + K) / d["ld"], 3),
                           select_speedup=round(d["select_ms"] / f["select_ms"], 2), build_speedup=round(d["build_ms"] / f["build_ms"], 2),
                           same_picks=bool(np.array_equal(sd, sf)), max_lambda2_difference=float(np.max(np.abs(ld_ - lf))),
                           applications_per_solved=[d["applications_per_solved"], f["applications_per_solved"]])), flush=True)
 
 
 if __name__ == "__main__":
-    for mf in (False, True):      # (HIP context and code objects of both routes: not build_ms)
+    for mf in (False, True, "tree"):      # (HIP context and code objects of every route: not build_ms)
         GreedyEig([Edge(0, 1, 1.0), Edge(1, 2, 1.0)], [Edge(0, 2, 1.0)], 3, matrix_free=mf).subset(1)
     for c in sys.argv[1:] or ["intel10", "intel50", "city20"]:
         if c == "intel10":
@@ -72,5 +75,9 @@ if __name__ == "__main__":
             pair(c, "intel", lambda m: int(0.5 * m))
         elif c == "city20":
             pair(c, "city10000", lambda m: 20)
+        elif c == "intel_kept50":
+            pair(c, "intel", lambda m: int(0.1 * m), kept=50)
+        elif c == "city_kept50":
+            pair(c, "city10000", lambda m: 20, kept=50)
         else:
             raise SystemExit(f"unknown case {c}")
