@@ -18,7 +18,8 @@
 // starts from the current Fiedler vector.  Per iteration three launches (k_eig_resid, k_eig_product, k_eig_rr) and one 4-byte
 // read (the number of columns still active).  On a MACHIP_EIG_MATRIX_FREE handle (form 2 of the machip_esp underneath: no Sigma) k_eig_z
 // and k_eig_product are replaced by the scans and history products of eig_free.h (form 3, MACHIP_EIG_MATRIX_FREE_TREE: the sweeps over a
-// spanning tree of eig_free_tree.h in the place of the scans); everything else here is shared.
+// spanning tree of eig_free_tree.h in the place of the scans): machip_eig::columns / apply / push, which alone ask for the form
+// (eig_routes.h, with the handle's creation).  The rest is shared, with eig_exchange.h too: scan, push_column, adopt_pair.
 #pragma once
 #include <algorithm>
 #include <chrono>
@@ -91,6 +92,11 @@ __global__ __launch_bounds__(kBlock) void k_eig_z(EspView V, const double* __res
         const double s = (u >= 0 ? esp_z_entry(V, S, u, v, j, alpha, u) : 0.0) - (v >= 0 ? esp_z_entry(V, S, u, v, j, alpha, v) : 0.0);
         cdst[b] = V.cw[e] / (1.0 + V.cw[e] * s);
     }
+}
+
+// the dense routes' columns (machip_eig::columns): z_e, c_e of the batch against Sigma and the pending block
+inline void eig_dense_columns(const machip_esp* base, const EspView& V, const int* bc, int count, double* Z, double* cc) {
+    k_eig_z<<<dim3((base->ld + kBlock - 1) / kBlock, count), kBlock, 0, base->stream>>>(V, base->sig, base->pending, bc, Z, cc);
 }
 
 // ---- every column starts from v.  grid = (ceil(n / 256), columns) ----
@@ -326,18 +332,26 @@ __global__ __launch_bounds__(kBlock) void k_eig_rr(EigView E, const double* __re
     if (tid == 0) { E.hasp[b] = 1; E.iters[b] += 1; }
 }
 
+// the dense routes' application (machip_eig::apply): T = Sigma Q, then the step with the pending block's correction
+inline void eig_dense_apply(const machip_esp* base, const EigView& E, int count) {
+    k_eig_product<<<dim3((count + kGjT - 1) / kGjT, base->ld / kGjT), 256, 0, base->stream>>>(base->sig, E, count);
+    k_eig_rr<<<count, kBlock, 0, base->stream>>>(E, base->Zb, base->cb, base->pending);
+}
+
+// What the bounded candidate scan (machip_eig::scan) of a pick, or of the rows of an exchange round, has established so far
+struct EigScan {
+    std::vector<int> ord, last;      // the candidates in decreasing order of their bound; those of the last batch solved (still in X)
+    double top = -INFINITY;          // the largest value solved
+    int solved = 0;                  // candidates solved
+    int resident_column(int e) const {      // the column of X that holds e's vector, -1 when e was not in the last batch
+        const auto it = std::find(last.begin(), last.end(), e);
+        return it == last.end() ? -1 : (int)(it - last.begin());
+    }
+};
+
 struct EigXch;      // eig_exchange.h: the exchange's candidate arrays, removal pairs and bound matrix, made by its first call
 struct EigFree;     // eig_free.h: the scan chunks and projection buffers of the routes without Sigma (forms 2, 3 of the machip_esp underneath)
 
-}  // namespace machip
-
-struct machip_eig;
-namespace machip {
-// eig_free.h -- forms 2, 3 only: z_e / c_e of the batch's columns, T = Sigma_cur Q, the winner's column into the history, its room
-int eig_free_columns(machip_eig* h, int count);
-int eig_free_apply(machip_eig* h, int count);
-int eig_free_push(machip_eig* h);
-int eig_free_reserve(machip_eig* h, int64_t K);
 }  // namespace machip
 
 // ---- the handle (include/machip.h: machip_eig) ----
@@ -364,7 +378,7 @@ struct machip_eig {
     int seeds = 0;                       // form 3 (MACHIP_EIG_MATRIX_FREE_TREE): the history's leading columns, the fixed links outside the spanning tree
     const int *xcu = nullptr, *xcv = nullptr;      // while an exchange runs: its own candidate arrays (the m candidates, then
     const double* xcw = nullptr;                   // the negated copies of the selected ones); NULL: the greedy's
-    std::vector<int> h_bc, h_conv;
+    std::vector<int> h_conv;
     std::vector<double> h_lam;
 
     machip::EigView view() const {
@@ -377,6 +391,10 @@ struct machip_eig {
     }
 
     bool matrix_free() const { return base->form == machip::kEspFormFree || base->form == machip::kEspFormTree; }
+
+    // What a route is (eig_routes.h, one switch on the form each): room for K picks; z_e, c_e of the columns bc[0..count) into Z / cc;
+    // one application and step of the batch (T = Sigma_cur Q, k_eig_rr); `best`, just polished in column 0, joins the block or the history.
+    int reserve(int64_t K); int columns(int count); int apply(int count); int push(int best);
 
     machip::EspView zview() const {      // what k_eig_z reads the candidates from
         machip::EspView V = base->view();
@@ -441,13 +459,8 @@ struct machip_eig {
         hipStream_t st = base->stream;
         HIP_TRY(hipMemcpyAsync(bc, bcand, sizeof(int) * (size_t)count, hipMemcpyHostToDevice, st));
         const EigView E = view();
-        const EspView V = zview();
-        const int zg = (base->ld + kBlock - 1) / kBlock;
-        const bool mf = matrix_free();
-        if (mf) ST_TRY(eig_free_columns(this, count));
-        else k_eig_z<<<dim3(zg, count), kBlock, 0, st>>>(V, base->sig, base->pending, bc, Z, cc);
+        ST_TRY(columns(count));
         k_eig_init<<<dim3((n + kBlock - 1) / kBlock, count), kBlock, 0, st>>>(E, vstart);
-        const dim3 pg((count + kGjT - 1) / kGjT, base->ld / kGjT);
         for (int it = 0; it <= kEigMaxIter + 1; ++it) {
             int act = 0;
             HIP_TRY(hipMemsetAsync(nactive, 0, sizeof(int), st));
@@ -456,13 +469,7 @@ struct machip_eig {
             HIP_TRY(hipStreamSynchronize(st));
             if (act == 0) break;
             if (napp) *napp += act;
-            if (mf) {       // the history's correction is in T already: only the column's own term is left for k_eig_rr
-                ST_TRY(eig_free_apply(this, count));
-                k_eig_rr<<<count, kBlock, 0, st>>>(E, nullptr, nullptr, 0);
-            } else {
-                k_eig_product<<<pg, 256, 0, st>>>(base->sig, E, count);
-                k_eig_rr<<<count, kBlock, 0, st>>>(E, base->Zb, base->cb, base->pending);
-            }
+            ST_TRY(apply(count));
         }
         HIP_TRY(hipGetLastError());
         h_lam.resize((size_t)count); h_conv.resize((size_t)count);
@@ -520,83 +527,80 @@ struct machip_eig {
         return MACHIP_OK;
     }
 
-    // lambda_2(L_cur + e) of every unselected candidate (NaN for the selected), no pruning
-    int all_lambda2(double* out) {
-        std::vector<int> list;
-        for (int e = 0; e < m; ++e) {
-            if (sel[(size_t)e]) out[e] = NAN;
-            else list.push_back(e);
-        }
-        for (size_t q = 0; q < list.size(); q += (size_t)batch) {
-            const int cnt = (int)std::min(list.size() - q, (size_t)batch);
-            ST_TRY(solve_batch(list.data() + q, cnt, vcur, nullptr));
-            for (int b = 0; b < cnt; ++b) out[list[q + (size_t)b]] = h_lam[(size_t)b];
+    // dense handles: the column of candidate *cand (on the device; an index into zview()'s) joins the pending block, folded when full
+    void push_column(const int* cand) {
+        const int j = base->pending;
+        machip::eig_dense_columns(base, zview(), cand, 1, base->Zb + (size_t)j * (size_t)base->ld, base->cb + j);
+        base->pending = j + 1;
+        if (base->pending == base->fold) { base->fold_into(base->sig, base->pending); base->pending = 0; }
+    }
+
+    // the pair of L_cur + candidate `cand` (-1: none), polished from vstart (the next bounds are only as tight as it), becomes current
+    int adopt_pair(int cand, const double* vstart, int* napp) {
+        ST_TRY(solve_batch(&cand, 1, vstart, napp, true));
+        HIP_TRY(hipMemcpyAsync(vcur, X, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, base->stream));
+        lamcur = h_lam[0];
+        return MACHIP_OK;
+    }
+
+    // The bounded scan: the unselected candidates in decreasing order of their bound u (a stable sort), solved from vstart batch after
+    // batch until a batch's first bound is below max(floor, s.top): a value already established.  report(candidate, value) per solve.
+    template <class Report>
+    int scan(machip::EigScan& s, const std::vector<double>& u, double floor, const double* vstart, int* napp, Report report) {
+        s.ord.clear();
+        for (int e = 0; e < m; ++e) if (!sel[(size_t)e]) s.ord.push_back(e);
+        std::stable_sort(s.ord.begin(), s.ord.end(), [&](int a, int b) { return u[(size_t)a] > u[(size_t)b]; });
+        for (size_t q = 0; q < s.ord.size(); q += (size_t)batch) {
+            if (u[(size_t)s.ord[q]] < std::max(floor, s.top)) break;
+            const int cnt = (int)std::min(s.ord.size() - q, (size_t)batch);
+            ST_TRY(solve_batch(s.ord.data() + q, cnt, vstart, napp));
+            for (int b = 0; b < cnt; ++b) {
+                report(s.ord[q + (size_t)b], h_lam[(size_t)b]);
+                s.top = std::max(s.top, h_lam[(size_t)b]);
+            }
+            s.solved += cnt;
+            s.last.assign(s.ord.begin() + (long)q, s.ord.begin() + (long)q + cnt);
         }
         return MACHIP_OK;
     }
 
+    // lambda_2(L_cur + e) of every unselected candidate (NaN for the selected), no pruning: the scan in index order, no bound below anything
+    int all_lambda2(double* out) {
+        std::fill(out, out + m, NAN);
+        machip::EigScan s;
+        return scan(s, std::vector<double>((size_t)m, INFINITY), -INFINITY, vcur, nullptr, [&](int e, double val) { out[e] = val; });
+    }
+
     int select(int K, int32_t* order_out, double* lambda2_out, double* t_ms_out) {
         using namespace machip;
-        hipStream_t st = base->stream;
-        if (matrix_free()) ST_TRY(eig_free_reserve(this, K));      // (refused before the state is touched)
+        ST_TRY(reserve(K));      // (refused before the state is touched)
         ST_TRY(reset());
         const auto t0 = std::chrono::steady_clock::now();
         std::vector<double> u, l2((size_t)m);
-        std::vector<int> ord, list;
         std::vector<char> done((size_t)m);
         for (int k = 0; k < K; ++k) {
             ST_TRY(bounds(u));
-            ord.clear();
-            for (int e = 0; e < m; ++e) if (!sel[(size_t)e]) ord.push_back(e);
-            std::stable_sort(ord.begin(), ord.end(), [&](int a, int b) { return u[(size_t)a] > u[(size_t)b]; });
             std::fill(done.begin(), done.end(), 0);
-            double top = -INFINITY;
-            int nsolved = 0, napp = 0;
-            size_t last_q = 0;
-            int last_cnt = 0;
-            for (size_t q = 0; q < ord.size(); q += (size_t)batch) {
-                if (u[(size_t)ord[q]] < top) break;           // every bound from here on is below a value already established
-                const int cnt = (int)std::min(ord.size() - q, (size_t)batch);
-                ST_TRY(solve_batch(ord.data() + q, cnt, vcur, &napp));
-                for (int b = 0; b < cnt; ++b) {
-                    const int e = ord[q + (size_t)b];
-                    l2[(size_t)e] = h_lam[(size_t)b]; done[(size_t)e] = 1;
-                    top = std::max(top, h_lam[(size_t)b]);
-                }
-                nsolved += cnt; last_q = q; last_cnt = cnt;
-            }
+            EigScan s;
+            int napp = 0;
+            ST_TRY(scan(s, u, -INFINITY, vcur, &napp, [&](int e, double val) { l2[(size_t)e] = val; done[(size_t)e] = 1; }));
             // the reference's scan: candidate-index order, a candidate replaces the running best only if it exceeds it by more than 1e-8
             int best = -1;
             double best_l2 = 0.0;
             for (int e = 0; e < m; ++e)
                 if (done[(size_t)e] && l2[(size_t)e] > best_l2 + kEigTol) { best = e; best_l2 = l2[(size_t)e]; }
             if (best < 0) return fail(MACHIP_NOT_CONVERGED, "GreedyEig: no candidate raises lambda_2 above 1e-8 at pick " + std::to_string(k));
-            // the winner's pair, polished (the next bounds are only as tight as this vector): one more solve of that column alone,
-            // from its converged vector when that is still resident (it was in the last batch), else from the current one
-            int col = -1;
-            for (int b = 0; b < last_cnt; ++b) if (ord[last_q + (size_t)b] == best) col = b;
-            ST_TRY(solve_batch(&best, 1, col >= 0 ? X + (size_t)col * (size_t)ldv : vcur, &napp, true));
-            best_l2 = h_lam[0];
-            HIP_TRY(hipMemcpyAsync(vcur, X, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, st));
-            lamcur = best_l2;
-            // its z joins the pending block; fold when due (form 2: the history, never folded -- the polished solve left z, c in column 0)
-            if (matrix_free()) {
-                ST_TRY(eig_free_push(this));
-            } else {
-                HIP_TRY(hipMemcpyAsync(bc, &best, sizeof(int), hipMemcpyHostToDevice, st));
-                HIP_TRY(hipStreamSynchronize(st));
-                const int j = base->pending;
-                k_eig_z<<<dim3((base->ld + kBlock - 1) / kBlock, 1), kBlock, 0, st>>>(base->view(), base->sig, j, bc, base->Zb + (size_t)j * (size_t)base->ld, base->cb + j);
-                base->pending = j + 1;
-                if (base->pending == base->fold) { base->fold_into(base->sig, base->pending); base->pending = 0; }
-            }
+            // the winner's pair: from its converged vector when that is still resident, else from the current one
+            const int col = s.resident_column(best);
+            ST_TRY(adopt_pair(best, col >= 0 ? X + (size_t)col * (size_t)ldv : vcur, &napp));
+            ST_TRY(push(best));
             HIP_TRY(hipGetLastError());
             sel[(size_t)best] = 1;
             add_edge(hci[(size_t)best], hcj[(size_t)best], hcw[(size_t)best]);
             ST_TRY(upload_graph());
-            solved.push_back(nsolved); applies.push_back(napp);
+            solved.push_back(s.solved); applies.push_back(napp);
             if (order_out) order_out[k] = best;
-            if (lambda2_out) lambda2_out[k] = best_l2;
+            if (lambda2_out) lambda2_out[k] = lamcur;
             if (t_ms_out) t_ms_out[k] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
         }
         return MACHIP_OK;

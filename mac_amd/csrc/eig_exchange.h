@@ -12,12 +12,12 @@
 //     and lambda the Rayleigh quotient the solver stored with it)  u(e, f) = lambda_2(S \ e) + w_f (x_i - x_j)^2 >= lambda_2(S \ e + f).
 //     K x ldm bounds, -inf for the selected f, and one maximum per workgroup.
 //   * exact solves: rows in decreasing order of their largest bound while that is above max(tau, top) (tau = lambda_2(S) + min_gain,
-//     top the largest value solved in the round); in a row, the greedy's rule: candidates in decreasing order of the bound, batch
-//     after batch from the start vector v^-e, until a batch's first bound is below max(tau, top).  For a row the downdate column of e
-//     is appended to the pending block (and dropped afterwards: a trial never folds) and the CSR of L_{S \ e} is uploaded.
+//     top the largest value solved in the round); in a row, the greedy's own scan (machip_eig::scan) from the start vector v^-e with
+//     the floor tau.  For a row the downdate column of e is appended to the pending block (and dropped afterwards: a trial never
+//     folds) and the CSR of L_{S \ e} is uploaded.
 //   * scan: the solved pairs in (e, f) order, a pair replaces the running value (initially tau) only if it exceeds it by more than
-//     1e-8 -- GreedyEig's rule.  Nobody: converged.  Else the swap: two columns join the pending block (folding when due), the
-//     adjacency, the flags and the negated copy of the row are rewritten, the new pair is polished.
+//     1e-8 -- GreedyEig's rule.  Nobody: converged.  Else the swap: two columns join the pending block (machip_eig::push_column), the
+//     adjacency, the flags and the negated copy of the row are rewritten, the new pair is polished (machip_eig::adopt_pair).
 // Everything is a function of the inputs alone: sorts are stable, reductions run in a fixed order, no floating-point atomics.
 #pragma once
 #include <chrono>
@@ -99,6 +99,8 @@ inline void eig_xch_release(EigXch*& x) {
 // The arguments, decided on the host before a device is touched.  sorted_out: the selection ascending.
 inline int eig_xch_check(const machip_eig* h, int64_t k, const int32_t* sel_in, int64_t max_swaps, double min_gain, std::vector<int>& sorted_out) {
     if (!h) return fail(MACHIP_BAD_ARG, "NULL handle");
+    if (h->matrix_free())
+        return fail(MACHIP_BAD_ARG, "the exchange works on the dense inverse: it is not available on a MACHIP_EIG_MATRIX_FREE handle");
     if (!sel_in) return fail(MACHIP_BAD_ARG, "sel_in is NULL");
     if (max_swaps < 0) return fail(MACHIP_BAD_ARG, "max_swaps must be >= 0 (got " + std::to_string((long long)max_swaps) + ")");
     if (!(min_gain >= 0.0) || !std::isfinite(min_gain)) return fail(MACHIP_BAD_ARG, "min_gain must be finite and >= 0");
@@ -180,16 +182,15 @@ struct EigXchPair {
     double val;
 };
 
-// The call (machip_eig_exchange after the argument checks).  rowe: the selection ascending.  Every output may be NULL.
-inline int eig_exchange(machip_eig* h, std::vector<int> rowe, int64_t max_swaps, double min_gain, int32_t* sel_out, int32_t* out_idx,
-                        int32_t* in_idx, double* lambda2_out, int64_t* n_swaps, int32_t* converged, int32_t* counts, double* t_ms) {
+// The rounds.  rowe: the selection ascending.  Every output may be NULL.
+inline int eig_exchange_run(machip_eig* h, std::vector<int> rowe, int64_t max_swaps, double min_gain, int32_t* sel_out, int32_t* out_idx,
+                            int32_t* in_idx, double* lambda2_out, int64_t* n_swaps, int32_t* converged, int32_t* counts, double* t_ms) {
     machip_esp* base = h->base;
     hipStream_t st = base->stream;
-    const int K = (int)rowe.size(), m = h->m, n = h->n, ld = base->ld, ldv = h->ldv, batch = h->batch;
+    const int K = (int)rowe.size(), m = h->m, ld = base->ld, ldv = h->ldv, batch = h->batch;
     const int ldm = (m + 3) / 4 * 4;
     const int chunks = std::max(1, std::min((m + kBlock - 1) / kBlock, (kEigXchTargetGroups + K - 1) / K));
     const int per = ((m + chunks - 1) / chunks + 3) / 4 * 4;
-    const int zg = (ld + kBlock - 1) / kBlock;
     ST_TRY(eig_xch_prepare(h->xc, (size_t)m, (size_t)K, (size_t)ldv, (size_t)ldm, (size_t)K * (size_t)chunks));
     EigXch* X = h->xc;
     while (base->ev.size() < 2) {
@@ -221,37 +222,27 @@ inline int eig_exchange(machip_eig* h, std::vector<int> rowe, int64_t max_swaps,
     };
     ST_TRY(upload_view());
     h->xcu = X->cu; h->xcv = X->cv; h->xcw = X->cw;
-    // the column of the candidate idx[at] joins the pending block; the block is folded when it is full
-    auto push_column = [&](int at) {
-        const int j = base->pending;
-        k_eig_z<<<dim3(zg, 1), kBlock, 0, st>>>(h->zview(), base->sig, j, X->idx + at, base->Zb + (size_t)j * (size_t)ld, base->cb + j);
-        base->pending = j + 1;
-        if (base->pending == base->fold) { base->fold_into(base->sig, base->pending); base->pending = 0; }
-    };
     for (int r = 0; r < K; ++r) {
         const int e = rowe[(size_t)r];
-        push_column(r);
+        h->push_column(X->idx + r);
         h->sel[(size_t)e] = 1;
         h->add_edge(h->hci[(size_t)e], h->hcj[(size_t)e], h->hcw[(size_t)e]);
     }
     HIP_TRY(hipGetLastError());
     ST_TRY(h->upload_graph());
-    const int none = -1;
-    ST_TRY(h->solve_batch(&none, 1, h->v0, nullptr, true));
-    HIP_TRY(hipMemcpyAsync(h->vcur, h->X, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, st));
-    h->lamcur = h->h_lam[0];
+    ST_TRY(h->adopt_pair(-1, h->v0, nullptr));
     if (lambda2_out) lambda2_out[0] = h->lamcur;
 
     // ---- rounds ----
     int64_t t = 0;
     int conv = 0;
     std::vector<double> lamr((size_t)K), part((size_t)K * (size_t)chunks), rowmax((size_t)K), u((size_t)m);
-    std::vector<int> list, rord((size_t)K), ord, last_ord;
+    std::vector<int> list, rord((size_t)K);
     std::vector<EigXchPair> pairs;
     while (t < max_swaps) {
         if (base->pending > 0 && base->pending + 2 > base->fold) { base->fold_into(base->sig, base->pending); base->pending = 0; }
         const double tau = h->lamcur + min_gain;
-        int napp = 0, nsolved = 0;
+        int napp = 0;
         // removal pairs: column b of a batch is the negated copy of row q + b
         for (int q = 0; q < K; q += batch) {
             const int cnt = std::min(K - q, batch);
@@ -275,16 +266,15 @@ inline int eig_exchange(machip_eig* h, std::vector<int> rowe, int64_t max_swaps,
         }
         std::stable_sort(rord.begin(), rord.end(), [&](int a, int b) { return rowmax[(size_t)a] > rowmax[(size_t)b]; });
         // exact solves
-        double top = -INFINITY;
+        EigScan scan;      // of the round: top runs over the rows, the last batch is the last row's that solved one
         pairs.clear();
-        int last_row = -1, last_cnt = 0;
-        size_t last_q = 0;
+        int last_row = -1;
         bool trial_graph = false;
         for (int r : rord) {
-            if (!(rowmax[(size_t)r] > std::max(tau, top))) break;
+            if (!(rowmax[(size_t)r] > std::max(tau, scan.top))) break;
             const int e = rowe[(size_t)r], a = h->hci[(size_t)e], b = h->hcj[(size_t)e];
             const int j = base->pending;
-            k_eig_z<<<dim3(zg, 1), kBlock, 0, st>>>(h->zview(), base->sig, j, X->idx + K + r, base->Zb + (size_t)j * (size_t)ld, base->cb + j);
+            eig_dense_columns(base, h->zview(), X->idx + K + r, 1, base->Zb + (size_t)j * (size_t)ld, base->cb + j);
             HIP_TRY(hipGetLastError());
             base->pending = j + 1;
             {      // the CSR of L_{S \ e}; the host's adjacency stays L_S
@@ -298,22 +288,11 @@ inline int eig_exchange(machip_eig* h, std::vector<int> rowe, int64_t max_swaps,
             }
             HIP_TRY(hipMemcpyAsync(u.data(), X->U + (size_t)r * (size_t)ldm, sizeof(double) * (size_t)m, hipMemcpyDeviceToHost, st));
             HIP_TRY(hipStreamSynchronize(st));
-            ord.clear();
-            for (int f = 0; f < m; ++f) if (!hsel[(size_t)f]) ord.push_back(f);
-            std::stable_sort(ord.begin(), ord.end(), [&](int x, int y) { return u[(size_t)x] > u[(size_t)y]; });
-            for (size_t q = 0; q < ord.size(); q += (size_t)batch) {
-                if (u[(size_t)ord[q]] < std::max(tau, top)) break;
-                const int cnt = (int)std::min(ord.size() - q, (size_t)batch);
-                const int rc = h->solve_batch(ord.data() + q, cnt, X->Vr + (size_t)r * (size_t)ldv, &napp);
-                if (rc != MACHIP_OK) { base->pending = j; return rc; }
-                for (int c = 0; c < cnt; ++c) {
-                    pairs.push_back({e, ord[q + (size_t)c], r, h->h_lam[(size_t)c]});
-                    top = std::max(top, h->h_lam[(size_t)c]);
-                }
-                nsolved += cnt; last_row = r; last_q = q; last_cnt = cnt;
-            }
-            if (last_row == r) last_ord = ord;
+            const int before = scan.solved;      // (h->sel is hsel: the scan leaves out the selected f)
+            const int rc = h->scan(scan, u, tau, X->Vr + (size_t)r * (size_t)ldv, &napp, [&](int f, double val) { pairs.push_back({e, f, r, val}); });
+            if (scan.solved > before) last_row = r;
             base->pending = j;      // the trial column is dropped: Sigma never saw it
+            if (rc != MACHIP_OK) return rc;
         }
         // scan
         std::stable_sort(pairs.begin(), pairs.end(), [](const EigXchPair& x, const EigXchPair& y) { return x.e < y.e || (x.e == y.e && x.f < y.f); });
@@ -323,30 +302,26 @@ inline int eig_exchange(machip_eig* h, std::vector<int> rowe, int64_t max_swaps,
             if (pairs[p].val > running + kEigTol) { best = (int)p; running = pairs[p].val; }
         if (best < 0) {
             if (trial_graph) ST_TRY(h->upload_graph());
-            h->solved.push_back(nsolved); h->applies.push_back(napp); h->removal.push_back(K);
+            h->solved.push_back(scan.solved); h->applies.push_back(napp); h->removal.push_back(K);
             conv = 1;
             break;
         }
         // the swap
         const EigXchPair w = pairs[(size_t)best];
-        push_column(K + w.row);                       // e leaves (the negated copy, still e's)
+        h->push_column(X->idx + K + w.row);          // e leaves (the negated copy, still e's)
         set_row(w.row, w.f);
         hsel[(size_t)w.e] = 0; hsel[(size_t)w.f] = 1;
         ST_TRY(upload_view());
-        push_column(w.row);                           // f enters
+        h->push_column(X->idx + w.row);              // f enters
         HIP_TRY(hipGetLastError());
         h->sel[(size_t)w.e] = 0; h->sel[(size_t)w.f] = 1;
         ST_TRY(eig_xch_remove_edge(h, h->hci[(size_t)w.e], h->hcj[(size_t)w.e], h->hcw[(size_t)w.e]));
         h->add_edge(h->hci[(size_t)w.f], h->hcj[(size_t)w.f], h->hcw[(size_t)w.f]);
         ST_TRY(h->upload_graph());
         // the new pair, polished: from the pair's converged vector when that is still resident (it was in the last batch), else from v^-e
-        int col = -1;
-        if (last_row == w.row)
-            for (int c = 0; c < last_cnt; ++c) if (last_ord[last_q + (size_t)c] == w.f) col = c;
-        ST_TRY(h->solve_batch(&none, 1, col >= 0 ? h->X + (size_t)col * (size_t)ldv : X->Vr + (size_t)w.row * (size_t)ldv, &napp, true));
-        HIP_TRY(hipMemcpyAsync(h->vcur, h->X, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, st));
-        h->lamcur = h->h_lam[0];
-        h->solved.push_back(nsolved); h->applies.push_back(napp); h->removal.push_back(K);
+        const int col = last_row == w.row ? scan.resident_column(w.f) : -1;
+        ST_TRY(h->adopt_pair(-1, col >= 0 ? h->X + (size_t)col * (size_t)ldv : X->Vr + (size_t)w.row * (size_t)ldv, &napp));
+        h->solved.push_back(scan.solved); h->applies.push_back(napp); h->removal.push_back(K);
         if (out_idx) out_idx[t] = w.e;
         if (in_idx) in_idx[t] = w.f;
         if (lambda2_out) lambda2_out[t + 1] = h->lamcur;
@@ -371,6 +346,18 @@ inline int eig_exchange(machip_eig* h, std::vector<int> rowe, int64_t max_swaps,
         t_ms[1] = ms;
     }
     return MACHIP_OK;
+}
+
+// The call after its checks: the handle leaves it with the greedy's candidate arrays and, after a failure, at the fixed graph (message kept)
+inline int eig_exchange(machip_eig* h, const std::vector<int>& rowe, int64_t max_swaps, double min_gain, int32_t* sel_out, int32_t* out_idx,
+                        int32_t* in_idx, double* lambda2_out, int64_t* n_swaps, int32_t* converged, int32_t* counts, double* t_ms) {
+    const int st = eig_exchange_run(h, rowe, max_swaps, min_gain, sel_out, out_idx, in_idx, lambda2_out, n_swaps, converged, counts, t_ms);
+    h->xcu = h->xcv = nullptr; h->xcw = nullptr;
+    if (st != MACHIP_OK) {
+        const std::string msg = machip_last_error();
+        if (h->reset() == MACHIP_OK) return fail((machip_status)st, msg);
+    }
+    return st;
 }
 
 }  // namespace machip

@@ -17,7 +17,8 @@
 // (k_eigf_alpha), written column-major into Z; k_eigf_cc makes c_e.  No atomics; the order of every sum is a function of
 // (ld, j, the batch, options eig_free_rows / eig_free_split) alone.
 // On a spanning-tree handle (form 3, eig_free_tree.h) pass 1 is that file's four sweeps over the tree, the history starts with the r
-// seeds of esp_tree.h (j = r + picks) and the batch's z_e take their base from the same sweeps; passes 2 and 3 are shared.
+// seeds of esp_tree.h (j = r + picks) and the batch's z_e take their base from the same sweeps; passes 2 and 3 (eig_free_history),
+// eig_free_init and the z_e's history part (eig_free_columns) are shared; machip_eig::apply (eig_routes.h) runs the form's pass 1.
 #pragma once
 #include <string>
 
@@ -255,11 +256,9 @@ inline size_t eig_free_part_elems(int K64, int ldq, int opt) {
     return std::max(y, (size_t)kEigFreeWgs * kGjT * kGjT);
 }
 
-// eig_free_tree.h -- form 3 only: the tables and S of the sweeps over the spanning tree, T = Sigma0(T) Q, the batch's z_e / c_e
+// eig_free_tree.h -- form 3 only: the tables and S of the sweeps over the spanning tree
 struct EigFreeTree;
 void eig_tree_release(EigFreeTree* G);
-int eig_tree_sweeps(machip_eig* h, int count, bool all);
-int eig_tree_columns(machip_eig* h, int count);
 
 // what the route keeps beside the batch arrays of machip_eig
 struct EigFree {
@@ -270,26 +269,25 @@ struct EigFree {
     EigFreeTree* tree = nullptr;               // form 3: the spanning tree in the place of the chain (cs / cu: its row and tour chunks' sums)
 };
 
-// Bytes of the batch arrays of a form-2 handle (machip_eig::alloc plus the chunks' sums), refused at create when they do not fit.
-inline int eig_free_check_batch(int n, int ld, int ldv, int ldq, int nchunks) {
-    const double need = 8.0 * (6.0 * ldv + 3.0 * ld + 2.0 * nchunks) * (double)ldq;
-    size_t fr = 0, tot = 0;
-    HIP_TRY(hipMemGetInfo(&fr, &tot));
-    if (need > (double)fr - 268435456.0)
-        return fail(MACHIP_BAD_ARG, "the batch arrays of MACHIP_EIG_MATRIX_FREE do not fit in device memory: n = " + std::to_string(n) + ", batch columns " +
-                                        std::to_string(ldq) + " ask for 8 (6 ldv + 3 ld + 2 chunks) ldq = " + std::to_string((unsigned long long)need) +
-                                        " bytes (ld = " + std::to_string(ld) + "), " + std::to_string((unsigned long long)fr) + " bytes are free: lower `batch`");
-    return MACHIP_OK;
-}
-
-inline int eig_free_init(machip_eig* h) {
+// What both routes start from: the scan chunks and option eig_free_split, then the batch arrays' bytes (machip_eig::alloc plus the
+// chunks' sums; form 3: S as well), refused when they do not fit, then the chunks' sums.  eig_tree_init adds the tree's tables.
+inline int eig_free_init(machip_eig* h, bool tree = false) {
     EigFree* F = new EigFree();
     h->fr = F;
     const Options& D = default_options();
-    F->rows = eig_free_rows(h->base->ld, (int)std::max(0l, std::min<long>(D.get(kOpt_eig_free_rows, 0), INT_MAX)));
-    F->nchunks = (h->base->ld + F->rows - 1) / F->rows;
+    const int ld = h->base->ld, mats = tree ? 4 : 3;
+    F->rows = eig_free_rows(ld, (int)std::max(0l, std::min<long>(D.get(kOpt_eig_free_rows, 0), INT_MAX)));
+    F->nchunks = (ld + F->rows - 1) / F->rows;
     F->split = (int)std::max(0l, std::min<long>(D.get(kOpt_eig_free_split, 0), kEigFreeMaxSplit));
-    ST_TRY(eig_free_check_batch(h->n, h->base->ld, h->ldv, h->ldq, F->nchunks));
+    const double need = 8.0 * (6.0 * h->ldv + (double)mats * ld + 2.0 * F->nchunks) * (double)h->ldq;
+    size_t fr = 0, tot = 0;
+    HIP_TRY(hipMemGetInfo(&fr, &tot));
+    if (need > (double)fr - 268435456.0)
+        return fail(MACHIP_BAD_ARG, std::string("the batch arrays of MACHIP_EIG_MATRIX_FREE") + (tree ? "_TREE" : "") + " do not fit in device memory: n = " +
+                                        std::to_string(h->n) + (tree ? " (r = " + std::to_string(h->seeds) + " seeds)" : "") + ", batch columns " +
+                                        std::to_string(h->ldq) + " ask for 8 (6 ldv + " + std::to_string(mats) + " ld + 2 chunks) ldq = " +
+                                        std::to_string((unsigned long long)need) + " bytes (ld = " + std::to_string(ld) + "), " +
+                                        std::to_string((unsigned long long)fr) + " bytes are free: lower `batch`");
     ST_TRY(dev_alloc(&F->cs, (size_t)F->nchunks * (size_t)h->ldq));
     ST_TRY(dev_alloc(&F->cu, (size_t)F->nchunks * (size_t)h->ldq));
     return MACHIP_OK;
@@ -340,10 +338,11 @@ inline int eig_free_reserve(machip_eig* h, int64_t K) {
     return MACHIP_OK;
 }
 
-// z_e = Sigma_cur a_e and c_e of the columns bc[0..count) into Z / cc
+// z_e = Sigma_cur a_e and c_e of the columns bc[0..count) into Z / cc: Sigma0 a_e from R (form 2), or as the sweeps over the spanning
+// tree left it in T (FROM_T: eig_tree_columns), minus the history's part
+template <bool FROM_T = false>
 inline int eig_free_columns(machip_eig* h, int count) {
     const EigFree* F = h->fr;
-    if (F->tree) return eig_tree_columns(h, count);
     const machip_esp* base = h->base;
     const EigView E = h->view();
     hipStream_t st = base->stream;
@@ -352,28 +351,31 @@ inline int eig_free_columns(machip_eig* h, int count) {
         const size_t tot = (size_t)j64 * (size_t)h->ldq;
         k_eigf_alpha<<<(unsigned)std::min<size_t>(kMaxGrid, (tot + kBlock - 1) / kBlock), kBlock, 0, st>>>(E, base->Zb, base->cb, F->Y, j, j64, count);
     }
-    k_eigf_back<true><<<dim3((count + kGjT - 1) / kGjT, base->ld / kGjT), 256, 0, st>>>(E, base->R, base->Zb, F->Y, j, count);
+    k_eigf_back<true, FROM_T><<<dim3((count + kGjT - 1) / kGjT, base->ld / kGjT), 256, 0, st>>>(E, FROM_T ? nullptr : base->R, base->Zb, F->Y, j, count);
     k_eigf_cc<<<(count + kBlock - 1) / kBlock, kBlock, 0, st>>>(E, count);
     return MACHIP_OK;
 }
 
-// T = Sigma_cur Q for the live columns of the batch
-inline int eig_free_apply(machip_eig* h, int count) {
+// form 2, pass 1: T = Sigma0 Q for the live columns of the batch
+inline void eig_free_scans(machip_eig* h, int count) {
     const EigFree* F = h->fr;
     const machip_esp* base = h->base;
     const EigView E = h->view();
+    const dim3 sg((count + kGjT - 1) / kGjT, F->nchunks);
+    k_eigf_scan<0><<<sg, kWave, 0, base->stream>>>(E, base->R, F->cs, F->cu, F->rows, count);
+    k_eigf_scan<1><<<sg, kWave, 0, base->stream>>>(E, base->R, F->cs, F->cu, F->rows, count);
+    k_eigf_scan<2><<<sg, kWave, 0, base->stream>>>(E, base->R, F->cs, F->cu, F->rows, count);
+}
+
+// both routes, passes 2 and 3: T -= Zb diag(cb) Zb^T Q, which leaves T = Sigma_cur Q
+inline void eig_free_history(machip_eig* h, int count) {
+    const EigFree* F = h->fr;
+    const machip_esp* base = h->base;
+    const int j = base->pending;
+    if (j == 0) return;
+    const EigView E = h->view();
     hipStream_t st = base->stream;
     const int cg = (count + kGjT - 1) / kGjT;
-    if (F->tree) {
-        ST_TRY(eig_tree_sweeps(h, count, false));
-    } else {
-        const dim3 sg(cg, F->nchunks);
-        k_eigf_scan<0><<<sg, kWave, 0, st>>>(E, base->R, F->cs, F->cu, F->rows, count);
-        k_eigf_scan<1><<<sg, kWave, 0, st>>>(E, base->R, F->cs, F->cu, F->rows, count);
-        k_eigf_scan<2><<<sg, kWave, 0, st>>>(E, base->R, F->cs, F->cu, F->rows, count);
-    }
-    const int j = base->pending;
-    if (j == 0) return MACHIP_OK;
     const int jt = (j + kGjT - 1) / kGjT, j64 = jt * kGjT, ldp = cg * kGjT;
     const int S = eig_free_slices(base->ld, j, count, F->split);
     const int per = (base->ld / kEigFreePanel + S - 1) / S * kEigFreePanel;
@@ -381,7 +383,6 @@ inline int eig_free_apply(machip_eig* h, int count) {
     const size_t tot = (size_t)j64 * (size_t)ldp;
     k_eigf_ysum<<<(unsigned)std::min<size_t>(kMaxGrid, (tot + kBlock - 1) / kBlock), kBlock, 0, st>>>(F->part, base->cb, F->Y, S, j, j64, ldp, h->ldq);
     k_eigf_back<false><<<dim3(cg, base->ld / kGjT), 256, 0, st>>>(E, base->R, base->Zb, F->Y, j, count);
-    return MACHIP_OK;
 }
 
 // the winner's z_e, c_e (column 0 of Z / cc after its polished solve) become column j of the history

@@ -113,31 +113,13 @@ __global__ __launch_bounds__(kBlock) void k_eigt_fill(EigView E, int count) {
     }
 }
 
-// Bytes of the batch arrays of a form-3 handle (machip_eig::alloc, S and the chunks' sums), refused at create when they do not fit.
-inline int eig_tree_check_batch(int n, int seeds, int ld, int ldv, int ldq, int nchunks) {
-    const double need = 8.0 * (6.0 * ldv + 4.0 * ld + 2.0 * nchunks) * (double)ldq;
-    size_t fr = 0, tot = 0;
-    HIP_TRY(hipMemGetInfo(&fr, &tot));
-    if (need > (double)fr - 268435456.0)
-        return fail(MACHIP_BAD_ARG, "the batch arrays of MACHIP_EIG_MATRIX_FREE_TREE do not fit in device memory: n = " + std::to_string(n) + " (r = " +
-                                        std::to_string(seeds) + " seeds), batch columns " + std::to_string(ldq) +
-                                        " ask for 8 (6 ldv + 4 ld + 2 chunks) ldq = " + std::to_string((unsigned long long)need) + " bytes (ld = " +
-                                        std::to_string(ld) + "), " + std::to_string((unsigned long long)fr) + " bytes are free: lower `batch`");
-    return MACHIP_OK;
-}
-
-// The route's tables from the plan (node_of, the tour, d) and its buffers; the chunks and the options as eig_free_init.
+// eig_free_init, then the route's tables from the plan (node_of, the tour, d) and S.
 inline int eig_tree_init(machip_eig* h, const EspTreePlan& P) {
-    EigFree* F = new EigFree();
-    h->fr = F;
+    ST_TRY(eig_free_init(h, true));
+    EigFree* F = h->fr;
     EigFreeTree* G = new EigFreeTree();
     F->tree = G;
     const machip_esp* base = h->base;
-    const Options& D = default_options();
-    F->rows = eig_free_rows(base->ld, (int)std::max(0l, std::min<long>(D.get(kOpt_eig_free_rows, 0), INT_MAX)));
-    F->nchunks = (base->ld + F->rows - 1) / F->rows;
-    F->split = (int)std::max(0l, std::min<long>(D.get(kOpt_eig_free_split, 0), kEigFreeMaxSplit));
-    ST_TRY(eig_tree_check_batch(h->n, h->seeds, base->ld, h->ldv, h->ldq, F->nchunks));
     const int N = h->n;
     const size_t n = (size_t)N;
     std::vector<int> node_of(n), tour, stack;
@@ -155,8 +137,6 @@ inline int eig_tree_init(machip_eig* h, const EspTreePlan& P) {
     }
     while (!stack.empty()) { tour.push_back(stack.back() | kEigTreeLeave); stack.pop_back(); }
     G->nev = (int)tour.size();
-    ST_TRY(dev_alloc(&F->cs, (size_t)F->nchunks * (size_t)h->ldq));
-    ST_TRY(dev_alloc(&F->cu, (size_t)F->nchunks * (size_t)h->ldq));
     ST_TRY(dev_alloc(&G->S, (size_t)base->ld * (size_t)h->ldq));
     ST_TRY(dev_alloc(&G->node_of, n)); ST_TRY(dev_alloc(&G->d, n)); ST_TRY(dev_alloc(&G->tour, tour.size()));
     hipStream_t st = base->stream;
@@ -193,21 +173,11 @@ inline int eig_tree_sweeps(machip_eig* h, int count, bool all) {
 
 // z_e = Sigma_cur a_e and c_e of the columns bc[0..count) into Z / cc; Q is left all zero (what machip_eig::alloc promises, and more)
 inline int eig_tree_columns(machip_eig* h, int count) {
-    const EigFree* F = h->fr;
-    const machip_esp* base = h->base;
-    const EigView E = h->view();
-    hipStream_t st = base->stream;
-    const size_t qtot = (size_t)base->ld * (size_t)h->ldq;
-    k_eigt_fill<<<(unsigned)std::min<size_t>(kMaxGrid, (qtot + kBlock - 1) / kBlock), kBlock, 0, st>>>(E, count);
+    const size_t qtot = (size_t)h->base->ld * (size_t)h->ldq;
+    k_eigt_fill<<<(unsigned)std::min<size_t>(kMaxGrid, (qtot + kBlock - 1) / kBlock), kBlock, 0, h->base->stream>>>(h->view(), count);
     ST_TRY(eig_tree_sweeps(h, count, true));
-    const int j = base->pending, j64 = (j + kGjT - 1) / kGjT * kGjT;
-    if (j > 0) {
-        const size_t tot = (size_t)j64 * (size_t)h->ldq;
-        k_eigf_alpha<<<(unsigned)std::min<size_t>(kMaxGrid, (tot + kBlock - 1) / kBlock), kBlock, 0, st>>>(E, base->Zb, base->cb, F->Y, j, j64, count);
-    }
-    k_eigf_back<true, true><<<dim3((count + kGjT - 1) / kGjT, base->ld / kGjT), 256, 0, st>>>(E, nullptr, base->Zb, F->Y, j, count);
-    k_eigf_cc<<<(count + kBlock - 1) / kBlock, kBlock, 0, st>>>(E, count);
-    HIP_TRY(hipMemsetAsync(h->Q, 0, sizeof(double) * qtot, st));
+    ST_TRY(eig_free_columns<true>(h, count));
+    HIP_TRY(hipMemsetAsync(h->Q, 0, sizeof(double) * qtot, h->base->stream));
     return MACHIP_OK;
 }
 

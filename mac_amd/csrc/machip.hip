@@ -23,10 +23,8 @@
 #include "esp_relax.h"
 #include "esp_exchange.h"
 #include "esp_exchange_edge.h"
-#include "eig.h"
 #include "eig_exchange.h"
-#include "eig_free.h"
-#include "eig_free_tree.h"
+#include "eig_routes.h"
 
 namespace machip {
 thread_local std::string g_err;
@@ -1569,15 +1567,15 @@ int machip_host_follow_records(const double* tri3, int J, int n, double e_target
 
 // ---- GreedyESP (esp.h; the routes without Sigma: esp_free.h, esp_tree.h; the three together: esp_select.h) ----
 
-int machip_esp_create(int device, int64_t n, int64_t n_fixed, const int32_t* fi, const int32_t* fj, const double* fw,
-                      int64_t m, const int32_t* ci, const int32_t* cj, const double* cw, int fold, int flags, machip_esp** out) {
+// machip_esp_create; tplan: the spanning-tree plan the handle's tables are made from (MACHIP_ESP_SPANNING_TREE), left to the caller
+static int esp_create(int device, int64_t n, int64_t n_fixed, const int32_t* fi, const int32_t* fj, const double* fw, int64_t m,
+                      const int32_t* ci, const int32_t* cj, const double* cw, int fold, int flags, machip_esp** out, EspTreePlan& tplan) {
     if (!out) return fail(MACHIP_BAD_ARG, "out is NULL");
     *out = nullptr;
     ST_TRY(esp_create_check(n, n_fixed, fi, fj, fw, m, ci, cj, cw, fold, flags));
     const bool mfree = (flags & MACHIP_ESP_MATRIX_FREE) != 0, tree = (flags & MACHIP_ESP_SPANNING_TREE) != 0;
     EspFixedClass fixed;
     ST_TRY(esp_classify_fixed(n, n_fixed, fi, fj, fw, flags, fixed));
-    EspTreePlan tplan;
     if (tree) ST_TRY(esp_tree_plan(n, n_fixed, fi, fj, fw, tplan));
     if (machip_device_count() <= 0) return fail(MACHIP_NO_DEVICE, "no HIP device visible");
     HIP_TRY(hipSetDevice(device));
@@ -1596,6 +1594,12 @@ int machip_esp_create(int device, int64_t n, int64_t n_fixed, const int32_t* fi,
     if (st != MACHIP_OK) { machip_esp_destroy(h); return st; }
     *out = h;
     return MACHIP_OK;
+}
+
+int machip_esp_create(int device, int64_t n, int64_t n_fixed, const int32_t* fi, const int32_t* fj, const double* fw,
+                      int64_t m, const int32_t* ci, const int32_t* cj, const double* cw, int fold, int flags, machip_esp** out) {
+    EspTreePlan tplan;
+    return esp_create(device, n, n_fixed, fi, fj, fw, m, ci, cj, cw, fold, flags, out, tplan);
 }
 
 void machip_esp_destroy(machip_esp* h) {
@@ -1723,76 +1727,17 @@ int machip_esp_relax_gram(machip_esp* h, double* G_out, int64_t M) {
     return MACHIP_OK;
 }
 
-// ---- GreedyEig (eig.h) ----
+// ---- GreedyEig (eig.h; the routes without Sigma: eig_free.h, eig_free_tree.h; the three together: eig_routes.h) ----
 
 int machip_eig_create(int device, int64_t n, int64_t n_fixed, const int32_t* fi, const int32_t* fj, const double* fw,
                       int64_t m, const int32_t* ci, const int32_t* cj, const double* cw, int fold, int batch, int flags, machip_eig** out) {
     if (!out) return fail(MACHIP_BAD_ARG, "out is NULL");
     *out = nullptr;
-    const int fold_given = fold;
-    if (fold == 0) fold = kEigDefaultFold;
-    if (batch == 0) batch = kEigDefaultBatch;
-    if (batch < 1 || batch > kEigMaxBatch) return fail(MACHIP_BAD_ARG, "batch must be in [1, 4096]");
-    const bool efree = (flags & MACHIP_EIG_MATRIX_FREE) != 0, etree = (flags & MACHIP_EIG_MATRIX_FREE_TREE) != 0;
-    if ((flags & MACHIP_ESP_MATRIX_FREE) && !efree)
-        return fail(MACHIP_BAD_ARG, "GreedyEig solves against the dense inverse: MACHIP_ESP_MATRIX_FREE is not available here");
-    if (flags & MACHIP_ESP_SPANNING_TREE)
-        return fail(MACHIP_BAD_ARG, "GreedyEig solves against the dense inverse: MACHIP_ESP_SPANNING_TREE is not available here");
-    if (etree && !(efree && (flags & MACHIP_ESP_MATRIX_FREE)))
-        return fail(MACHIP_BAD_ARG, "MACHIP_EIG_MATRIX_FREE_TREE puts GreedyEig on the spanning-tree handle: it is valid only as MACHIP_ESP_MATRIX_FREE | MACHIP_EIG_MATRIX_FREE | MACHIP_EIG_MATRIX_FREE_TREE");
-    if (efree) {      // the routes without Sigma (eig_free.h, eig_free_tree.h): every refusal here and in machip_esp_create is decided before a device is touched
-        if (!(flags & MACHIP_ESP_MATRIX_FREE))
-            return fail(MACHIP_BAD_ARG, "MACHIP_EIG_MATRIX_FREE puts GreedyEig on the chain-free handle: it is valid only as MACHIP_ESP_MATRIX_FREE | MACHIP_EIG_MATRIX_FREE");
-        if (flags & MACHIP_ESP_DENSE_INVERSE)
-            return fail(MACHIP_BAD_ARG, "MACHIP_EIG_MATRIX_FREE keeps no Sigma: it cannot be combined with MACHIP_ESP_DENSE_INVERSE");
-        if (flags & ~(MACHIP_ESP_MATRIX_FREE | MACHIP_EIG_MATRIX_FREE | MACHIP_EIG_MATRIX_FREE_TREE))
-            return fail(MACHIP_BAD_ARG, "unknown flags: MACHIP_EIG_MATRIX_FREE is valid only as MACHIP_ESP_MATRIX_FREE | MACHIP_EIG_MATRIX_FREE");
-        if (fold_given != 0)      // (an argument that would be ignored is refused, not dropped)
-            return fail(MACHIP_BAD_ARG, "MACHIP_EIG_MATRIX_FREE never folds: fold has no meaning on this route and must be 0");
-        fold = 0;
-    }
+    ST_TRY(eig_create_check(fold, batch, flags));      // (flags: the machip_esp's from here on)
     machip_esp* base = nullptr;
-    // (the tree route asks for the spanning-tree handle itself: a caller's MACHIP_ESP_SPANNING_TREE stays refused above)
-    ST_TRY(machip_esp_create(device, n, n_fixed, fi, fj, fw, m, ci, cj, cw, fold,
-                             (flags & ~(MACHIP_EIG_MATRIX_FREE | MACHIP_EIG_MATRIX_FREE_TREE)) | (etree ? MACHIP_ESP_SPANNING_TREE : 0), &base));
-    if (base->beta != 0.0) {
-        machip_esp_destroy(base);
-        return fail(MACHIP_DISCONNECTED, "GreedyEig needs a connected fixed graph (lambda_2 of the fixed graph is 0 otherwise)");
-    }
-    machip_eig* h = new machip_eig();
-    h->base = base; h->n = (int)n; h->m = (int)m; h->batch = batch;
-    h->ldq = (batch + kGjT - 1) / kGjT * kGjT;
-    h->ldv = ((int)n + kGjT - 1) / kGjT * kGjT;
-    h->adj0.assign((size_t)n, {}); h->hdeg0.assign((size_t)n, 0.0);
-    for (int64_t e = 0; e < n_fixed; ++e) {
-        if (fi[e] == fj[e]) continue;
-        h->adj0[(size_t)fi[e]].emplace_back(fj[e], fw[e]); h->adj0[(size_t)fj[e]].emplace_back(fi[e], fw[e]);
-        h->hdeg0[(size_t)fi[e]] += fw[e]; h->hdeg0[(size_t)fj[e]] += fw[e];
-    }
-    h->hci.assign(ci, ci + m); h->hcj.assign(cj, cj + m); h->hcw.assign(cw, cw + m);
-    h->sel.assign((size_t)m, 0);
-    h->seeds = etree ? base->tr->seeds : 0;
-    auto body = [&]() -> int {
-        if (etree) {      // the plan machip_esp_create has just made its tables from: the same arguments, the same plan
-            EspTreePlan tplan;
-            ST_TRY(esp_tree_plan(n, n_fixed, fi, fj, fw, tplan));
-            ST_TRY(eig_tree_init(h, tplan));
-        } else if (efree) {
-            ST_TRY(eig_free_init(h));      // (its memory check comes before the batch arrays are allocated)
-        }
-        ST_TRY(h->alloc());
-        h->adj = h->adj0; h->hdeg = h->hdeg0;
-        ST_TRY(h->upload_graph());
-        if (!efree) ST_TRY(base->load_sigma0());
-        if (etree) ST_TRY(eig_free_reserve(h, 0));      // the seeds into the history: the fixed graph's own pair needs them
-        base->pending = h->seeds;
-        ST_TRY(h->first_pair());
-        return h->reset();
-    };
-    const int st = body();
-    if (st != MACHIP_OK) { machip_eig_destroy(h); return st; }
-    *out = h;
-    return MACHIP_OK;
+    EspTreePlan tplan;
+    ST_TRY(esp_create(device, n, n_fixed, fi, fj, fw, m, ci, cj, cw, fold, flags, &base, tplan));
+    return eig_create_build(base, tplan, batch, out);
 }
 
 void machip_eig_destroy(machip_eig* h) {
@@ -1816,19 +1761,11 @@ int machip_eig_select(machip_eig* h, int64_t k, int32_t* order_out, double* lamb
 int machip_eig_exchange(machip_eig* h, int64_t k, const int32_t* sel_in, int64_t max_swaps, double min_gain, int32_t* sel_out,
                         int32_t* out_idx, int32_t* in_idx, double* lambda2_out, int64_t* n_swaps, int32_t* converged, int32_t* counts, double* t_ms) {
     std::vector<int> rowe;
-    if (h && h->matrix_free())
-        return fail(MACHIP_BAD_ARG, "the exchange works on the dense inverse: it is not available on a MACHIP_EIG_MATRIX_FREE handle");
     ST_TRY(eig_xch_check(h, k, sel_in, max_swaps, min_gain, rowe));
     if (n_swaps) *n_swaps = 0;
     if (converged) *converged = 0;
     HIP_TRY(hipSetDevice(h->base->device));
-    const int st = eig_exchange(h, rowe, max_swaps, min_gain, sel_out, out_idx, in_idx, lambda2_out, n_swaps, converged, counts, t_ms);
-    h->xcu = h->xcv = nullptr; h->xcw = nullptr;
-    if (st != MACHIP_OK) {      // (a solve that did not converge, a HIP error: back to the fixed graph, the message kept)
-        const std::string msg = machip_last_error();
-        if (h->reset() == MACHIP_OK) return fail((machip_status)st, msg);
-    }
-    return st;
+    return eig_exchange(h, rowe, max_swaps, min_gain, sel_out, out_idx, in_idx, lambda2_out, n_swaps, converged, counts, t_ms);
 }
 
 int machip_eig_candidate_lambda2(machip_eig* h, double* out) {

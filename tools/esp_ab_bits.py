@@ -4,13 +4,16 @@ cases below return, bit for bit.
     python tools/esp_ab_bits.py LIB_A LIB_B      (two builds, MACHIP_BUILD_OUT=; ESP_AB_BITS_OUT=DIR keeps A.npz and B.npz there)
 
 Each library runs the cases once in a fresh child process of its own (MACHIP_LIB is read at import), one child after the other,
-and saves what it got; the parent opens no device, compares with np.array_equal, and exits 1 at the first difference with the
+and saves what it got; the parent opens no device, compares shape, type and bytes, and exits 1 at the first difference with the
 case and the array named.  Times (t_ms) are left out.  The cases are the smallest shapes at which each shared host driver can go
 wrong: the dense greedy (chain form at ld = 192 with 63 padding rows, fold 4, budgets [3, 11] and a restart; Gauss-Jordan form at
 ld = 128), the chain-free greedy (K = 40: one slice up to pick 31, two from 32 on; esp_free_split = 2; a grown history at K = 60),
 the tree greedy (5 seeds, carried over when the history grows), the dense exchange (folds inside rounds, LDS and global rows,
 max_swaps = 0), the edge-space exchange (chain; tree with the seeds as forced picks) and five Frank-Wolfe iterations in the three
-spaces, with relax_inner as a handle's first call."""
+spaces, with relax_inner as a handle's first call.
+
+The child / save / compare harness is `main(argv, cases, script)`: another family's tool (tools/eig_ab_bits.py) passes its own case
+set and file, and gets the same rules -- NAME_OUT=DIR for a tool NAME.py."""
 import os
 import subprocess
 import sys
@@ -98,31 +101,33 @@ def cases():
     return out
 
 
-def main(argv):
+def main(argv, cases=cases, script=__file__):
+    """cases: () -> {"case/array": values}, run in the child; script: the file that calls this with them (what the child runs)."""
+    tool = os.path.splitext(os.path.basename(script))[0]
     if len(argv) == 3 and argv[1] == "--child":
         np.savez(argv[2], **cases())
         return 0
     if len(argv) != 3:
-        print(__doc__)
+        print(sys.modules[cases.__module__].__doc__)
         return 2
     got = []
-    keep = os.environ.get("ESP_AB_BITS_OUT") or tempfile.mkdtemp(prefix="esp_ab_bits_")      # (the saved arrays: A.npz, B.npz)
+    keep = os.environ.get(f"{tool.upper()}_OUT") or tempfile.mkdtemp(prefix=f"{tool}_")      # (the saved arrays: A.npz, B.npz)
     os.makedirs(keep, exist_ok=True)
     for i, lib in enumerate(argv[1:]):
         path = os.path.join(keep, f"{'AB'[i]}.npz")
         env = dict(os.environ, MACHIP_LIB=os.path.abspath(lib))
-        subprocess.run([sys.executable, os.path.abspath(__file__), "--child", path], env=env, check=True)      # (one child at a time)
+        subprocess.run([sys.executable, os.path.abspath(script), "--child", path], env=env, check=True)      # (one child at a time)
         got.append(np.load(path))
     A, B = got
     if sorted(A.files) != sorted(B.files):
         print("DIFFERENT: the two runs did not return the same arrays", sorted(set(A.files) ^ set(B.files)))
         return 1
     for name in A.files:
-        if A[name].shape != B[name].shape or not np.array_equal(A[name], B[name]):
+        if A[name].shape != B[name].shape or A[name].dtype != B[name].dtype or A[name].tobytes() != B[name].tobytes():      # (NaN is a value like any other)
             print(f"DIFFERENT: case {name.rsplit('/', 1)[0]}, array {name.rsplit('/', 1)[1]}\n A = {A[name]}\n B = {B[name]}")
             return 1
         print(f"same  {name}  {A[name].dtype}{list(A[name].shape)}")
-    print(f"esp_ab_bits: {len(A.files)} arrays bit-identical between {argv[1]} and {argv[2]}")
+    print(f"{tool}: {len(A.files)} arrays bit-identical between {argv[1]} and {argv[2]}")
     return 0
 
 
