@@ -37,6 +37,9 @@ constexpr int kEspChainMaxN = 32768;   // chain form: 2 x 8.6 GB of Sigma at the
 constexpr int kEspDenseMaxN = 16384;   // general form: 512 Gauss-Jordan launches over 2 x 2.1 GB (k_gj_step indexes with int: ld^2 < 2^31)
 constexpr int kEspFormFree = 2;        // machip_esp::form of MACHIP_ESP_MATRIX_FREE: no Sigma at all, no n limit (esp_free.h)
 constexpr int kEspFormTree = 3;        // machip_esp::form of MACHIP_ESP_MATRIX_FREE | MACHIP_ESP_SPANNING_TREE (esp_tree.h)
+// machip_esp::relax_space, what machip_esp_relax_info reports: the nodes (esp_relax.h), the candidates of a chain handle
+// (MACHIP_ESP_EDGE_RELAX, esp_relax_edge.h), the candidates and seeds of a spanning-tree handle (MACHIP_ESP_EDGE_RELAX_TREE, esp_relax_edge_tree.h)
+enum EspRelaxSpace : int { kEspRelaxNode = 0, kEspRelaxEdge = 1, kEspRelaxEdgeTree = 2 };
 constexpr int kEspMaxFold = 256;
 constexpr int kEspDefaultFold = 64;
 constexpr int kEspGrid = 256;          // workgroups of the score / update pass (= partials of the argmax)
@@ -250,8 +253,7 @@ struct machip_esp {
     int device = 0;
     hipStream_t stream = nullptr;
     int n = 0, np = 0, ld = 0, m = 0, fold = machip::kEspDefaultFold;
-    bool edge_relax = false;      // MACHIP_ESP_EDGE_RELAX (form 2 only): the relaxation runs in the candidates' space (esp_relax_edge.h)
-    bool edge_tree = false;       // MACHIP_ESP_EDGE_RELAX_TREE (form 3 only): the same over the spanning tree's columns (esp_relax_edge_tree.h)
+    machip::EspRelaxSpace relax_space = machip::kEspRelaxNode;      // the space the relaxation and the edge-space exchange work in (esp_relax.h: esp_relax_route)
     int form = 0;                 // 0 chain, 1 general (dense Gauss-Jordan inverse), 2 chain without Sigma (esp_free.h), 3 spanning tree without Sigma (esp_tree.h)
     double beta = 0.0;
     double *R = nullptr, *part = nullptr;      // form 2: the chain's prefix resistances (n'); forms 2, 3: the column slices' partial sums

@@ -200,7 +200,7 @@ inline int esp_xch_check(const machip_esp* h, int64_t k, const int32_t* sel_in, 
     if (max_swaps < 0) return fail(MACHIP_BAD_ARG, "max_swaps must be >= 0 (got " + std::to_string((long long)max_swaps) + ")");
     if (max_swaps > 0 && (!out_idx || !in_idx || !ratio)) return fail(MACHIP_BAD_ARG, "out_idx, in_idx or ratio is NULL with max_swaps > 0");
     if (!(min_gain >= 0.0) || !std::isfinite(min_gain)) return fail(MACHIP_BAD_ARG, "min_gain must be finite and >= 0");
-    if (edge && !h->edge_relax && !h->edge_tree)
+    if (edge && h->relax_space == kEspRelaxNode)
         return fail(MACHIP_BAD_ARG, "the edge-space exchange works on the relaxation's Gram matrix: the handle must be made with MACHIP_ESP_EDGE_RELAX or MACHIP_ESP_EDGE_RELAX_TREE");
     if (!edge && (h->form == kEspFormFree || h->form == kEspFormTree))
         return fail(MACHIP_BAD_ARG, "the exchange works on the dense Sigma: not available on a MACHIP_ESP_MATRIX_FREE handle");

@@ -128,9 +128,8 @@ inline void esp_xe_release(EspXchEdge*& e) {
 // The view's own arrays, once per handle (the relaxation's state exists: its ld is the view's).
 inline int esp_xe_prepare(machip_esp* h, EspXchEdge* e) {
     if (e->cu) return MACHIP_OK;
-    const EspRelax* r = h->rx;
-    e->M = r->et ? r->et->M : h->m;
-    e->ld = r->ld;
+    e->M = h->rx->edge->M;
+    e->ld = h->rx->edge->ld;
     const size_t ld = (size_t)e->ld;
     ST_TRY(dev_alloc(&e->cu, ld)); ST_TRY(dev_alloc(&e->cv, ld)); ST_TRY(dev_alloc(&e->cw, ld)); ST_TRY(dev_alloc(&e->s, ld));
     ST_TRY(dev_alloc(&e->sel, ld)); ST_TRY(dev_alloc(&e->Zb, ld * (size_t)kEspDefaultFold)); ST_TRY(dev_alloc(&e->cb, (size_t)kEspDefaultFold));
@@ -146,26 +145,20 @@ inline int esp_xe_prepare(machip_esp* h, EspXchEdge* e) {
     return MACHIP_OK;
 }
 
-// R <- G into the relaxation's N buffer; the buffer is returned.
-inline int esp_xe_load_gram(machip_esp* h, const EspXchEdge* e, double** Rm) {
-    const EspRelax* r = h->rx;
-    hipStream_t st = h->stream;
-    if (r->et) {
-        *Rm = r->et->bufN;
-        HIP_TRY(hipMemcpyAsync(*Rm, r->et->G, sizeof(double) * (size_t)e->ld * (size_t)e->ld, hipMemcpyDeviceToDevice, st));
-    } else {
-        *Rm = r->ed->bufN;
-        k_esp_xe_init<<<e->ld, kBlock, 0, st>>>(*Rm, e->ld, h->m, r->ed->lo, r->ed->hi, h->R);
-        HIP_TRY(hipGetLastError());
-    }
+// R <- G into the relaxation's N buffer (a copy of G where it is stored, the chain's closed form where not); the buffer is returned.
+inline int esp_xe_load_gram(machip_esp* h, double** Rm) {
+    const EspEdge* E = h->rx->edge;
+    *Rm = E->bufN;
+    if (E->G) HIP_TRY(hipMemcpyAsync(*Rm, E->G, sizeof(double) * (size_t)E->ld * (size_t)E->ld, hipMemcpyDeviceToDevice, h->stream));
+    else k_esp_xe_init<<<E->ld, kBlock, 0, h->stream>>>(*Rm, E->ld, h->m, E->eu, E->ev, h->R);
+    HIP_TRY(hipGetLastError());
     return MACHIP_OK;
 }
 
 // the edge handles' space: R from G in the relaxation's N buffer, the seeds ahead of the selection, the entering column's closed form
 struct EspXchEdgeSpace : EspXchSpace {
     machip_esp* h;
-    const EspXchEdge* E;
-    ESP_INLINE int load(double** S) { return esp_xe_load_gram(h, E, S); }
+    ESP_INLINE int load(double** S) { return esp_xe_load_gram(h, S); }
     ESP_INLINE void pairs() { k_esp_xch_pairs_edge<<<dim3((unsigned)K, (unsigned)chunks), kBlock, 0, h->stream>>>(V, h->m, X->T, X->rowe, per, X->pv, X->pf); }
     ESP_INLINE void entered(int e, int j) { k_esp_xe_entered<<<1, kBlock, 0, h->stream>>>(V, e, j, X->scale); }      // (s_e / (1 + s_e) without the cancellation)
     ESP_INLINE void finish(int) {}
@@ -175,7 +168,7 @@ struct EspXchEdgeSpace : EspXchSpace {
 inline int esp_exchange_edge(machip_esp* h, int64_t k, std::vector<int>& rowe, int64_t max_swaps, double min_gain, int32_t* sel_out,
                              int32_t* out_idx, int32_t* in_idx, double* ratio, int64_t* n_swaps, int32_t* converged, double* t_ms) {
     EspXchEdgeSpace sp; sp.h = h;
-    const int m = h->m, ld = esp_relax_ld(h);
+    const int m = h->m, ld = esp_relax_route(h).ld;
     sp.K = (int)k; sp.fold = kEspDefaultFold; sp.sel_count = ld;
     sp.chunks = std::max(1, std::min((m + kBlock - 1) / kBlock, (kEspXchTargetGroups + sp.K - 1) / sp.K));
     sp.per = ((m + sp.chunks - 1) / sp.chunks + 1) & ~1;      // (even: a chunk starts on a 16-byte boundary of its rows)
@@ -187,7 +180,7 @@ inline int esp_exchange_edge(machip_esp* h, int64_t k, std::vector<int>& rowe, i
         esp_xe_release(h->xe);
         return stp;
     }
-    sp.E = E; sp.X = E->x; sp.V = E->view(); sp.P = E->grid(); sp.seeds = E->M - m;
+    sp.X = E->x; sp.V = E->view(); sp.P = E->grid(); sp.seeds = E->M - m;
     return esp_xch_run(h, sp, rowe, max_swaps, min_gain, sel_out, out_idx, in_idx, ratio, n_swaps, converged, t_ms);
 }
 

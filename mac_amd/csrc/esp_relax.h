@@ -19,10 +19,12 @@
 //   6. k_fw_final (partials of g.(s - x) and g.g, x_next = x + gamma (s - x)) and k_relax_scalars (F, dual, |g|).
 // The host reads three scalars and the pivot flag per iteration (the stop tests), nothing else.
 //
-// On a MACHIP_ESP_EDGE_RELAX handle steps 1-4 are those of esp_relax_edge.h instead -- N(x) = I + G D in the candidates' space,
-// its inverse and the gradient from it -- and steps 5-6, the reading of the scalars and the loop are the ones here.  On a
-// MACHIP_ESP_EDGE_RELAX_TREE handle they are those of esp_relax_edge_tree.h: the same N(x) over the candidates and the seeds of a
-// spanning tree, its Gram matrix stored, log det N(0) subtracted.
+// On a MACHIP_ESP_EDGE_RELAX handle the kernels of steps 1 and 4 are those of esp_relax_edge.h instead -- N(x) = I + G D in the
+// candidates' space and the gradient from its inverse -- on a MACHIP_ESP_EDGE_RELAX_TREE handle those of esp_relax_edge_tree.h:
+// the same N(x) over the candidates and the seeds of a spanning tree, its Gram matrix stored, log det N(0) subtracted.
+// Everything else is written once, here.  The space is a field of the handle (machip_esp::relax_space) and EspRelaxRoute
+// below is what follows from it -- columns, leading dimension, limit, messages; four places switch on it: esp_relax_limits,
+// esp_relax_prepare, esp_relax_eval_on and, in esp_exchange_edge.h, the loading of the Gram matrix (by whether G is stored).
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -35,7 +37,51 @@
 
 namespace machip {
 
+// What follows from the space of a handle's relaxation (machip_esp::relax_space), from the handle alone: nothing is allocated
+// before it is asked.  The one place that rounds up to 64, compares with the dense limit and words the spaces' messages.
+struct EspRelaxRoute {
+    EspRelaxSpace space;
+    int64_t cols;      // what the dense limit is on: num_nodes (an evaluation inverts the n - 1 reduced columns), m, m + r
+    int ld;            // leading dimension of the matrix an evaluation inverts: the handle's, or cols rounded up to 64 (at least 64)
+    bool oversize() const { return cols > kEspDenseMaxN; }
+    const char* lost_pivot() const {
+        return space == kEspRelaxNode ? "M(x) is not positive definite numerically (a non-positive Gauss-Jordan pivot)"
+                                      : "N(x) = I + G D has a non-positive Gauss-Jordan pivot (its leading minors are positive: lost numerically)";
+    }
+};
+
+inline EspRelaxRoute esp_relax_route(const machip_esp* h) {
+    EspRelaxRoute R{h->relax_space, h->n, h->ld};
+    switch (R.space) {
+    case kEspRelaxNode: return R;
+    case kEspRelaxEdge: R.cols = h->m; break;
+    case kEspRelaxEdgeTree: R.cols = (int64_t)h->m + h->tr->seeds; break;
+    }
+    R.ld = (int)((std::max<int64_t>(R.cols, 1) + kGjT - 1) / kGjT * kGjT);
+    return R;
+}
+
+// What the relaxation cannot do on this handle.
+inline int esp_relax_limits(const machip_esp* h) {
+    const EspRelaxRoute R = esp_relax_route(h);
+    // (tr: a MACHIP_ESP_MATRIX_FREE | MACHIP_ESP_SPANNING_TREE handle, esp_tree.h)
+    if (R.space == kEspRelaxNode && (h->form == kEspFormFree || h->tr))
+        return fail(MACHIP_BAD_ARG, "the relaxation inverts the dense M(x): not available on a MACHIP_ESP_MATRIX_FREE handle");
+    if (!R.oversize()) return MACHIP_OK;
+    switch (R.space) {
+    case kEspRelaxEdgeTree:
+        return fail(MACHIP_BAD_ARG, "MACHIP_ESP_EDGE_RELAX_TREE inverts the dense (m + r) x (m + r) N(x): candidates plus seeds must be <= 16384 (m = " +
+                                        std::to_string((int64_t)h->m) + ", r = " + std::to_string((int64_t)h->tr->seeds) + ")");
+    case kEspRelaxEdge:
+        return fail(MACHIP_BAD_ARG, "MACHIP_ESP_EDGE_RELAX inverts the dense m x m N(x): the number of candidates must be <= 16384 (m = " +
+                                        std::to_string(h->m) + ")");
+    default:
+        return fail(MACHIP_BAD_ARG, "the relaxation inverts the dense M(x) (no chain closed form): num_nodes must be <= 16384");
+    }
+}
+
 struct EspRelax {
+    EspRelaxRoute route;                     // of the handle, when the state was made
     double* bufC = nullptr;                  // the inverse's second buffer (the first is the handle's working copy `sig`)
     int *rowptr = nullptr, *ecol = nullptr, *tptr = nullptr, *tx = nullptr;     // incidence list by node (below)
     double* tw = nullptr;
@@ -44,9 +90,7 @@ struct EspRelax {
     SelState* st = nullptr;
     unsigned int* hist = nullptr;
     double logdet0 = 0.0;                    // log det M(0), by the same kernels in the same order (F(0) = 0 exactly)
-    int ld = 0;                              // leading dimension of the matrix an evaluation inverts (node space: the handle's)
-    EspEdge* ed = nullptr;                   // edge space (esp_relax_edge.h): N(x) instead of M(x); bufC .. tw above stay unused
-    EspEdgeTree* et = nullptr;               // edge space over a spanning tree (esp_relax_edge_tree.h): likewise
+    EspEdge* edge = nullptr;                 // both edge spaces (esp_relax_edge.h): N(x) instead of M(x); bufC .. tw and hist stay unused
 };
 
 // Row i of M(x): zeros, then entry q in [rowptr[i], rowptr[i + 1]) at column ecol[q] = sum over its terms t in
@@ -110,8 +154,7 @@ inline void esp_relax_release(machip_esp* h) {
     if (!r) return;
     void* bufs[] = {r->bufC, r->rowptr, r->ecol, r->tptr, r->tx, r->tw, r->xa, r->xb, r->part, r->ldet, r->scal, r->st, r->hist};
     for (void* q : bufs) if (q) (void)hipFree(q);
-    esp_edge_release(r->ed);
-    esp_edge_tree_release(r->et);
+    esp_edge_release(r->edge);
     delete r;
     h->rx = nullptr;
 }
@@ -156,119 +199,100 @@ inline int esp_relax_build_lists(machip_esp* h, EspRelax* r) {
     return MACHIP_OK;
 }
 
-// Steps 1-4 for the x in `x`: M(x) and its inverse in h->sig (the greedy's working copy: the last selection run's state is
-// gone, Sigma0 is not touched), the blocks' log-determinants in ldet[], the gradient in h->s (want_grad).
+// Steps 1-4 for the x in `x`: the space's matrix and its inverse (ld / 32 is even: the inverse ends where the matrix was
+// assembled), the blocks' log-determinants in ldet[], the gradient in h->s (want_grad).  Node space: in h->sig, the greedy's
+// working copy -- the last selection run's state is gone, Sigma0 is not touched.  Edge spaces: in the state's own bufN; neither
+// h->live nor h->pending is written, the greedy's last run stays what it was.
 inline int esp_relax_eval_on(machip_esp* h, const double* x, bool want_grad) {
     EspRelax* r = h->rx;
-    if (r->ed) return esp_edge_eval_on(h, r->ed, x, r->ldet, want_grad);
-    if (r->et) return esp_edge_tree_eval_on(h, r->et, x, r->ldet, want_grad);
+    const EspEdge* E = r->edge;
+    const EspRelaxSpace space = r->route.space;
+    const int ld = r->route.ld, m = h->m;
     hipStream_t st = h->stream;
-    h->live = false;
-    h->pending = 0;
+    double *src = nullptr, *dst = nullptr, *piv = nullptr;
     HIP_TRY(hipMemsetAsync(h->bad, 0, sizeof(int), st));
-    k_relax_assemble<<<h->ld, kBlock, 0, st>>>(h->sig, h->ld, r->rowptr, r->ecol, r->tptr, r->tw, r->tx, x);
-    double *src = h->sig, *dst = r->bufC;
-    h->gj_inverse<true>(src, dst, r->ldet);          // (ld / 32 is even: the inverse ends in h->sig)
-    if (want_grad && h->m) k_esp_scores<<<h->grid_m(), kBlock, 0, st>>>(h->view(), src, 0);
+    switch (space) {
+    case kEspRelaxNode:
+        h->live = false;
+        h->pending = 0;
+        src = h->sig; dst = r->bufC; piv = h->piv;
+        k_relax_assemble<<<ld, kBlock, 0, st>>>(src, ld, r->rowptr, r->ecol, r->tptr, r->tw, r->tx, x);
+        break;
+    case kEspRelaxEdge:
+        src = E->bufN; dst = E->bufC; piv = E->piv;
+        k_edge_assemble<<<ld, kBlock, 0, st>>>(src, ld, m, E->eu, E->ev, h->cw, h->R, x);
+        break;
+    case kEspRelaxEdgeTree:
+        src = E->bufN; dst = E->bufC; piv = E->piv;
+        k_edge_tree_assemble<<<ld, kBlock, 0, st>>>(src, E->G, ld, E->M, m, h->cw, h->tr->sw, x);
+        break;
+    }
+    h->gj_inverse_of<true>(src, dst, ld, piv, r->ldet);
+    if (want_grad && m) switch (space) {
+        case kEspRelaxNode: k_esp_scores<<<h->grid_m(), kBlock, 0, st>>>(h->view(), src, 0); break;
+        case kEspRelaxEdge: k_edge_grad<<<m, kBlock, 0, st>>>(src, ld, m, E->eu, E->ev, h->cw, h->R, h->s); break;
+        case kEspRelaxEdgeTree: k_edge_tree_grad<<<m, kBlock, 0, st>>>(src, E->G, ld, E->M, h->cw, h->s); break;
+    }
     HIP_TRY(hipGetLastError());
     return MACHIP_OK;
 }
 
-// Step 5 on the gradient in h->s: the launch sequence of machip_lp_topk's select (machip.hip: select_on), into r->st.
+// Step 5 on the gradient in h->s, into r->st: machip_lp_topk's select and its tie rule (kernels.h: sel_launch).
 inline int esp_relax_select(machip_esp* h, long k) {
     EspRelax* r = h->rx;
-    const long m = h->m;
-    if (m <= kSelSmallMax) {
-        k_sel_small<<<1, 1024, 0, h->stream>>>(h->s, m, (long long)k, r->st, 0);
-    } else {
-        if (!r->hist) return fail(MACHIP_BAD_ARG, "the multi-launch select has no histogram on this handle (edge space allocates none: m <= 16384 must stay below kSelSmallMax)");
-        constexpr int B = 1024, U = 4;
-        const int grid = (int)std::max<long>(1, std::min<long>(128, (m + (long)B * U - 1) / ((long)B * U)));
-        k_sel_init<<<1, 1024, 0, h->stream>>>(r->st, (long long)k, r->hist, 6 * kBins);
-        for (int pass = 0; pass < 6; ++pass) k_sel_pass<U, B><<<grid, B, 0, h->stream>>>(h->s, m, pass, r->hist, r->st);
-        k_sel_ties<<<1, 1024, 0, h->stream>>>(h->s, m, r->st, 0);
-    }
-    HIP_TRY(hipGetLastError());
-    return MACHIP_OK;
+    if (h->m > kSelSmallMax && !r->hist) return fail(MACHIP_BAD_ARG, "the multi-launch select has no histogram on this handle (edge space allocates none: m <= 16384 must stay below kSelSmallMax)");
+    return sel_launch(h->stream, h->s, h->m, k, r->st, r->hist, 0, true, false);
 }
 
 // F (and the other two scalars when `np` partials of k_fw_final are there) to the host, with the pivot flag.
 inline int esp_relax_read(machip_esp* h, int np, double* out3) {
     EspRelax* r = h->rx;
     int hbad = 0;
-    k_relax_scalars<<<1, kBlock, 0, h->stream>>>(r->ldet, r->ld / kGjB, r->logdet0, r->part, np, r->scal);
+    k_relax_scalars<<<1, kBlock, 0, h->stream>>>(r->ldet, r->route.ld / kGjB, r->logdet0, r->part, np, r->scal);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(out3, r->scal, sizeof(double) * 3, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipMemcpyAsync(&hbad, h->bad, sizeof(int), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
-    if (hbad && (r->ed || r->et)) return fail(MACHIP_NOT_CONVERGED, "N(x) = I + G D has a non-positive Gauss-Jordan pivot (its leading minors are positive: lost numerically)");
-    if (hbad) return fail(MACHIP_NOT_CONVERGED, "M(x) is not positive definite numerically (a non-positive Gauss-Jordan pivot)");
+    if (hbad) return fail(MACHIP_NOT_CONVERGED, r->route.lost_pivot());
     return MACHIP_OK;
 }
 
-// The leading dimension an edge handle's relaxation inverts at, from the handle alone (node space: 0 -- machip_esp_relax_info's).
-inline int esp_relax_ld(const machip_esp* h) {
-    return h->edge_tree ? esp_edge_tree_ld((int64_t)h->m + h->tr->seeds) : h->edge_relax ? (std::max(h->m, 1) + kGjT - 1) / kGjT * kGjT : 0;
-}
-
-// the matrix an evaluation would invert is beyond the dense limit (the one statement of the three limits)
-inline bool esp_relax_oversize(const machip_esp* h) {
-    return h->edge_tree ? (int64_t)h->m + h->tr->seeds > kEspDenseMaxN : h->edge_relax ? h->m > kEspDenseMaxN : h->n > kEspDenseMaxN;
-}
-
-// What the relaxation cannot do on this handle, decided from the handle alone (nothing is allocated before it is asked).
-inline int esp_relax_limits(const machip_esp* h) {
-    if (h->edge_tree) {
-        if (esp_relax_oversize(h))
-            return fail(MACHIP_BAD_ARG, "MACHIP_ESP_EDGE_RELAX_TREE inverts the dense (m + r) x (m + r) N(x): candidates plus seeds must be <= 16384 (m = " +
-                                            std::to_string((int64_t)h->m) + ", r = " + std::to_string((int64_t)h->tr->seeds) + ")");
-        return MACHIP_OK;
-    }
-    if (h->edge_relax) {
-        if (esp_relax_oversize(h))
-            return fail(MACHIP_BAD_ARG, "MACHIP_ESP_EDGE_RELAX inverts the dense m x m N(x): the number of candidates must be <= 16384 (m = " +
-                                            std::to_string(h->m) + ")");
-        return MACHIP_OK;
-    }
-    if (h->form == kEspFormFree || h->tr)      // (tr: a MACHIP_ESP_MATRIX_FREE | MACHIP_ESP_SPANNING_TREE handle, esp_tree.h)
-        return fail(MACHIP_BAD_ARG, "the relaxation inverts the dense M(x): not available on a MACHIP_ESP_MATRIX_FREE handle");
-    if (esp_relax_oversize(h))
-        return fail(MACHIP_BAD_ARG, "the relaxation inverts the dense M(x) (no chain closed form): num_nodes must be <= 16384");
-    return MACHIP_OK;
-}
-
-// First relaxation call on a handle.  Node space: the third buffer, the incidence list, log det M(0).  Edge space: the state of
-// esp_relax_edge.h (log det N(0) = log det I = 0: nothing to evaluate).  Edge space over a spanning tree: the state of
-// esp_relax_edge_tree.h with its Gram matrix, and log det N(0) -- the seeds' -- by one evaluation at x = 0.
+// First relaxation call on a handle: the limits, then the space's own resources, the ones every space has, and log det of the
+// matrix at x = 0 by one evaluation there -- except on the chain edge route, where N(0) = I: ldet is zeroed (what
+// k_relax_scalars sums when machip_esp_relax_inner is the handle's first call) and the ld^3 inverse is not paid.  Neither edge
+// space has a histogram or an incidence list: m <= 16 384 is below kSelSmallMax, the multi-launch select is never taken.
 inline int esp_relax_prepare(machip_esp* h) {
     ST_TRY(esp_relax_limits(h));
     HIP_TRY(hipSetDevice(h->device));
     if (h->rx) return MACHIP_OK;
-    EspRelax* r = new EspRelax();
+    EspRelax* r = new EspRelax{esp_relax_route(h)};
     h->rx = r;
     auto body = [&]() -> int {
-        if (h->edge_relax) {
-            r->ed = new EspEdge();
-            ST_TRY(esp_edge_prepare(h, r->ed));
+        const EspRelaxRoute& R = r->route;
+        const size_t ld = (size_t)R.ld, ms = (size_t)std::max(h->m, 1);
+        bool identity_at_0 = false;
+        switch (R.space) {
+        case kEspRelaxNode:
+            ST_TRY(dev_alloc(&r->bufC, ld * ld));
+            ST_TRY(dev_alloc(&r->hist, (size_t)6 * kBins));
+            ST_TRY(esp_relax_build_lists(h, r));
+            break;
+        case kEspRelaxEdge:
+            ST_TRY(esp_edge_alloc(r->edge = new EspEdge(), (int)R.cols, R.ld, false));
+            ST_TRY(esp_edge_chain_ends(h, r->edge));
+            identity_at_0 = true;
+            break;
+        case kEspRelaxEdgeTree:
+            ST_TRY(esp_edge_alloc(r->edge = new EspEdge(), (int)R.cols, R.ld, true));
+            ST_TRY(esp_edge_tree_gram(h, r->edge));
+            break;
         }
-        if (h->edge_tree) {
-            r->et = new EspEdgeTree();
-            ST_TRY(esp_edge_tree_prepare(h, r->et));
-        }
-        r->ld = r->ed ? r->ed->ld : r->et ? r->et->ld : h->ld;
-        const size_t ld = (size_t)r->ld, ms = (size_t)std::max(h->m, 1);
-        if (!r->ed && !r->et) ST_TRY(dev_alloc(&r->bufC, ld * ld));
         ST_TRY(dev_alloc(&r->xa, ms)); ST_TRY(dev_alloc(&r->xb, ms));
         ST_TRY(dev_alloc(&r->part, (size_t)2 * kMaxGrid)); ST_TRY(dev_alloc(&r->ldet, ld / kGjB)); ST_TRY(dev_alloc(&r->scal, 4));
         ST_TRY(dev_alloc(&r->st, 1));
-        if (r->ed) {                             // (m <= 16 384 is below kSelSmallMax: the multi-launch select's histogram is never used)
-            // log det N(0) = 0 in every block: what k_relax_scalars sums when machip_esp_relax_inner is the handle's first call
+        if (identity_at_0) {
             HIP_TRY(hipMemsetAsync(r->ldet, 0, sizeof(double) * (ld / kGjB), h->stream));
             return MACHIP_OK;
-        }
-        if (!r->et) {                            // (edge space over a tree: m <= 16 384 as above, no incidence list)
-            ST_TRY(dev_alloc(&r->hist, (size_t)6 * kBins));
-            ST_TRY(esp_relax_build_lists(h, r));
         }
         HIP_TRY(hipMemsetAsync(r->xa, 0, sizeof(double) * ms, h->stream));
         ST_TRY(esp_relax_eval_on(h, r->xa, false));
@@ -310,7 +334,7 @@ inline int esp_relax_eval(machip_esp* h, const double* x, double* F_out, double*
 // machip_esp_relax_run after its NULL checks: Frank-Wolfe from x_inout, steps 1-6 and three scalars to the host per iteration
 inline int esp_relax_run(machip_esp* h, int64_t k, int max_iters, double gap_tol, double grad_tol, double* x_inout, double* f_traj,
                          double* dual_traj, double* gnorm_traj, int* iters_out, double* upper_out) {
-    if (esp_relax_oversize(h)) return esp_relax_prepare(h);      // (the limit's message, nothing allocated)
+    if (esp_relax_route(h).oversize()) return esp_relax_limits(h);      // (the refusal ahead of the argument checks, nothing allocated)
     if (k <= 0 || k > h->m) return fail(MACHIP_BAD_ARG, "k must be in [1, m] (m = " + std::to_string(h->m) + " candidates)");
     ST_TRY(esp_relax_check_x(h, x_inout));
     ST_TRY(esp_relax_prepare(h));
@@ -353,9 +377,33 @@ inline int esp_relax_inner(machip_esp* h, const double* a, const double* b, doub
         HIP_TRY(hipMemcpyAsync(r->xb, b, mb, hipMemcpyHostToDevice, h->stream));
     }
     k_relax_inner<<<grid, kBlock, 0, h->stream>>>(r->xa, r->xb, h->m, r->part);
-    k_relax_scalars<<<1, kBlock, 0, h->stream>>>(r->ldet, r->ld / kGjB, r->logdet0, r->part, grid, r->scal);
+    k_relax_scalars<<<1, kBlock, 0, h->stream>>>(r->ldet, r->route.ld / kGjB, r->logdet0, r->part, grid, r->scal);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(out, r->scal + 3, sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    return MACHIP_OK;
+}
+
+// machip_esp_relax_info after its NULL checks.  A node-space handle reports ld = 0 until its first relaxation call.
+inline int esp_relax_info(const machip_esp* h, int32_t* info2) {
+    const EspRelaxRoute R = esp_relax_route(h);
+    info2[0] = R.space;
+    info2[1] = R.space == kEspRelaxNode && !h->rx ? 0 : R.ld;
+    return MACHIP_OK;
+}
+
+// machip_esp_relax_gram after its NULL checks: the M x M corner of the stored Gram matrix, made by the first relaxation call
+inline int esp_relax_gram(machip_esp* h, double* G_out, int64_t M) {
+    const EspRelaxRoute R = esp_relax_route(h);
+    if (R.space != kEspRelaxEdgeTree) return fail(MACHIP_BAD_ARG, "the stored Gram matrix belongs to a MACHIP_ESP_EDGE_RELAX_TREE handle: this handle keeps none");
+    if (M != R.cols)
+        return fail(MACHIP_BAD_ARG, "M must be m + r = " + std::to_string((long long)R.cols) + " (m = " + std::to_string(h->m) + " candidates, r = " +
+                                        std::to_string(h->tr->seeds) + " seeds), not " + std::to_string((long long)M));
+    ST_TRY(esp_relax_prepare(h));
+    if (!M) return MACHIP_OK;
+    const EspEdge* E = h->rx->edge;
+    HIP_TRY(hipMemcpy2DAsync(G_out, sizeof(double) * (size_t)M, E->G, sizeof(double) * (size_t)E->ld, sizeof(double) * (size_t)M, (size_t)M,
+                             hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     return MACHIP_OK;
 }

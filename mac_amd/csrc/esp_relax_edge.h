@@ -20,9 +20,10 @@
 //   3. k_edge_grad: row e of N^-1 against column e of G, which is built by the function step 1 built it with (the same bits);
 //      8 ld m bytes read once;
 //   4. the LP vertex, k_fw_final and k_relax_scalars of esp_relax.h (logdet0 = 0, ld / 32 blocks).
-// State: lo, hi (int32[m]), two ld x ld buffers, 2 x 32 x 32 pivots.  w is the handle's cw and R the prefix array the matrix-free
-// greedy uploaded: nothing of size n is allocated here.  The greedy's history, flags and pending count are never written; the
-// gradient goes to the handle's score array, which the greedy rebuilds from R (and its history) at every use.
+// State: the one EspEdge below, shared with esp_relax_edge_tree.h -- the columns' two int32 endpoint arrays (here lo, hi), two
+// ld x ld buffers, 2 x 32 x 32 pivots, and no stored G: esp_edge_G is the closed form.  w is the handle's cw and R the prefix array
+// the matrix-free greedy uploaded: nothing of size n is allocated here.  The greedy's history, flags and pending count are never
+// written; the gradient goes to the handle's score array, which the greedy rebuilds from R (and its history) at every use.
 #pragma once
 #include <algorithm>
 #include <vector>
@@ -32,9 +33,13 @@
 
 namespace machip {
 
+// The state of the edge-space relaxation on either route (esp_relax.h makes it, evaluates on it and releases it;
+// esp_exchange_edge.h keeps its R in bufN).
 struct EspEdge {
-    int ld = 0;                              // m rounded up to a multiple of 64 (at least 64)
-    int *lo = nullptr, *hi = nullptr;        // reduced endpoints (node - 1; -1 = node 0), lo <= hi
+    int M = 0, ld = 0;                       // columns (chain: m; tree: m + r) and the route's leading dimension
+    int *eu = nullptr, *ev = nullptr;        // the columns' endpoints, int32[M].  Chain: reduced (node - 1; -1 = node 0), eu <= ev
+                                             // (lo, hi of the kernels below); tree: preorder numbers (pu, pv of esp_relax_edge_tree.h)
+    double* G = nullptr;                     // the stored Gram matrix, ld x ld (tree); null on the chain, where esp_edge_G is G
     double *bufN = nullptr, *bufC = nullptr; // N(x) / its inverse, and the elimination's second buffer
     double* piv = nullptr;                   // look-ahead pivot blocks (2 x 32 x 32)
 };
@@ -96,42 +101,34 @@ __global__ __launch_bounds__(kBlock) void k_edge_grad(const double* __restrict__
 
 inline void esp_edge_release(EspEdge* E) {
     if (!E) return;
-    void* bufs[] = {E->lo, E->hi, E->bufN, E->bufC, E->piv};
+    void* bufs[] = {E->eu, E->ev, E->G, E->bufN, E->bufC, E->piv};
     for (void* q : bufs) if (q) (void)hipFree(q);
     delete E;
 }
 
-// The route's own state for the handle's candidates (the caller owns *E and releases it on failure).
-inline int esp_edge_prepare(machip_esp* h, EspEdge* E) {
-    const int m = h->m;
-    E->ld = (std::max(m, 1) + kGjT - 1) / kGjT * kGjT;
-    const size_t ld = (size_t)E->ld, ms = (size_t)std::max(m, 1);
-    ST_TRY(dev_alloc(&E->lo, ms)); ST_TRY(dev_alloc(&E->hi, ms));
-    ST_TRY(dev_alloc(&E->bufN, ld * ld)); ST_TRY(dev_alloc(&E->bufC, ld * ld));
+// What both routes allocate for M columns at leading dimension ld (the caller owns *E and releases it on failure).
+inline int esp_edge_alloc(EspEdge* E, int M, int ld, bool stored_gram) {
+    E->M = M; E->ld = ld;
+    const size_t l2 = (size_t)ld * (size_t)ld, Ms = (size_t)std::max(M, 1);
+    ST_TRY(dev_alloc(&E->eu, Ms)); ST_TRY(dev_alloc(&E->ev, Ms));
+    if (stored_gram) ST_TRY(dev_alloc(&E->G, l2));
+    ST_TRY(dev_alloc(&E->bufN, l2)); ST_TRY(dev_alloc(&E->bufC, l2));
     ST_TRY(dev_alloc(&E->piv, (size_t)2 * kGjB * kGjB));
-    if (m) {
-        std::vector<int> lo((size_t)m), hi((size_t)m);
-        for (int e = 0; e < m; ++e) {
-            lo[(size_t)e] = std::min(h->hci[(size_t)e], h->hcj[(size_t)e]) - 1;
-            hi[(size_t)e] = std::max(h->hci[(size_t)e], h->hcj[(size_t)e]) - 1;
-        }
-        HIP_TRY(hipMemcpyAsync(E->lo, lo.data(), sizeof(int) * (size_t)m, hipMemcpyHostToDevice, h->stream));
-        HIP_TRY(hipMemcpyAsync(E->hi, hi.data(), sizeof(int) * (size_t)m, hipMemcpyHostToDevice, h->stream));
-        HIP_TRY(hipStreamSynchronize(h->stream));          // (host staging goes out of scope)
-    }
     return MACHIP_OK;
 }
 
-// Steps 1-3 for the x in `x`: N(x) and its inverse in E->bufN, the blocks' log-determinants in ldet[], the gradient in h->s
-// (want_grad).  Neither h->live nor h->pending is written: the greedy's last run stays what it was.
-inline int esp_edge_eval_on(machip_esp* h, EspEdge* E, const double* x, double* ldet, bool want_grad) {
-    hipStream_t st = h->stream;
-    HIP_TRY(hipMemsetAsync(h->bad, 0, sizeof(int), st));
-    k_edge_assemble<<<E->ld, kBlock, 0, st>>>(E->bufN, E->ld, h->m, E->lo, E->hi, h->cw, h->R, x);
-    double *src = E->bufN, *dst = E->bufC;
-    h->gj_inverse_of<true>(src, dst, E->ld, E->piv, ldet);          // (ld / 32 is even: the inverse ends in E->bufN)
-    if (want_grad && h->m) k_edge_grad<<<h->m, kBlock, 0, st>>>(src, E->ld, h->m, E->lo, E->hi, h->cw, h->R, h->s);
-    HIP_TRY(hipGetLastError());
+// The chain route's part of the state: lo, hi from the candidates' lists as given.
+inline int esp_edge_chain_ends(machip_esp* h, EspEdge* E) {
+    const size_t m = (size_t)h->m;
+    if (!m) return MACHIP_OK;
+    std::vector<int> lo(m), hi(m);
+    for (size_t e = 0; e < m; ++e) {
+        lo[e] = std::min(h->hci[e], h->hcj[e]) - 1;
+        hi[e] = std::max(h->hci[e], h->hcj[e]) - 1;
+    }
+    HIP_TRY(hipMemcpyAsync(E->eu, lo.data(), sizeof(int) * m, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(E->ev, hi.data(), sizeof(int) * m, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));          // (host staging goes out of scope)
     return MACHIP_OK;
 }
 

@@ -18,10 +18,10 @@
 //   2. gj_inverse_of<true> (esp.h) on the route's own N / second buffer / look-ahead pivot buffer;
 //   3. k_edge_tree_grad: row e of N^-1 against row e of G (= column e, G being bit-symmetric: contiguous); 16 ld m bytes read;
 //   4. the LP vertex, k_fw_final and k_relax_scalars of esp_relax.h over the m candidates (logdet0 = log det N(0)).
-// State: three ld x ld buffers (24 ld^2 bytes), 2 x 32 x 32 pivots, the int32 preorder endpoints of the M columns.  The candidates'
-// weights are the handle's cw, the seeds' the tree state's sw; nothing of size n is allocated beyond the tree handle's tables.
-// The greedy's history, seeds, s0, pending count and flags are never written, and the seeds need not have been run; the gradient
-// goes to the handle's score array, which the greedy rebuilds at every use.
+// State: the EspEdge of esp_relax_edge.h with G stored -- three ld x ld buffers (24 ld^2 bytes), 2 x 32 x 32 pivots, the int32
+// preorder endpoints of the M columns.  The candidates' weights are the handle's cw, the seeds' the tree state's sw; nothing of size
+// n is allocated beyond the tree handle's tables.  The greedy's history, seeds, s0, pending count and flags are never written, and
+// the seeds need not have been run; the gradient goes to the handle's score array, which the greedy rebuilds at every use.
 #pragma once
 #include <algorithm>
 
@@ -29,13 +29,6 @@
 #include "esp_tree.h"
 
 namespace machip {
-
-struct EspEdgeTree {
-    int ld = 0, M = 0;                                        // M = m + r columns; ld = M rounded up to a multiple of 64 (at least 64)
-    int *pu = nullptr, *pv = nullptr;                         // preorder numbers of the columns' endpoints (int32[M])
-    double *G = nullptr, *bufN = nullptr, *bufC = nullptr;    // the Gram matrix; N(x) / its inverse; the elimination's second buffer
-    double* piv = nullptr;                                    // look-ahead pivot blocks (2 x 32 x 32)
-};
 
 // ---- G, once per handle.  grid = ld: workgroup e owns row e, lanes own the columns f.  All four lifting chains start from the
 // row's two endpoints (wave-uniform starts; only ancestors of u_e and v_e are ever read, so the lines stay in L2) and climb side by
@@ -115,15 +108,6 @@ __global__ __launch_bounds__(kBlock) void k_edge_tree_grad(const double* __restr
     if (threadIdx.x == 0) g[e] = w[e] * acc;
 }
 
-inline void esp_edge_tree_release(EspEdgeTree* E) {
-    if (!E) return;
-    void* bufs[] = {E->pu, E->pv, E->G, E->bufN, E->bufC, E->piv};
-    for (void* q : bufs) if (q) (void)hipFree(q);
-    delete E;
-}
-
-inline int esp_edge_tree_ld(int64_t M) { return (int)((std::max<int64_t>(M, 1) + kGjT - 1) / kGjT * kGjT); }
-
 // ---- the columns' endpoints by preorder number, from the reduced node ids (node - 1) the handle and the tree state keep ----
 __global__ __launch_bounds__(kBlock) void k_edge_tree_ends(int* __restrict__ pu, int* __restrict__ pv, int M, int m, const int* __restrict__ cu,
                                                            const int* __restrict__ cv, const int* __restrict__ su, const int* __restrict__ sv,
@@ -135,31 +119,12 @@ __global__ __launch_bounds__(kBlock) void k_edge_tree_ends(int* __restrict__ pu,
     }
 }
 
-// The route's own state and the Gram matrix (the caller owns *E and releases it on failure).
-inline int esp_edge_tree_prepare(machip_esp* h, EspEdgeTree* E) {
+// The tree route's part of the state: the columns' preorder endpoints and the Gram matrix from them.
+inline int esp_edge_tree_gram(machip_esp* h, EspEdge* E) {
     const EspTreeState* t = h->tr;
-    E->M = h->m + t->seeds;
-    E->ld = esp_edge_tree_ld(E->M);
-    const size_t ld = (size_t)E->ld, Ms = (size_t)std::max(E->M, 1);
-    ST_TRY(dev_alloc(&E->pu, Ms)); ST_TRY(dev_alloc(&E->pv, Ms));
-    ST_TRY(dev_alloc(&E->G, ld * ld)); ST_TRY(dev_alloc(&E->bufN, ld * ld)); ST_TRY(dev_alloc(&E->bufC, ld * ld));
-    ST_TRY(dev_alloc(&E->piv, (size_t)2 * kGjB * kGjB));
     hipStream_t st = h->stream;
-    if (E->M) k_edge_tree_ends<<<std::max(1, std::min(kMaxGrid, (E->M + kBlock - 1) / kBlock)), kBlock, 0, st>>>(E->pu, E->pv, E->M, h->m, h->cu, h->cv, t->su, t->sv, t->pre);
-    k_edge_tree_gram<<<E->ld, kBlock, 0, st>>>(E->G, E->ld, E->M, E->pu, E->pv, t->view(h->n));
-    HIP_TRY(hipGetLastError());
-    return MACHIP_OK;
-}
-
-// Steps 1-3 for the x in `x`: N(x) and its inverse in E->bufN, the blocks' log-determinants in ldet[], the gradient in h->s
-// (want_grad).  Neither h->live nor h->pending is written: the greedy's last run stays what it was.
-inline int esp_edge_tree_eval_on(machip_esp* h, EspEdgeTree* E, const double* x, double* ldet, bool want_grad) {
-    hipStream_t st = h->stream;
-    HIP_TRY(hipMemsetAsync(h->bad, 0, sizeof(int), st));
-    k_edge_tree_assemble<<<E->ld, kBlock, 0, st>>>(E->bufN, E->G, E->ld, E->M, h->m, h->cw, h->tr->sw, x);
-    double *src = E->bufN, *dst = E->bufC;
-    h->gj_inverse_of<true>(src, dst, E->ld, E->piv, ldet);          // (ld / 32 is even: the inverse ends in E->bufN)
-    if (want_grad && h->m) k_edge_tree_grad<<<h->m, kBlock, 0, st>>>(src, E->G, E->ld, E->M, h->cw, h->s);
+    if (E->M) k_edge_tree_ends<<<std::max(1, std::min(kMaxGrid, (E->M + kBlock - 1) / kBlock)), kBlock, 0, st>>>(E->eu, E->ev, E->M, h->m, h->cu, h->cv, t->su, t->sv, t->pre);
+    k_edge_tree_gram<<<E->ld, kBlock, 0, st>>>(E->G, E->ld, E->M, E->eu, E->ev, t->view(h->n));
     HIP_TRY(hipGetLastError());
     return MACHIP_OK;
 }

@@ -6,6 +6,8 @@
 // one partial per workgroup, re-reduced in fixed order by the consumer kernel (bit-
 // reproducible; no floating-point atomics anywhere).
 #pragma once
+#include <algorithm>
+
 #include "common.h"
 
 namespace machip {
@@ -1679,6 +1681,30 @@ __global__ void k_sel_init(SelState* st, long long k, unsigned int* __restrict__
         st->prefix = 0; st->kk = k; st->cnt_eq = 0; st->T = 0; st->tie_limit = -1; st->k = k;
         for (int i = 0; i < 8; ++i) st->ticket[i] = 0;
     }
+}
+
+// The select's launch sequence, the one place it is written: the k-th largest of keys[0..m), 0 <= k <= m, into *st (threshold,
+// remaining rank, tie rule).  small_ok: short key vectors take the one-launch form (hist may then be null).  hist0_done: the
+// first digit's histogram has been counted by the producer of the keys (k_grad<true>) behind a k_sel_init.
+inline int sel_launch(hipStream_t stream, const double* keys, long m, long k, SelState* st, unsigned int* hist, int prefer_high,
+                      bool small_ok, bool hist0_done) {
+    if (m <= kSelSmallMax && small_ok) {      // short key vectors: the whole select in one launch
+        k_sel_small<<<1, 1024, 0, stream>>>(keys, m, (long long)k, st, prefer_high);
+        HIP_TRY(hipGetLastError());
+        return MACHIP_OK;
+    }
+    if (!hist0_done) k_sel_init<<<1, 1024, 0, stream>>>(st, (long long)k, hist, 6 * kBins);
+    if (k > 0) {
+        // few, large workgroups: a dense digit costs one returning device-scope atomic per non-empty bin and workgroup (above)
+        // (measured at configs[3], 16 MB of keys: 512 x 256 threads 17 us per dense pass, 128 x 1 024 threads 10 us)
+        constexpr int B = 1024, U = 4;
+        const int grid = (int)std::max<long>(1, std::min<long>(128, (m + (long)B * U - 1) / ((long)B * U)));
+        if (hist0_done) k_sel_close0<<<1, 1024, 0, stream>>>(hist, st);
+        for (int pass = hist0_done ? 1 : 0; pass < 6; ++pass) k_sel_pass<U, B><<<grid, B, 0, stream>>>(keys, m, pass, hist, st);
+    }
+    k_sel_ties<<<1, 1024, 0, stream>>>(keys, m, st, prefer_high);
+    HIP_TRY(hipGetLastError());
+    return MACHIP_OK;
 }
 
 }  // namespace machip

@@ -324,30 +324,10 @@ int alloc_common(machip_problem* p, int vbudget_mb = 0) {
     return MACHIP_OK;
 }
 
-// k-th largest of keys[0..m): threshold, remaining rank and tie rule into *st.
-// hist0_done: the first digit's histogram has been counted by the producer of the keys (k_grad<true>) behind a k_sel_init.
+// k-th largest of keys[0..m), k clamped to [0, m]: kernels.h's sel_launch on the problem's histogram, under option sel_small.
 int select_on(machip_problem* p, const double* keys, long k, SelState* st, int prefer_high, bool hist0_done = false) {
     const Options& opt = p->sol.opt;
-    const long m = p->m;
-    if (k < 0) k = 0;
-    if (k > m) k = m;
-    if (m <= kSelSmallMax && OPT(sel_small, 1)) {      // short key vectors: the whole select in one launch
-        k_sel_small<<<1, 1024, 0, p->stream>>>(keys, m, (long long)k, st, prefer_high);
-        HIP_TRY(hipGetLastError());
-        return MACHIP_OK;
-    }
-    if (!hist0_done) k_sel_init<<<1, 1024, 0, p->stream>>>(st, (long long)k, p->hist, 6 * kBins);
-    if (k > 0) {
-        // few, large workgroups: a dense digit costs one returning device-scope atomic per non-empty bin and workgroup (kernels.h)
-        // (measured at configs[3], 16 MB of keys: 512 x 256 threads 17 us per dense pass, 128 x 1 024 threads 10 us)
-        constexpr int B = 1024, U = 4;
-        const int grid = (int)std::max<long>(1, std::min<long>(128, (m + (long)B * U - 1) / ((long)B * U)));
-        if (hist0_done) k_sel_close0<<<1, 1024, 0, p->stream>>>(p->hist, st);
-        for (int pass = hist0_done ? 1 : 0; pass < 6; ++pass) k_sel_pass<U, B><<<grid, B, 0, p->stream>>>(keys, m, pass, p->hist, st);
-    }
-    k_sel_ties<<<1, 1024, 0, p->stream>>>(keys, m, st, prefer_high);
-    HIP_TRY(hipGetLastError());
-    return MACHIP_OK;
+    return sel_launch(p->stream, keys, p->m, std::max(0l, std::min(k, p->m)), st, p->hist, prefer_high, OPT(sel_small, 1) != 0, hist0_done);
 }
 
 int select_topk(machip_problem* p, long k, bool hist0_done = false) { return select_on(p, p->g, k, p->sel, 0, hist0_done); }
@@ -1582,8 +1562,7 @@ static int esp_create(int device, int64_t n, int64_t n_fixed, const int32_t* fi,
     machip_esp* h = new machip_esp();
     h->device = device; h->n = (int)n; h->np = (int)n - 1; h->m = (int)m; h->fold = mfree ? 0 : fold; h->beta = fixed.beta;
     h->form = tree ? kEspFormTree : mfree ? kEspFormFree : fixed.chain ? 0 : 1;
-    h->edge_relax = (flags & MACHIP_ESP_EDGE_RELAX) != 0;
-    h->edge_tree = (flags & MACHIP_ESP_EDGE_RELAX_TREE) != 0;
+    h->relax_space = (flags & MACHIP_ESP_EDGE_RELAX_TREE) ? kEspRelaxEdgeTree : (flags & MACHIP_ESP_EDGE_RELAX) ? kEspRelaxEdge : kEspRelaxNode;
     h->free_split = (int)std::max(0l, std::min<long>(default_options().get(kOpt_esp_free_split, 0), kEspFreeMaxSplit));
     h->ld = (h->np + kGjT - 1) / kGjT * kGjT;
     h->hfi.assign(fi, fi + n_fixed); h->hfj.assign(fj, fj + n_fixed); h->hfw.assign(fw, fw + n_fixed);
@@ -1706,25 +1685,12 @@ int machip_esp_relax_inner(machip_esp* h, const double* a, const double* b, doub
 
 int machip_esp_relax_info(machip_esp* h, int32_t* info2) {
     if (!h || !info2) return fail(MACHIP_BAD_ARG, "NULL handle or output");
-    info2[0] = h->edge_tree ? 2 : h->edge_relax ? 1 : 0;
-    info2[1] = h->rx ? h->rx->ld : esp_relax_ld(h);
-    return MACHIP_OK;
+    return esp_relax_info(h, info2);
 }
 
 int machip_esp_relax_gram(machip_esp* h, double* G_out, int64_t M) {
     if (!h || !G_out) return fail(MACHIP_BAD_ARG, "NULL handle or output");
-    if (!h->edge_tree) return fail(MACHIP_BAD_ARG, "the stored Gram matrix belongs to a MACHIP_ESP_EDGE_RELAX_TREE handle: this handle keeps none");
-    const int64_t cols = (int64_t)h->m + h->tr->seeds;
-    if (M != cols)
-        return fail(MACHIP_BAD_ARG, "M must be m + r = " + std::to_string((long long)cols) + " (m = " + std::to_string(h->m) + " candidates, r = " +
-                                        std::to_string(h->tr->seeds) + " seeds), not " + std::to_string((long long)M));
-    ST_TRY(esp_relax_prepare(h));
-    if (!M) return MACHIP_OK;
-    const EspEdgeTree* E = h->rx->et;
-    HIP_TRY(hipMemcpy2DAsync(G_out, sizeof(double) * (size_t)M, E->G, sizeof(double) * (size_t)E->ld, sizeof(double) * (size_t)M, (size_t)M,
-                             hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    return MACHIP_OK;
+    return esp_relax_gram(h, G_out, M);
 }
 
 // ---- GreedyEig (eig.h; the routes without Sigma: eig_free.h, eig_free_tree.h; the three together: eig_routes.h) ----

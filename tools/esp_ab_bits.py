@@ -9,8 +9,11 @@ case and the array named.  Times (t_ms) are left out.  The cases are the smalles
 wrong: the dense greedy (chain form at ld = 192 with 63 padding rows, fold 4, budgets [3, 11] and a restart; Gauss-Jordan form at
 ld = 128), the chain-free greedy (K = 40: one slice up to pick 31, two from 32 on; esp_free_split = 2; a grown history at K = 60),
 the tree greedy (5 seeds, carried over when the history grows), the dense exchange (folds inside rounds, LDS and global rows,
-max_swaps = 0), the edge-space exchange (chain; tree with the seeds as forced picks) and five Frank-Wolfe iterations in the three
-spaces, with relax_inner as a handle's first call.
+max_swaps = 0), the edge-space exchange (chain; tree with the seeds as forced picks; as a handle's first call with relax_run after
+it) and the relaxation in the three spaces: five Frank-Wolfe iterations, relax_inner as a handle's first call, relax_eval with
+and without the gradient (in edge space at x = 0 too), relax_info before and after the first call, relax_gram as a handle's
+first call, one iteration through the multi-launch select (m = 40 000), and the refusals with their messages as byte arrays
+(where a call breaks two rules, the message says which check comes first).
 
 The child / save / compare harness is `main(argv, cases, script)`: another family's tool (tools/eig_ab_bits.py) passes its own case
 set and file, and gets the same rules -- NAME_OUT=DIR for a tool NAME.py."""
@@ -40,6 +43,10 @@ def cases():
 
     def put_select(case, r):
         put(case, order=r[0], gain=r[1])
+
+    def relax_info(h):      # (space, ld) as integers
+        i = h.relax_info()
+        return [("node", "edge", "edge_tree").index(i["form"]), i["ld"]]
 
     def put_xch(case, r):
         put(case, **{k: r[k] for k in ("selection", "out", "in", "ratios", "swaps", "converged")})
@@ -98,6 +105,57 @@ def cases():
         r = h.relax_run(k, np.full(m, k / m), max_iters=5, gap_tol=0.0, grad_tol=0.0)
         put(f"relax_{tag}/run", **r)
         put(f"relax_{tag}", inner_after_run=h.relax_inner(a, b))
+
+        h = _lib.Esp(*g, **kw)
+        put(f"relax_{tag}/info", before=relax_info(h))
+        x = rng.random(m) * (k / m)
+        put(f"relax_{tag}/eval", F_only=h.relax_eval(x, want_grad=False)[0])
+        put(f"relax_{tag}/info", after=relax_info(h))
+        F, grad = h.relax_eval(x)
+        put(f"relax_{tag}/eval", F=F, grad=grad)
+        if kw:
+            F0, grad0 = h.relax_eval(np.zeros(m))
+            assert F0 == 0.0
+            put(f"relax_{tag}/eval", F_at_0=F0, grad_at_0=grad0)
+
+    put("relax_edge_tree", gram_first_call=_lib.Esp(*tree, matrix_free="tree", edge_relax="tree").relax_gram())
+
+    for tag, g, kw, kx in (("chain", chain60, dict(matrix_free=True, edge_relax=True), K),
+                           ("tree", tree, dict(matrix_free="tree", edge_relax="tree"), Kt)):
+        h = _lib.Esp(*g, **kw)
+        m = len(g[6])
+        put_xch(f"edge_exchange_first_call/{tag}", h.exchange_edge(naive_start(g, kx), 10 * kx))
+        put(f"edge_exchange_first_call/{tag}/relax_run", **h.relax_run(kx, np.full(m, kx / m), max_iters=3, gap_tol=0.0, grad_tol=0.0))
+
+    from test_esp_relax_gpu import many_parallel_candidates
+    g = many_parallel_candidates()
+    m, k = len(g[6]), 4001
+    assert m > 32768
+    put("relax_node_multi_launch_select", **_lib.Esp(*g).relax_run(k, np.random.default_rng(3).random(m) * (k / m), max_iters=1, gap_tol=0.0, grad_tol=0.0))
+
+    def refusal(case, call):
+        try:
+            call()
+        except (AssertionError, _lib.MachipError) as e:
+            put("refusals", **{case: np.frombuffer(str(e).encode(), dtype=np.uint8)})
+        else:
+            raise SystemExit(f"{case}: the call was not refused")
+
+    m = len(chain[6])
+    for tag, kw in (("chain", dict(matrix_free=True)), ("tree", dict(matrix_free="tree"))):
+        g = chain if tag == "chain" else tree
+        refusal(f"relax_eval_on_matrix_free_{tag}", lambda: _lib.Esp(*g, **kw).relax_eval(np.zeros(len(g[6]))))
+        # (k outside [1, m] as well: the run's k check comes first on a handle that is not oversize)
+        refusal(f"relax_run_on_matrix_free_{tag}_bad_k", lambda: _lib.Esp(*g, **kw).relax_run(0, np.zeros(len(g[6]))))
+        refusal(f"relax_run_on_matrix_free_{tag}", lambda: _lib.Esp(*g, **kw).relax_run(3, np.zeros(len(g[6]))))
+    refusal("exchange_edge_on_node_handle", lambda: _lib.Esp(*chain60, fold=4).exchange_edge(start, 10 * K))
+    refusal("exchange_edge_on_matrix_free_handle", lambda: _lib.Esp(*chain60, matrix_free=True).exchange_edge(start, 10 * K))
+    refusal("relax_gram_on_chain_edge_handle", lambda: _lib.Esp(*chain, matrix_free=True, edge_relax=True).relax_gram())
+    refusal("relax_gram_on_node_handle", lambda: _lib.Esp(*chain).relax_gram())
+    h = _lib.Esp(*tree, matrix_free="tree", edge_relax="tree")
+    Mt = len(tree[6]) + h.info()["seeds"]
+    for wrong in (Mt + 1, Mt - 1, 0):
+        refusal(f"relax_gram_wrong_M_{wrong - Mt:+d}", lambda: _lib.check(h._lib.machip_esp_relax_gram(h._h, _lib.p_f64(np.empty((Mt + 1, Mt + 1))), wrong)))
     return out
 
 
