@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define MACHIP_ABI_VERSION 17   /* 17: MACHIP_EIG_MATRIX_FREE_TREE (GreedyEig on any connected fixed graph without a dense Sigma; machip_eig_seeds); 16: MACHIP_EIG_MATRIX_FREE (GreedyEig on a chain without a dense Sigma; options eig_free_rows, eig_free_split); 15: machip_eig_exchange (best-swap local search on lambda_2; option eig_xch_max_mb); 14: machip_esp_exchange_edge (the exchange in the candidates' space on MACHIP_ESP_EDGE_RELAX / MACHIP_ESP_EDGE_RELAX_TREE handles); 13: machip_esp_exchange (best-swap local search on the log tree count; options esp_xch_lds_kb, esp_xch_max_mb, esp_xch_profile); 12: MACHIP_ESP_EDGE_RELAX (the relaxation in the candidates' space on a chain-fixed graph; machip_esp_relax_info); 11: MACHIP_ESP_SPANNING_TREE (the matrix-free route of GreedyESP for any connected fixed graph; machip_esp_tree_plan, machip_esp_seeds); 10: MACHIP_ESP_MATRIX_FREE (GreedyESP on a chain without a dense Sigma, option esp_free_split); 9: the relaxation of GreedyESP's problem (machip_esp_relax_*); 8: GreedyEig handle (machip_eig_*); 7: GreedyESP handle (machip_esp_*); 6: machip_solve_stats.drift, machip_panel_plan fills 12 entries; 5: per-handle option table (machip_set_option), machip_comm_drop_ipc; 4: inter-process communicator */
+#define MACHIP_ABI_VERSION 18   /* 18: machip_eig_exchange_free (the exchange on lambda_2 on MACHIP_EIG_MATRIX_FREE / _TREE handles; option eig_xch_free_swaps), machip_eig_history; 17: MACHIP_EIG_MATRIX_FREE_TREE (GreedyEig on any connected fixed graph without a dense Sigma; machip_eig_seeds); 16: MACHIP_EIG_MATRIX_FREE (GreedyEig on a chain without a dense Sigma; options eig_free_rows, eig_free_split); 15: machip_eig_exchange (best-swap local search on lambda_2; option eig_xch_max_mb); 14: machip_esp_exchange_edge (the exchange in the candidates' space on MACHIP_ESP_EDGE_RELAX / MACHIP_ESP_EDGE_RELAX_TREE handles); 13: machip_esp_exchange (best-swap local search on the log tree count; options esp_xch_lds_kb, esp_xch_max_mb, esp_xch_profile); 12: MACHIP_ESP_EDGE_RELAX (the relaxation in the candidates' space on a chain-fixed graph; machip_esp_relax_info); 11: MACHIP_ESP_SPANNING_TREE (the matrix-free route of GreedyESP for any connected fixed graph; machip_esp_tree_plan, machip_esp_seeds); 10: MACHIP_ESP_MATRIX_FREE (GreedyESP on a chain without a dense Sigma, option esp_free_split); 9: the relaxation of GreedyESP's problem (machip_esp_relax_*); 8: GreedyEig handle (machip_eig_*); 7: GreedyESP handle (machip_esp_*); 6: machip_solve_stats.drift, machip_panel_plan fills 12 entries; 5: per-handle option table (machip_set_option), machip_comm_drop_ipc; 4: inter-process communicator */
 
 typedef enum machip_status {
     MACHIP_OK = 0,
@@ -538,7 +538,7 @@ typedef struct machip_eig machip_eig;
  * (ld, j, the batch, options eig_free_rows / eig_free_split) alone, so runs repeat bit for bit.  MACHIP_BAD_ARG, decided on the host
  * before a device is touched: the flag alone, with MACHIP_ESP_DENSE_INVERSE, with fold != 0 (nothing is folded: an argument without
  * a meaning is refused, not ignored), or a fixed graph that is not the chain.  machip_eig_exchange answers MACHIP_BAD_ARG on such a
- * handle.  The stop rule is relative to ||L_e||_inf: on a long chain (lambda_2 / ||L||_inf ~ pi^2 / 4 n^2 < 1e-8 from n ~ 16 000 on) it
+ * handle (machip_eig_exchange_free is its form here).  The stop rule is relative to ||L_e||_inf: on a long chain (lambda_2 / ||L||_inf ~ pi^2 / 4 n^2 < 1e-8 from n ~ 16 000 on) it
  * certifies little more than the sign of lambda_2 -- on this route as on the dense one. */
 #define MACHIP_EIG_MATRIX_FREE 64
 /* flag of machip_eig_create only (machip_esp_create answers "unknown flags"), valid only as MACHIP_ESP_MATRIX_FREE |
@@ -551,7 +551,7 @@ typedef struct machip_eig machip_eig;
  * arrive with their messages (a fixed graph that is not connected, links whose summed weight is not positive), all before a device is
  * touched.  Nothing of size ld x ld exists.  The difference of suffix sums in the sweeps loses about n eps: it costs the
  * preconditioner nothing that decides (every lambda_2 and pick is the sparse L_cur's).  The order of every sum depends on (ld, the
- * tree, j, the batch, options eig_free_rows / eig_free_split) alone.  machip_eig_exchange answers MACHIP_BAD_ARG.  The stop rule's caveat
+ * tree, j, the batch, options eig_free_rows / eig_free_split) alone.  machip_eig_exchange answers MACHIP_BAD_ARG (machip_eig_exchange_free runs).  The stop rule's caveat
  * above holds for chain-like trees. */
 #define MACHIP_EIG_MATRIX_FREE_TREE 128
 /* fold: as machip_esp_create (0 = 16; must be 0 with MACHIP_EIG_MATRIX_FREE); batch: columns solved together (1..4096; 0 = 512).
@@ -595,12 +595,30 @@ int machip_eig_seeds(machip_eig* h, int64_t* seeds_out);
  * machip_eig_destroy.
  * MACHIP_BAD_ARG, decided on the host (machip_last_error names the reason): NULL handle or sel_in; k < 1 or k >= m; an index
  * outside [0, m); a repeated index; max_swaps < 0; min_gain < 0 or not finite; 8 k (ldv + ldm) bytes beyond the device's free
- * memory (or option eig_xch_max_mb, MiB); a MACHIP_EIG_MATRIX_FREE handle (no Sigma to exchange on).  MACHIP_NOT_CONVERGED: a Fiedler solve missed the stop rule (the handle is reset).
+ * memory (or option eig_xch_max_mb, MiB); a MACHIP_EIG_MATRIX_FREE handle (no Sigma to exchange on: machip_eig_exchange_free).  MACHIP_NOT_CONVERGED: a Fiedler solve missed the stop rule (the handle is reset).
  * Afterwards machip_eig_candidate_lambda2, machip_eig_candidate_bounds and machip_eig_info (its per-pick arrays: per round) refer
  * to the fixed graph plus sel_out; machip_eig_select resets as it always has. */
 int machip_eig_exchange(machip_eig* h, int64_t k, const int32_t* sel_in, int64_t max_swaps, double min_gain, int32_t* sel_out,
                         int32_t* out_idx, int32_t* in_idx, double* lambda2_out, int64_t* n_swaps, int32_t* converged, int32_t* counts,
                         double* t_ms);
+/* machip_eig_exchange on a MACHIP_EIG_MATRIX_FREE or MACHIP_EIG_MATRIX_FREE_TREE handle (mac_amd/csrc/eig_exchange_free.h): the same
+ * rounds, rule, scan, tie tolerance, stop rule and outputs, with the history of the route in the place of Sigma and its pending
+ * block.  The selection is loaded into the history in blocks of 64 columns (the history is read once per block, not once per edge);
+ * a round's trial column is history column `pending` and is dropped after the row; a swap appends two columns (the downdate of e,
+ * then f).  The history is sized for k + 2 C + 1 columns after the handle's seeds, C = min(max_swaps, option eig_xch_free_swaps:
+ * 1..4096, unset 32), refused with machip_eig_select's message before the state is touched when that does not fit.  When a round
+ * would not fit (pending + 3 > seeds + k + 2 C + 1) the history is compacted first: back to the seeds, then the current selection
+ * loaded again, ascending; the Fiedler pair is untouched and nothing is solved again.  *n_compactions (may be NULL) counts them.
+ * No sum's order depends on anything but the inputs and the options: runs repeat bit for bit.  MACHIP_BAD_ARG: machip_eig_exchange's,
+ * by the same messages, except that here a handle with the dense inverse is the one refused (the message names machip_eig_exchange). */
+int machip_eig_exchange_free(machip_eig* h, int64_t k, const int32_t* sel_in, int64_t max_swaps, double min_gain, int32_t* sel_out,
+                             int32_t* out_idx, int32_t* in_idx, double* lambda2_out, int64_t* n_swaps, int32_t* converged, int32_t* counts,
+                             double* t_ms, int64_t* n_compactions);
+/* The history of a MACHIP_EIG_MATRIX_FREE / _TREE handle as it stands, to the host: *cols = its columns (machip_eig_info's pending;
+ * _TREE: the seeds first); Z[ld * *cols] the columns, ld doubles each, column-major as stored (rows n - 1 .. ld are 0), c[*cols] their
+ * coefficients: Sigma_cur = Sigma0 - Z diag(c) Z^T, Sigma0 the inverse of the chain's (the spanning tree's) reduced Laplacian.  Z and
+ * c both NULL: only *cols.  MACHIP_BAD_ARG: NULL handle, a handle with the dense inverse, cap_cols below the columns held. */
+int machip_eig_history(machip_eig* h, int64_t cap_cols, double* Z, double* c, int64_t* cols);
 
 #ifdef __cplusplus
 }

@@ -129,6 +129,9 @@ SIGNATURES = {
     "machip_eig_seeds": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     "machip_eig_exchange": (C.c_int, [C.c_void_p, C.c_int64, _i32p, C.c_int64, C.c_double, _i32p, _i32p, _i32p, _f64p,
                                       C.POINTER(C.c_int64), C.POINTER(C.c_int32), _i32p, _f64p]),
+    "machip_eig_exchange_free": (C.c_int, [C.c_void_p, C.c_int64, _i32p, C.c_int64, C.c_double, _i32p, _i32p, _i32p, _f64p,
+                                           C.POINTER(C.c_int64), C.POINTER(C.c_int32), _i32p, _f64p, C.POINTER(C.c_int64)]),
+    "machip_eig_history": (C.c_int, [C.c_void_p, C.c_int64, _f64p, _f64p, C.POINTER(C.c_int64)]),
 }
 
 
@@ -712,23 +715,49 @@ class Eig:
         check(self._lib.machip_eig_candidate_bounds(self._h, p_f64(out)))
         return out[:self.m]
 
-    def exchange(self, sel, max_swaps, min_gain=0.0):
-        """Best-swap local search on lambda_2 from the selection ``sel`` (candidate indices; machip_eig_exchange):
-        dict(selection int32[K] ascending, out, in (one entry per swap), lambda2 float64[swaps + 1], swaps, converged,
-        solved, applications, removal_solves (one entry per round), t_ms float64[2])."""
+    def _exchange(self, free, sel, max_swaps, min_gain):
+        """What ``exchange`` (machip_eig_exchange) and ``exchange_free`` (machip_eig_exchange_free: one more output) share."""
         sel = i32(sel)
         K, S = len(sel), max(int(max_swaps), 0)
         sel_out = np.empty(max(K, 1), dtype=np.int32)
         out, inn = np.empty(max(S, 1), dtype=np.int32), np.empty(max(S, 1), dtype=np.int32)
         lam, counts = np.empty(S + 1), np.zeros(3 * max(S, 1), dtype=np.int32)
-        n, conv, t = C.c_int64(0), C.c_int32(0), np.zeros(2)
-        check(self._lib.machip_eig_exchange(self._h, K, p_i32(sel), int(max_swaps), float(min_gain), p_i32(sel_out), p_i32(out),
-                                            p_i32(inn), p_f64(lam), C.byref(n), C.byref(conv), p_i32(counts), p_f64(t)))
+        n, conv, t, comp = C.c_int64(0), C.c_int32(0), np.zeros(2), C.c_int64(0)
+        args = (self._h, K, p_i32(sel), int(max_swaps), float(min_gain), p_i32(sel_out), p_i32(out), p_i32(inn), p_f64(lam), C.byref(n),
+                C.byref(conv), p_i32(counts), p_f64(t))
+        check(self._lib.machip_eig_exchange_free(*args, C.byref(comp)) if free else self._lib.machip_eig_exchange(*args))
         q = int(n.value)
         c = counts[:3 * (q + int(conv.value))].reshape(-1, 3)
-        return {"selection": sel_out[:K], "out": out[:q], "in": inn[:q], "lambda2": lam[:q + 1], "swaps": q,
-                "converged": int(conv.value), "solved": c[:, 0].copy(), "applications": c[:, 1].copy(),
-                "removal_solves": c[:, 2].copy(), "t_ms": t}
+        r = {"selection": sel_out[:K], "out": out[:q], "in": inn[:q], "lambda2": lam[:q + 1], "swaps": q,
+             "converged": int(conv.value), "solved": c[:, 0].copy(), "applications": c[:, 1].copy(),
+             "removal_solves": c[:, 2].copy(), "t_ms": t}
+        if free:
+            r["compactions"] = int(comp.value)
+        return r
+
+    def exchange(self, sel, max_swaps, min_gain=0.0):
+        """Best-swap local search on lambda_2 from the selection ``sel`` (candidate indices; machip_eig_exchange):
+        dict(selection int32[K] ascending, out, in (one entry per swap), lambda2 float64[swaps + 1], swaps, converged,
+        solved, applications, removal_solves (one entry per round), t_ms float64[2])."""
+        return self._exchange(False, sel, max_swaps, min_gain)
+
+    def exchange_free(self, sel, max_swaps, min_gain=0.0):
+        """``exchange`` on a matrix_free handle (machip_eig_exchange_free; process option "eig_xch_free_swaps"): the same dict plus
+        ``compactions``."""
+        return self._exchange(True, sel, max_swaps, min_gain)
+
+    def history(self):
+        """The history of a matrix_free handle as it stands (machip_eig_history): (Z float64[ld, pending] -- column q is history
+        column q, rows n - 1 .. ld are 0 --, c float64[pending])."""
+        cols = C.c_int64(0)
+        check(self._lib.machip_eig_history(self._h, 0, None, None, C.byref(cols)))
+        j = int(cols.value)
+        a = np.zeros(6, dtype=np.int32)
+        check(self._lib.machip_eig_info(self._h, p_i32(a), None, 0, None, None))
+        ld = int(a[1])
+        Z, c = np.zeros(max(j, 1) * ld), np.zeros(max(j, 1))
+        check(self._lib.machip_eig_history(self._h, j, p_f64(Z), p_f64(c), C.byref(cols)))
+        return Z[:j * ld].reshape(j, ld).T.copy(), c[:j].copy()
 
     def info(self):
         """dict(form = "chain" | "dense" | "chain_free" | "tree_free", ld, fold, batch, pending (tree_free: seeds + picks), seeds, beta,

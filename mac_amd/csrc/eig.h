@@ -395,6 +395,12 @@ struct machip_eig {
     // What a route is (eig_routes.h, one switch on the form each): room for K picks; z_e, c_e of the columns bc[0..count) into Z / cc;
     // one application and step of the batch (T = Sigma_cur Q, k_eig_rr); `best`, just polished in column 0, joins the block or the history.
     int reserve(int64_t K); int columns(int count); int apply(int count); int push(int best);
+    // The exchange's steps that differ by route (eig_exchange.h; C: the swaps a history is sized for, 0 on the dense routes): room for
+    // the call; the selection `rows` (ascending; idx[r] on the device = rows[r]) loaded; room for a round's trial column and swap (a
+    // fold, or a compaction: counted); the column of candidate *cand (on the device) joins the block or the history -- as a trial it
+    // never folds and is dropped by the caller's pending = j.
+    int xch_reserve(int K, int C); int xch_load(const std::vector<int>& rows, const int* idx);
+    int xch_round_room(const std::vector<int>& rows, int C, int64_t* compactions); int xch_column(const int* cand, bool trial);
 
     machip::EspView zview() const {      // what k_eig_z reads the candidates from
         machip::EspView V = base->view();

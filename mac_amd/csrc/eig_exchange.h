@@ -19,6 +19,8 @@
 //     1e-8 -- GreedyEig's rule.  Nobody: converged.  Else the swap: two columns join the pending block (machip_eig::push_column), the
 //     adjacency, the flags and the negated copy of the row are rewritten, the new pair is polished (machip_eig::adopt_pair).
 // Everything is a function of the inputs alone: sorts are stable, reductions run in a fixed order, no floating-point atomics.
+// On a matrix-free handle (machip_eig_exchange_free) the same rounds run on the route's history: the load, the room
+// for a round, the trial column and the swap's columns are machip_eig::xch_* (eig_routes.h), the history's side is eig_exchange_free.h.
 #pragma once
 #include <chrono>
 #include <string>
@@ -29,6 +31,8 @@
 namespace machip {
 
 constexpr int kEigXchTargetGroups = 1024;     // workgroups of a pair pass the candidate range is cut for when K alone gives fewer
+constexpr int kEigXchFreeSwaps = 32;          // matrix-free handles: swaps the history has room for between two compactions (option
+constexpr int kEigXchFreeSwapsMax = 4096;     // eig_xch_free_swaps, 1 .. 4096)
 
 struct EigXch {
     int *cu = nullptr, *cv = nullptr;      // m + K reduced endpoints
@@ -97,10 +101,14 @@ inline void eig_xch_release(EigXch*& x) {
 }
 
 // The arguments, decided on the host before a device is touched.  sorted_out: the selection ascending.
-inline int eig_xch_check(const machip_eig* h, int64_t k, const int32_t* sel_in, int64_t max_swaps, double min_gain, std::vector<int>& sorted_out) {
+// free_entry: machip_eig_exchange_free's call, where the clause on the route is the other way round.
+inline int eig_xch_check(const machip_eig* h, int64_t k, const int32_t* sel_in, int64_t max_swaps, double min_gain, std::vector<int>& sorted_out,
+                         bool free_entry = false) {
     if (!h) return fail(MACHIP_BAD_ARG, "NULL handle");
-    if (h->matrix_free())
-        return fail(MACHIP_BAD_ARG, "the exchange works on the dense inverse: it is not available on a MACHIP_EIG_MATRIX_FREE handle");
+    if (h->matrix_free() && !free_entry)
+        return fail(MACHIP_BAD_ARG, "the exchange works on the dense inverse: it is not available on a MACHIP_EIG_MATRIX_FREE handle (machip_eig_exchange_free is)");
+    if (!h->matrix_free() && free_entry)
+        return fail(MACHIP_BAD_ARG, "machip_eig_exchange_free works on the history of a MACHIP_EIG_MATRIX_FREE handle: a handle with the dense inverse takes machip_eig_exchange");
     if (!sel_in) return fail(MACHIP_BAD_ARG, "sel_in is NULL");
     if (max_swaps < 0) return fail(MACHIP_BAD_ARG, "max_swaps must be >= 0 (got " + std::to_string((long long)max_swaps) + ")");
     if (!(min_gain >= 0.0) || !std::isfinite(min_gain)) return fail(MACHIP_BAD_ARG, "min_gain must be finite and >= 0");
@@ -184,13 +192,17 @@ struct EigXchPair {
 
 // The rounds.  rowe: the selection ascending.  Every output may be NULL.
 inline int eig_exchange_run(machip_eig* h, std::vector<int> rowe, int64_t max_swaps, double min_gain, int32_t* sel_out, int32_t* out_idx,
-                            int32_t* in_idx, double* lambda2_out, int64_t* n_swaps, int32_t* converged, int32_t* counts, double* t_ms) {
+                            int32_t* in_idx, double* lambda2_out, int64_t* n_swaps, int32_t* converged, int32_t* counts, double* t_ms,
+                            int64_t* n_compactions) {
     machip_esp* base = h->base;
     hipStream_t st = base->stream;
-    const int K = (int)rowe.size(), m = h->m, ld = base->ld, ldv = h->ldv, batch = h->batch;
+    const int K = (int)rowe.size(), m = h->m, ldv = h->ldv, batch = h->batch;
     const int ldm = (m + 3) / 4 * 4;
     const int chunks = std::max(1, std::min((m + kBlock - 1) / kBlock, (kEigXchTargetGroups + K - 1) / K));
     const int per = ((m + chunks - 1) / chunks + 3) / 4 * 4;
+    // the swaps a matrix-free history has room for between two compactions (option eig_xch_free_swaps, read per call)
+    const int C = h->matrix_free() ? (int)std::min<int64_t>(max_swaps, std::max(1, std::min(default_options().get(kOpt_eig_xch_free_swaps, kEigXchFreeSwaps), kEigXchFreeSwapsMax))) : 0;
+    ST_TRY(h->xch_reserve(K, C));      // (refused before the state is touched)
     ST_TRY(eig_xch_prepare(h->xc, (size_t)m, (size_t)K, (size_t)ldv, (size_t)ldm, (size_t)K * (size_t)chunks));
     EigXch* X = h->xc;
     while (base->ev.size() < 2) {
@@ -222,9 +234,9 @@ inline int eig_exchange_run(machip_eig* h, std::vector<int> rowe, int64_t max_sw
     };
     ST_TRY(upload_view());
     h->xcu = X->cu; h->xcv = X->cv; h->xcw = X->cw;
+    ST_TRY(h->xch_load(rowe, X->idx));
     for (int r = 0; r < K; ++r) {
         const int e = rowe[(size_t)r];
-        h->push_column(X->idx + r);
         h->sel[(size_t)e] = 1;
         h->add_edge(h->hci[(size_t)e], h->hcj[(size_t)e], h->hcw[(size_t)e]);
     }
@@ -234,13 +246,13 @@ inline int eig_exchange_run(machip_eig* h, std::vector<int> rowe, int64_t max_sw
     if (lambda2_out) lambda2_out[0] = h->lamcur;
 
     // ---- rounds ----
-    int64_t t = 0;
+    int64_t t = 0, compactions = 0;
     int conv = 0;
     std::vector<double> lamr((size_t)K), part((size_t)K * (size_t)chunks), rowmax((size_t)K), u((size_t)m);
     std::vector<int> list, rord((size_t)K);
     std::vector<EigXchPair> pairs;
     while (t < max_swaps) {
-        if (base->pending > 0 && base->pending + 2 > base->fold) { base->fold_into(base->sig, base->pending); base->pending = 0; }
+        ST_TRY(h->xch_round_room(rowe, C, &compactions));
         const double tau = h->lamcur + min_gain;
         int napp = 0;
         // removal pairs: column b of a batch is the negated copy of row q + b
@@ -274,9 +286,8 @@ inline int eig_exchange_run(machip_eig* h, std::vector<int> rowe, int64_t max_sw
             if (!(rowmax[(size_t)r] > std::max(tau, scan.top))) break;
             const int e = rowe[(size_t)r], a = h->hci[(size_t)e], b = h->hcj[(size_t)e];
             const int j = base->pending;
-            eig_dense_columns(base, h->zview(), X->idx + K + r, 1, base->Zb + (size_t)j * (size_t)ld, base->cb + j);
+            ST_TRY(h->xch_column(X->idx + K + r, true));
             HIP_TRY(hipGetLastError());
-            base->pending = j + 1;
             {      // the CSR of L_{S \ e}; the host's adjacency stays L_S
                 const auto ra = h->adj[(size_t)a], rb = h->adj[(size_t)b];
                 const double da = h->hdeg[(size_t)a], db = h->hdeg[(size_t)b];
@@ -308,11 +319,11 @@ inline int eig_exchange_run(machip_eig* h, std::vector<int> rowe, int64_t max_sw
         }
         // the swap
         const EigXchPair w = pairs[(size_t)best];
-        h->push_column(X->idx + K + w.row);          // e leaves (the negated copy, still e's)
+        ST_TRY(h->xch_column(X->idx + K + w.row, false));      // e leaves (the negated copy, still e's)
         set_row(w.row, w.f);
         hsel[(size_t)w.e] = 0; hsel[(size_t)w.f] = 1;
         ST_TRY(upload_view());
-        h->push_column(X->idx + w.row);              // f enters
+        ST_TRY(h->xch_column(X->idx + w.row, false));          // f enters
         HIP_TRY(hipGetLastError());
         h->sel[(size_t)w.e] = 0; h->sel[(size_t)w.f] = 1;
         ST_TRY(eig_xch_remove_edge(h, h->hci[(size_t)w.e], h->hcj[(size_t)w.e], h->hcw[(size_t)w.e]));
@@ -335,6 +346,7 @@ inline int eig_exchange_run(machip_eig* h, std::vector<int> rowe, int64_t max_sw
     }
     if (n_swaps) *n_swaps = t;
     if (converged) *converged = conv;
+    if (n_compactions) *n_compactions = compactions;
     if (counts)
         for (size_t r = 0; r < h->solved.size(); ++r) {
             counts[3 * r] = h->solved[r]; counts[3 * r + 1] = h->applies[r]; counts[3 * r + 2] = h->removal[r];
@@ -350,8 +362,9 @@ inline int eig_exchange_run(machip_eig* h, std::vector<int> rowe, int64_t max_sw
 
 // The call after its checks: the handle leaves it with the greedy's candidate arrays and, after a failure, at the fixed graph (message kept)
 inline int eig_exchange(machip_eig* h, const std::vector<int>& rowe, int64_t max_swaps, double min_gain, int32_t* sel_out, int32_t* out_idx,
-                        int32_t* in_idx, double* lambda2_out, int64_t* n_swaps, int32_t* converged, int32_t* counts, double* t_ms) {
-    const int st = eig_exchange_run(h, rowe, max_swaps, min_gain, sel_out, out_idx, in_idx, lambda2_out, n_swaps, converged, counts, t_ms);
+                        int32_t* in_idx, double* lambda2_out, int64_t* n_swaps, int32_t* converged, int32_t* counts, double* t_ms,
+                        int64_t* n_compactions = nullptr) {
+    const int st = eig_exchange_run(h, rowe, max_swaps, min_gain, sel_out, out_idx, in_idx, lambda2_out, n_swaps, converged, counts, t_ms, n_compactions);
     h->xcu = h->xcv = nullptr; h->xcw = nullptr;
     if (st != MACHIP_OK) {
         const std::string msg = machip_last_error();

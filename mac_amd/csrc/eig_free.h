@@ -267,6 +267,7 @@ struct EigFree {
     double *Y = nullptr, *part = nullptr;      // the projection (K64 x ldq) and the slices' partial tiles
     int k64 = 0;                               // history columns Y / part are sized for
     EigFreeTree* tree = nullptr;               // form 3: the spanning tree in the place of the chain (cs / cu: its row and tour chunks' sums)
+    double *xg = nullptr, *xn = nullptr;       // eig_exchange_free.h: G and N of a block of the blocked load (64 x 64 each), made by its first call
 };
 
 // What both routes start from: the scan chunks and option eig_free_split, then the batch arrays' bytes (machip_eig::alloc plus the
@@ -296,7 +297,7 @@ inline int eig_free_init(machip_eig* h, bool tree = false) {
 inline void eig_free_release(EigFree* F) {
     if (!F) return;
     eig_tree_release(F->tree);
-    void* bufs[] = {F->cs, F->cu, F->Y, F->part};
+    void* bufs[] = {F->cs, F->cu, F->Y, F->part, F->xg, F->xn};
     for (void* q : bufs) if (q) (void)hipFree(q);
     delete F;
 }

@@ -1,7 +1,8 @@
 // mac_amd/csrc/eig_routes.h -- GreedyEig's three routes together (eig.h: the dense inverse; eig_free.h, eig_free_tree.h: no Sigma): what
-// machip_eig::reserve / columns / apply / push do, one switch on the machip_esp's form each, and how a handle is made.  DESIGN 12, 21, 22.
+// machip_eig::reserve / columns / apply / push and the exchange's xch_reserve / xch_load / xch_round_room / xch_column do, one switch on
+// the machip_esp's form each, and how a handle is made.  DESIGN 12, 21, 22, 23.
 #pragma once
-#include "eig_free_tree.h"
+#include "eig_exchange_free.h"
 
 inline int machip_eig::reserve(int64_t K) { return matrix_free() ? machip::eig_free_reserve(this, K) : MACHIP_OK; }
 
@@ -29,6 +30,41 @@ inline int machip_eig::push(int best) {
     HIP_TRY(hipMemcpyAsync(bc, &best, sizeof(int), hipMemcpyHostToDevice, base->stream));
     HIP_TRY(hipStreamSynchronize(base->stream));
     push_column(bc);
+    return MACHIP_OK;
+}
+
+inline int machip_eig::xch_reserve(int K, int C) { return matrix_free() ? reserve((int64_t)K + 2 * (int64_t)C + 1) : MACHIP_OK; }
+
+inline int machip_eig::xch_load(const std::vector<int>& rows, const int* idx) {
+    if (matrix_free()) return machip::eig_xfree_load(this, rows);
+    for (size_t r = 0; r < rows.size(); ++r) push_column(idx + r);
+    return MACHIP_OK;
+}
+
+inline int machip_eig::xch_round_room(const std::vector<int>& rows, int C, int64_t* compactions) {
+    if (matrix_free()) {
+        if (base->pending + 3 > seeds + (int)rows.size() + 2 * C + 1) {
+            ST_TRY(machip::eig_xfree_compact(this, rows));
+            ++*compactions;
+        }
+    } else if (base->pending > 0 && base->pending + 2 > base->fold) {
+        base->fold_into(base->sig, base->pending);
+        base->pending = 0;
+    }
+    return MACHIP_OK;
+}
+
+inline int machip_eig::xch_column(const int* cand, bool trial) {
+    if (matrix_free()) {      // (trial or not, the same push: nothing folds here, and the caller's pending = j drops a trial)
+        HIP_TRY(hipMemcpyAsync(bc, cand, sizeof(int), hipMemcpyDeviceToDevice, base->stream));
+        ST_TRY(columns(1));
+        return machip::eig_free_push(this);
+    }
+    if (trial) {
+        const int j = base->pending;
+        machip::eig_dense_columns(base, zview(), cand, 1, base->Zb + (size_t)j * (size_t)base->ld, base->cb + j);
+        base->pending = j + 1;
+    } else push_column(cand);
     return MACHIP_OK;
 }
 

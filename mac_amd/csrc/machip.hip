@@ -1734,6 +1734,25 @@ int machip_eig_exchange(machip_eig* h, int64_t k, const int32_t* sel_in, int64_t
     return eig_exchange(h, rowe, max_swaps, min_gain, sel_out, out_idx, in_idx, lambda2_out, n_swaps, converged, counts, t_ms);
 }
 
+int machip_eig_exchange_free(machip_eig* h, int64_t k, const int32_t* sel_in, int64_t max_swaps, double min_gain, int32_t* sel_out,
+                             int32_t* out_idx, int32_t* in_idx, double* lambda2_out, int64_t* n_swaps, int32_t* converged, int32_t* counts, double* t_ms,
+                             int64_t* n_compactions) {
+    std::vector<int> rowe;
+    ST_TRY(eig_xch_check(h, k, sel_in, max_swaps, min_gain, rowe, true));
+    if (n_swaps) *n_swaps = 0;
+    if (converged) *converged = 0;
+    if (n_compactions) *n_compactions = 0;
+    HIP_TRY(hipSetDevice(h->base->device));
+    return eig_exchange(h, rowe, max_swaps, min_gain, sel_out, out_idx, in_idx, lambda2_out, n_swaps, converged, counts, t_ms, n_compactions);
+}
+
+int machip_eig_history(machip_eig* h, int64_t cap_cols, double* Z, double* c, int64_t* cols) {
+    if (!h) return fail(MACHIP_BAD_ARG, "NULL handle");
+    if (!h->matrix_free()) return fail(MACHIP_BAD_ARG, "machip_eig_history: only a MACHIP_EIG_MATRIX_FREE handle keeps a history");
+    HIP_TRY(hipSetDevice(h->base->device));
+    return eig_free_history_read(h, cap_cols, Z, c, cols);
+}
+
 int machip_eig_candidate_lambda2(machip_eig* h, double* out) {
     if (!h || (!out && h->m)) return fail(MACHIP_BAD_ARG, "NULL handle or output");
     HIP_TRY(hipSetDevice(h->base->device));

@@ -41,6 +41,9 @@ namespace machip {
     /* the exchange on lambda_2 (eig_exchange.h; process default, read by every machip_eig_exchange call): a cap in MiB, below     \
        the device's free memory, on the removal vectors and the bound matrix */                                                   \
     X(eig_xch_max_mb)                                                                                                              \
+    /* the same on a matrix-free handle (machip_eig_exchange_free; read by every call): swaps the history has room for between     \
+       two compactions, 1..4096 (unset: 32) */                                                                                    \
+    X(eig_xch_free_swaps)                                                                                                          \
     /* GreedyEig, matrix-free route (eig_free.h; read when the handle is made): rows per chunk of the two scans (0 / unset:         \
        automatic, at most 128 chunks of at least 32 rows; a value that would make more than 1 024 chunks is raised to           \
        ceil(ld / 1024)); row slices of the history projection, 1..32 (unset: about one            \

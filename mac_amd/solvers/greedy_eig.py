@@ -16,7 +16,8 @@ Size limits as GreedyESP: 32 768 poses when the fixed edges are exactly the chai
 ``matrix_free=True`` (chain-fixed graphs only) keeps no inverse at all: the chain's inverse applied to a batch is two scans, the
 picks are a low-rank correction kept as a history of n x k doubles, and one solver iteration costs 4 n j B flop plus three passes
 over the batch instead of 2 n^2 B (mac_amd/csrc/eig_free.h).  No limit on the number of poses but memory; the
-picks obey the same rule and stop rule, decided by the sparse Laplacian.  ``exchange`` is not available on that route.
+picks obey the same rule and stop rule, decided by the sparse Laplacian.  The polish on that route (and on "tree") is
+``exchange_free``; ``exchange`` itself stays the dense routes' and refuses a matrix-free handle.
 
 ``matrix_free="tree"`` is that route for ANY connected fixed graph -- a chain plus kept closures, odometry whose indices are not
 consecutive, a landmark spur, merged sessions: a spanning tree T of the fixed graph takes the chain's place (its inverse applied to
@@ -76,6 +77,7 @@ class GreedyEig:
         fi, fj, fw = edges_to_arrays(odom_measurements)
         self._dev = _lib.Eig(num_poses, fi, fj, fw, ci, cj, cw, fold=fold, batch=batch, dense_inverse=dense_inverse, device=device,
                              matrix_free=matrix_free if isinstance(matrix_free, str) else bool(matrix_free))
+        self._matrix_free = matrix_free if isinstance(matrix_free, str) else bool(matrix_free)
         self.last_lambda2: Optional[np.ndarray] = None      # lambda_2 after every pick of the last run
         self.last_times: Optional[np.ndarray] = None        # seconds from the start of the last run until each pick
 
@@ -134,6 +136,28 @@ class GreedyEig:
         result[r["selection"]] = 1.0
         info = {"swaps": [(int(a), int(b)) for a, b in zip(r["out"], r["in"])], "lambda2": r["lambda2"], "converged": bool(r["converged"]),
                 "solved": r["solved"], "applies": r["applications"], "removal_solves": r["removal_solves"], "t_ms": r["t_ms"]}
+        return result, [Edge(int(self.edge_list[e, 0]), int(self.edge_list[e, 1]), float(self.weights[e])) for e in r["selection"]], info
+
+    def exchange_free(self, selection, max_swaps: Optional[int] = None, min_gain: float = 0.0):
+        """``exchange`` on a handle made with ``matrix_free=True`` or ``"tree"``: the same rule, scan, tie tolerance, stop rule and
+        return triple, on the route's history instead of an inverse -- so it runs past the dense limits.  The selection is loaded
+        into the history in blocks of 64 columns; a swap appends two columns; the history has room for ``min(max_swaps, 32)`` swaps
+        (process option "eig_xch_free_swaps") and is compacted -- rebuilt from the current selection, nothing solved again -- when
+        the next round would not fit.  ``info`` has one more key, ``compactions``.  A handle with the dense inverse is a
+        ValueError: ``exchange`` is the entry there."""
+        m = len(self.weights)
+        sel = selection_indices(selection, m)
+        if not getattr(self, "_matrix_free", False):
+            raise ValueError("exchange_free works on the history of a matrix_free=True or \"tree\" GreedyEig: "
+                             "on this one, which keeps the dense inverse, use exchange")
+        if max_swaps is None:
+            max_swaps = 10 * len(sel)
+        r = self._dev.exchange_free(sel, max_swaps, min_gain)
+        result = np.zeros(m)
+        result[r["selection"]] = 1.0
+        info = {"swaps": [(int(a), int(b)) for a, b in zip(r["out"], r["in"])], "lambda2": r["lambda2"], "converged": bool(r["converged"]),
+                "solved": r["solved"], "applies": r["applications"], "removal_solves": r["removal_solves"], "t_ms": r["t_ms"],
+                "compactions": r["compactions"]}
         return result, [Edge(int(self.edge_list[e, 0]), int(self.edge_list[e, 1]), float(self.weights[e])) for e in r["selection"]], info
 
     def candidate_lambda2(self) -> np.ndarray:

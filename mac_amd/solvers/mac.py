@@ -46,6 +46,7 @@ class MAC:
         self.num_nodes = num_nodes
         self._edges = (fixed_edges, candidate_edges, device)        # what ``exchange`` builds its GreedyEig from
         self._greedy_eig = None
+        self._greedy_eig_free = None                                 # ``exchange_free``'s, matrix_free="tree", beside the dense one
         fi, fj, fw = edges_to_arrays(fixed_edges)
         ci, cj, cw = edges_to_arrays(candidate_edges)
         self.weights = cw                                            # mac.py:58-65
@@ -165,6 +166,17 @@ class MAC:
             self._greedy_eig = GreedyEig(fixed, cand, self.num_nodes, device=device)
         return self._greedy_eig.exchange(sel, max_swaps, min_gain)
 
+    def exchange_free(self, selection, max_swaps=None, min_gain=0.0):
+        """``GreedyEig.exchange_free`` (the same search without an inverse) on these edges and this device: a
+        ``GreedyEig(..., matrix_free="tree")`` is built on first use and kept beside ``exchange``'s dense one.  Returns its
+        ``(result, selected_edges, info)``."""
+        from mac_amd.solvers.greedy_eig import GreedyEig, selection_indices
+        sel = selection_indices(selection, len(self.weights))
+        if self._greedy_eig_free is None:
+            fixed, cand, device = self._edges
+            self._greedy_eig_free = GreedyEig(fixed, cand, self.num_nodes, device=device, matrix_free="tree")
+        return self._greedy_eig_free.exchange_free(sel, max_swaps, min_gain)
+
     def solve(self, k, x_init=None, rounding="nearest", fallback=False, max_iters=5,
               relative_duality_gap_tol=1e-4, grad_norm_tol=1e-8, random_rounding_max_iters=1,
               verbose=False, return_rounding_time=False, use_cache=False, *, exchange=False):
@@ -172,7 +184,8 @@ class MAC:
         ``(rounded, unrounded, upper_bound[, rounding_time])``.  ``exchange=True`` (not in the reference): the rounded selection
         is polished by ``exchange`` -- lambda_2 of what is returned is not below the rounded one's; the unrounded solution and
         the upper bound are the relaxation's, unchanged.  An integer instead of True caps the swaps (``max_swaps``); what the
-        polish did is kept in ``exchange_info``."""
+        polish did is kept in ``exchange_info``.  ``exchange="free"``: the polish by ``exchange_free``, to convergence (the one
+        string with a meaning of its own: any other still goes through ``int()``, as it always has)."""
         m = len(self.weights)
         if k >= m:                                                   # mac.py:173-180
             result = np.ones(m)
@@ -214,7 +227,9 @@ class MAC:
             if self.evaluate_objective(rounded) < self.evaluate_objective(x_init):
                 rounded = np.asarray(x_init, dtype=np.float64)
 
-        if exchange:
+        if isinstance(exchange, str) and exchange == "free":
+            rounded, _, self.exchange_info = self.exchange_free(rounded)
+        elif exchange:
             rounded, _, self.exchange_info = self.exchange(rounded, max_swaps=None if exchange is True else int(exchange))
 
         if return_rounding_time:
