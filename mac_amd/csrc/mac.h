@@ -1,0 +1,572 @@
+// mac_amd/csrc/mac.h -- the MAC handle (machip_problem) and what one handle does on its own: the union pattern and the assembly of
+// L(x), the buffers of a handle and of a lane (alloc_assembly, alloc_fw, alloc_common), the top-K select on the handle's histogram,
+// the shard arithmetic, the Fiedler solve (run_fiedler), the bodies of machip_create / machip_destroy, the CSR-only handle with its
+// cache, and the ABI's two device probes (profile_spmv, membench).  The gradient and the communicators: mac_comm.h; Frank-Wolfe:
+// mac_fw.h; the lanes: mac_lanes.h.  DESIGN sections 2-4 and 7 (LocalGroup).
+#pragma once
+#include <rccl/rccl.h>
+
+#include <algorithm>
+#include <cmath>
+#include <condition_variable>
+#include <memory>
+
+#include "solver.h"
+
+struct machip_problem;
+
+namespace machip {
+
+// a solve that left a vector to go on with: converged, stopped at its step cap, or on a disconnected selection (the soft statuses)
+inline bool completed(int st) { return st == MACHIP_OK || st == MACHIP_NOT_CONVERGED || st == MACHIP_DISCONNECTED; }
+
+// In-process communicator (machip_comm_init_local): the ranks are handles of ONE process driven by one host
+// thread each (one GPU per handle, or several handles on one GPU); the all-gather is peer-to-peer device copies
+// between the handles' gradient buffers, bracketed by a host barrier.  Same shard arithmetic and the same call
+// site as the RCCL communicator.
+struct LocalGroup {
+    int nranks = 0;
+    std::vector<double*> g;     // every rank's gradient buffer (device)
+    // row-partitioned eigen-solve (solver.h ShardGroup): rank 0 leads, its results are handed to the peers
+    std::vector<machip_problem*> members;
+    ShardGroup sg;
+    bool shard_eig = false;
+    int lead_status = MACHIP_OK;
+    double lead_lam = 0.0;
+    machip_solve_stats lead_stats{};
+    std::string lead_err;
+    ~LocalGroup() {
+        for (ShardRank& r : sg.rk) for (hipEvent_t e : r.ev) if (e) (void)hipEventDestroy(e);
+        if (sg.fork) (void)hipEventDestroy(sg.fork);
+    }
+    std::mutex mu;
+    std::condition_variable cv;
+    int waiting = 0;
+    unsigned long generation = 0;
+    bool broken = false;
+    // returns false when the group was broken (a rank failed or was destroyed): never blocks forever
+    bool barrier() {
+        std::unique_lock<std::mutex> lk(mu);
+        if (broken) return false;
+        const unsigned long gen = generation;
+        if (++waiting == nranks) { waiting = 0; ++generation; cv.notify_all(); return true; }
+        cv.wait(lk, [&] { return generation != gen || broken; });
+        return !broken;
+    }
+    void abort() {
+        std::lock_guard<std::mutex> lk(mu);
+        broken = true;
+        cv.notify_all();
+    }
+};
+
+}  // namespace machip
+
+struct machip_problem {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    int n = 0;
+    long m = 0, m_pad = 0;
+    double tol_sel = 1e-10;
+    // pattern (device)
+    int *prow = nullptr, *pcol = nullptr, *pk = nullptr;
+    double* pw = nullptr;
+    long P = 0;
+    int asm_G = 16, asm_rpb = 1, asm_grid = 1;
+    // candidates (device)
+    int *ci = nullptr, *cj = nullptr;
+    double* cw = nullptr;
+    double *x = nullptr, *x_next = nullptr, *g = nullptr, *s = nullptr, *scratch_m = nullptr;
+    // assembled CSR (device)
+    int *cnt = nullptr, *blk_sum = nullptr, *rowptr = nullptr, *col = nullptr;
+    double *val = nullptr, *blk_lnorm = nullptr;
+    unsigned long long *xb = nullptr, *xb_next = nullptr;     // support bitmaps of x / x_next (kernels.h k_x_bits)
+    bool xb_valid = false, xb_next_valid = false;
+    long nnz = 0, support = 0;
+    int maxlen = 0;           // longest row of the assembled L(x)
+    double lnorm = 0.0;
+    bool assembled = false, have_vec = false, csr_only = false;
+    bool band_dups_ok = true;    // no row holds more than 7 slots of columns r - 1 / r + 1 (the panel form packs that count in 3 bits)
+    // select / FW scalars
+    unsigned int* hist = nullptr;
+    machip::SelState* sel = nullptr;
+    double* part_fw = nullptr;
+    // pinned host
+    int* h_int = nullptr;        // mapped pinned memory; d_hint / d_hdbl = the device's view of it
+    double* h_dbl = nullptr;
+    int* d_hint = nullptr;
+    double* d_hdbl = nullptr;
+    machip::Solver sol;
+    // multi-GPU
+    ncclComm_t comm = nullptr;
+    std::shared_ptr<machip::LocalGroup> lgroup;
+    bool first_collective_pending = false;   // the communicator's first ncclAllGather is awaited with a time limit
+    hipEvent_t ev_g0 = nullptr, ev_g1 = nullptr, ev_g2 = nullptr;   // around the last gradient kernel / exchange of a communicator (machip_comm_timing)
+    bool ev_g_valid = false;
+    std::unique_ptr<machip::IpcGroup> ipcg;      // inter-process communicator with a row-partitioned eigen-solve (machip_comm_init_ipc)
+    int rank = 0, nranks = 1;
+    // evaluation lanes (machip_eval_batch): lightweight copies that share the pattern and the candidate arrays
+    bool is_lane = false, lane_fw_ready = false;
+    std::vector<machip_problem*> lanes;
+    unsigned long start_version = 0;          // bumped whenever sol.start changes
+    unsigned long seen_start_version = ~0ul;  // (lane) the owner's start_version this lane last copied
+
+    machip::CsrView csr() const { return machip::CsrView{n, rowptr, col, val}; }
+    machip::PatternView pattern() const { return machip::PatternView{n, prow, pcol, pk, pw}; }
+};
+
+namespace machip {
+
+inline std::mutex g_csr_mu;                        // machip_fiedler_csr's cached handle
+inline machip_problem* g_csr_cache = nullptr;
+
+struct Slot { int col, k; double w; };      // one entry of the union pattern: column, candidate index (-1: fixed), weight
+
+inline int build_pattern(machip_problem* p, int64_t nf, const int32_t* fi, const int32_t* fj, const double* fw,
+                         int64_t m, const int32_t* ci, const int32_t* cj, const double* cw) {
+    const Options& opt = p->sol.opt;
+    const int n = p->n;
+    std::vector<long> deg((size_t)n + 1, 0);
+    auto chk = [&](int a, int b) { return a >= 0 && a < n && b >= 0 && b < n; };
+    for (int64_t e = 0; e < nf; ++e) {
+        if (!chk(fi[e], fj[e])) return fail(MACHIP_BAD_ARG, "fixed edge endpoint out of range");
+        if (fi[e] != fj[e]) { deg[(size_t)fi[e]]++; deg[(size_t)fj[e]]++; }
+    }
+    for (int64_t e = 0; e < m; ++e) {
+        if (!chk(ci[e], cj[e])) return fail(MACHIP_BAD_ARG, "candidate edge endpoint out of range");
+        if (ci[e] != cj[e]) { deg[(size_t)ci[e]]++; deg[(size_t)cj[e]]++; }
+    }
+    std::vector<long> off((size_t)n + 1, 0);
+    for (int r = 0; r < n; ++r) off[(size_t)r + 1] = off[(size_t)r] + deg[(size_t)r];
+    std::vector<Slot> slots((size_t)off[(size_t)n]);
+    std::vector<long> cur(off.begin(), off.end() - 1);
+    for (int64_t e = 0; e < nf; ++e) {
+        const int a = fi[e], b = fj[e];
+        if (a == b) continue;   // a self-loop contributes +w -w = 0 (graphs.py:27-46)
+        slots[(size_t)cur[(size_t)a]++] = Slot{b, -1, fw[e]};
+        slots[(size_t)cur[(size_t)b]++] = Slot{a, -1, fw[e]};
+    }
+    for (int64_t e = 0; e < m; ++e) {
+        const int a = ci[e], b = cj[e];
+        if (a == b) continue;
+        slots[(size_t)cur[(size_t)a]++] = Slot{b, (int)e, cw[e]};
+        slots[(size_t)cur[(size_t)b]++] = Slot{a, (int)e, cw[e]};
+    }
+    // sort each row by (col, fixed first, k); merge duplicate fixed slots (coo->csr sums them)
+    std::vector<int> prow((size_t)n + 1, 0);
+    std::vector<int> pcol, pk;
+    std::vector<double> pw;
+    pcol.reserve(slots.size()); pk.reserve(slots.size()); pw.reserve(slots.size());
+    for (int r = 0; r < n; ++r) {
+        Slot* b = slots.data() + off[(size_t)r];
+        Slot* e = slots.data() + off[(size_t)r + 1];
+        std::sort(b, e, [](const Slot& x, const Slot& y) {
+            if (x.col != y.col) return x.col < y.col;
+            return x.k < y.k;
+        });
+        for (Slot* q = b; q < e; ++q) {
+            if (q->k < 0 && !pcol.empty() && (long)pcol.size() > prow[(size_t)r] && pcol.back() == q->col &&
+                pk.back() < 0) {
+                pw.back() += q->w;
+            } else {
+                pcol.push_back(q->col); pk.push_back(q->k); pw.push_back(q->w);
+            }
+        }
+        if (pcol.size() > 2000000000ull) return fail(MACHIP_BAD_ARG, "pattern exceeds int32 indexing");
+        {
+            int band_slots = 0;
+            for (size_t q = (size_t)prow[(size_t)r]; q < pcol.size(); ++q) band_slots += (pcol[q] == r - 1 || pcol[q] == r + 1);
+            if (band_slots > 7) p->band_dups_ok = false;
+        }
+        prow[(size_t)r + 1] = (int)pcol.size();
+    }
+    p->P = (long)pcol.size();
+    ST_TRY(dev_alloc(&p->prow, (size_t)n + 1));
+    ST_TRY(dev_alloc(&p->pcol, (size_t)p->P)); ST_TRY(dev_alloc(&p->pk, (size_t)p->P)); ST_TRY(dev_alloc(&p->pw, (size_t)p->P));
+    // (every copy of this library names the handle's own stream: the legacy stream would serialise with -- and, while a lane
+    // captures a chunk graph, fail against -- every blocking stream of the process; the lanes' CU-masked streams are blocking)
+    HIP_TRY(hipMemcpyAsync(p->prow, prow.data(), sizeof(int) * ((size_t)n + 1), hipMemcpyHostToDevice, p->stream));
+    if (p->P) {
+        HIP_TRY(hipMemcpyAsync(p->pcol, pcol.data(), sizeof(int) * (size_t)p->P, hipMemcpyHostToDevice, p->stream));
+        HIP_TRY(hipMemcpyAsync(p->pk, pk.data(), sizeof(int) * (size_t)p->P, hipMemcpyHostToDevice, p->stream));
+        HIP_TRY(hipMemcpyAsync(p->pw, pw.data(), sizeof(double) * (size_t)p->P, hipMemcpyHostToDevice, p->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(p->stream));      // (the host vectors go out of scope)
+    // assembly launch shape: G lanes per row ~ half the mean pattern degree
+    const double mean = n ? (double)p->P / n : 1.0;
+    int G = 4;
+    while (G < 64 && G < mean * 0.75) G <<= 1;
+    p->asm_G = OPT(asm_g, G);
+    const int gpb = kBlock / p->asm_G;
+    // (round 5: up to 4 096 workgroups -- with 1 024 a G-lane group walked 13 rows one after the other at configs[3], each a chain of
+    // dependent loads: prow -> pk -> x[pk]; the pass was latency-bound at a quarter of the chip's memory-level parallelism)
+    long nblk = std::min<long>(std::min(kAsmGrid, std::max(1, OPT(asm_maxgrid, kAsmGrid))), ((long)n + gpb - 1) / gpb);
+    if (nblk < 1) nblk = 1;
+    long rpb = ((long)n + nblk - 1) / nblk;
+    rpb = (rpb + gpb - 1) / gpb * gpb;
+    p->asm_rpb = (int)rpb;
+    p->asm_grid = (int)(((long)n + rpb - 1) / rpb);
+    if (p->asm_grid < 1) p->asm_grid = 1;
+    // k_asm_fill scans its rows' counts in (rpb + 1) ints of dynamic LDS: stay inside the 64 KB every launch may use
+    if ((rpb + 1) * (long)sizeof(int) > 64 * 1024)
+        return fail(MACHIP_BAD_ARG, "num_nodes above the supported 16.7 million (row-offset scan of the assembly kernel)");
+    return MACHIP_OK;
+}
+
+template <int G>
+void launch_asm(machip_problem* p, const PanSpec& S) {
+    const PatternView P = p->pattern();
+    const unsigned int* xb32 = reinterpret_cast<const unsigned int*>(p->xb);
+    k_asm_count<G><<<p->asm_grid, kBlock, 0, p->stream>>>(P, xb32, p->asm_rpb, p->cnt, p->blk_sum, p->d_hint);
+    const size_t lds = sizeof(int) * ((size_t)p->asm_rpb + 1);
+    k_asm_fill<G><<<p->asm_grid, kBlock, lds, p->stream>>>(P, xb32, p->x, p->asm_rpb, p->cnt, p->blk_sum,
+                                                           p->rowptr, p->col, p->val, p->d_hdbl, S);   // (row-sum maxima: host only)
+}
+
+inline int assemble(machip_problem* p) {
+    if (p->csr_only) return fail(MACHIP_BAD_ARG, "handle wraps a caller CSR; nothing to assemble");
+    // the fill pass writes the column-panel form's per-row tables on the side where that form can run at this n (solver.h)
+    PanSpec S;
+    ST_TRY(p->sol.pan_spec_prepare(&S));
+    if (!p->xb_valid) {     // x came from the host (or a copy): the support bitmap is taken here; k_fw_final leaves the next iterate's
+        const int grid = std::max(1, (int)std::min<long>(kMaxGrid, (p->m + kBlock - 1) / kBlock));
+        k_x_bits<<<grid, kBlock, 0, p->stream>>>(p->x, p->m, p->tol_sel, p->xb);
+        p->xb_valid = true;
+    }
+    switch (p->asm_G) {
+        case 4: launch_asm<4>(p, S); break;
+        case 8: launch_asm<8>(p, S); break;
+        case 16: launch_asm<16>(p, S); break;
+        case 32: launch_asm<32>(p, S); break;
+        default: launch_asm<64>(p, S); break;
+    }
+    HIP_TRY(hipGetLastError());       // a refused launch must not leave stale row offsets behind a MACHIP_OK
+    const int gb = p->asm_grid;
+    // (both kernels wrote the host's copies into mapped pinned memory.  Round 5 tried a completion word published by the fill pass's
+    // last workgroup -- system-scope fence + ticket per workgroup -- for the host to spin on instead of this wait: 3 125 fences made
+    // the launch 312 us instead of 82)
+    HIP_TRY(hipStreamSynchronize(p->stream));
+    long nnz = 0, supp = 0;
+    int maxlen = 0;
+    double ln = 0.0;
+    for (int b = 0; b < gb; ++b) {
+        nnz += p->h_int[b]; supp += p->h_int[kAsmGrid + b]; maxlen = std::max(maxlen, p->h_int[2 * kAsmGrid + b]);
+        ln = std::max(ln, p->h_dbl[b]);
+    }
+    p->nnz = nnz; p->support = supp / 2; p->lnorm = ln; p->maxlen = maxlen;     // (two pattern slots per active candidate)
+    p->assembled = true;
+    return MACHIP_OK;
+}
+
+inline int alloc_common(machip_problem* p, int vbudget_mb = 0) {
+    ST_TRY(p->sol.init(p->n, p->stream, vbudget_mb));
+    HIP_TRY(hipHostMalloc((void**)&p->h_int, sizeof(int) * 3 * kAsmGrid, hipHostMallocMapped));
+    HIP_TRY(hipHostMalloc((void**)&p->h_dbl, sizeof(double) * std::max(4 * kMaxGrid, kAsmGrid), hipHostMallocMapped));
+    HIP_TRY(hipHostGetDevicePointer((void**)&p->d_hint, p->h_int, 0));
+    HIP_TRY(hipHostGetDevicePointer((void**)&p->d_hdbl, p->h_dbl, 0));
+    return MACHIP_OK;
+}
+
+// What assemble writes, on the handle and on every lane: L(x) with room for the whole union pattern, the support bitmaps of x / x_next
+inline int alloc_assembly(machip_problem* p) {
+    const size_t cap = (size_t)p->P + (size_t)p->n + 8;
+    ST_TRY(dev_alloc(&p->cnt, (size_t)p->n + 1)); ST_TRY(dev_alloc(&p->blk_sum, 3 * kAsmGrid));
+    ST_TRY(dev_alloc(&p->rowptr, (size_t)p->n + 1)); ST_TRY(dev_alloc(&p->col, cap)); ST_TRY(dev_alloc(&p->val, cap));
+    ST_TRY(dev_alloc(&p->blk_lnorm, kAsmGrid));
+    ST_TRY(dev_alloc(&p->xb, (size_t)p->m / 64 + 2)); ST_TRY(dev_alloc(&p->xb_next, (size_t)p->m / 64 + 2));
+    p->sol.csr_cap = cap;
+    return MACHIP_OK;
+}
+
+// FW state of the handle and of a lane that takes part in a sweep, in two parts (the handle makes its assembly buffers in between):
+// next iterate, gradient and LP vertex -- the caller clears g -- and the select scratch
+inline int alloc_fw(machip_problem* p) {
+    const size_t mp = (size_t)p->m + 64 * 8;   // slack so a later all-gather padding fits
+    // each pointer guarded on its own: a failed allocation half way leaves nothing to leak when the next call retries
+    if (!p->x_next) ST_TRY(dev_alloc(&p->x_next, mp));
+    if (!p->g) ST_TRY(dev_alloc(&p->g, mp));
+    if (!p->s) ST_TRY(dev_alloc(&p->s, mp));
+    return MACHIP_OK;
+}
+inline int alloc_fw_select(machip_problem* p) {
+    if (!p->hist) ST_TRY(dev_alloc(&p->hist, (6 + kSelRep) * kBins));
+    if (!p->sel) ST_TRY(dev_alloc(&p->sel, 2));
+    if (!p->part_fw) ST_TRY(dev_alloc(&p->part_fw, 2 * kMaxGrid));
+    return MACHIP_OK;
+}
+
+// k-th largest of keys[0..m), k clamped to [0, m]: kernels.h's sel_launch on the problem's histogram, under option sel_small.
+inline int select_on(machip_problem* p, const double* keys, long k, SelState* st, int prefer_high, bool hist0_done = false) {
+    const Options& opt = p->sol.opt;
+    return sel_launch(p->stream, keys, p->m, std::max(0l, std::min(k, p->m)), st, p->hist, prefer_high, OPT(sel_small, 1) != 0, hist0_done);
+}
+
+inline int select_topk(machip_problem* p, long k, bool hist0_done = false) { return select_on(p, p->g, k, p->sel, 0, hist0_done); }
+
+// Contiguous candidate ranges: shard = ceil(m / R); rank r owns [r shard, (r+1) shard) clipped to m;
+// the gathered vector is padded to R shard entries.  The ONE place this arithmetic lives (machip_shard_plan exports it).
+inline void shard_plan(long m, int nranks, int rank, long* lo, long* hi, long* shard) {
+    const long sh = nranks > 0 ? (m + nranks - 1) / nranks : m;
+    *shard = sh;
+    *lo = std::min(m, sh * rank);
+    *hi = std::min(m, *lo + sh);
+}
+
+inline int run_fiedler(machip_problem* p, double tol, int max_steps, const double* x0, int warm_start,
+                       double* lambda2, machip_solve_stats* stats) {
+    if (!p->assembled) ST_TRY(assemble(p));
+    if (x0) {
+        HIP_TRY(hipMemcpyAsync(p->sol.start, x0, sizeof(double) * (size_t)p->n, hipMemcpyHostToDevice, p->stream));
+        HIP_TRY(hipStreamSynchronize(p->stream));
+        p->sol.have_start = true;
+        ++p->start_version;          // evaluation lanes must pick the new vector up (machip_eval_batch)
+    }
+    machip_solve_stats local;
+    memset(&local, 0, sizeof(local));
+    p->sol.maxlen_hint = p->maxlen;
+    p->sol.support_hint = (p->csr_only && !p->sol.chain_like) ? -1 : p->support;
+    p->sol.start_guess = x0 != nullptr;      // a caller's own start vector is taken as it is (no landscape weighting)
+    const int st = p->sol.solve(p->csr(), p->nnz, p->lnorm, tol, max_steps, (x0 == nullptr && warm_start) ? 1 : 0,
+                                kAuto, lambda2, &local);
+    p->sol.start_guess = false;
+    local.support = p->support;
+    if (stats) *stats = local;
+    p->have_vec = completed(st);
+    return st;
+}
+
+// machip_set_option on a handle: its lanes run on their owner's options
+inline void set_option(machip_problem* p, int id, long v) {
+    p->sol.opt.v[id] = v;
+    for (machip_problem* q : p->lanes) q->sol.opt.v[id] = v;
+}
+
+// the peers' waits on a rank that is gone end with an error, not a time-out
+inline void ipc_abort(machip_problem* p) {
+    k_ipc_abort<<<1, 64, 0, p->stream>>>(p->ipcg->view);
+    (void)hipStreamSynchronize(p->stream);
+}
+
+inline void destroy_handle(machip_problem* p) {
+    for (machip_problem* q : p->lanes) destroy_handle(q);
+    p->lanes.clear();
+    (void)hipSetDevice(p->device);
+    if (p->stream) (void)hipStreamSynchronize(p->stream);
+    if (p->is_lane) { p->prow = p->pcol = p->pk = nullptr; p->pw = nullptr; p->ci = p->cj = nullptr; p->cw = nullptr; }   // borrowed
+    if (p->comm) (void)ncclCommDestroy(p->comm);
+    if (p->lgroup) p->lgroup->abort();      // peers blocked in the group's barrier return an error instead of hanging
+    if (p->ipcg) {
+        if (!p->ipcg->clean_exit) ipc_abort(p);   // peers' waits end with an error, not a time-out
+        p->sol.ipc = nullptr;
+        p->ipcg.reset();                   // (~IpcGroup closes the mappings and frees the flag / error words)
+    }
+    p->sol.destroy();
+    void* ptrs[] = {p->prow, p->pcol, p->pk, p->pw, p->ci, p->cj, p->cw, p->x, p->x_next, p->g, p->s, p->scratch_m, p->cnt,
+                    p->blk_sum, p->rowptr, p->col, p->val, p->blk_lnorm, p->xb, p->xb_next, p->hist, p->sel, p->part_fw};
+    for (void* q : ptrs) if (q) (void)hipFree(q);
+    for (hipEvent_t e : {p->ev_g0, p->ev_g1, p->ev_g2}) if (e) (void)hipEventDestroy(e);
+    if (p->h_int) (void)hipHostFree(p->h_int);
+    if (p->h_dbl) (void)hipHostFree(p->h_dbl);
+    if (p->stream) (void)hipStreamDestroy(p->stream);
+    delete p;
+}
+
+// machip_create after its checks, on the device it set
+inline int create_handle(int device, int64_t n, int64_t n_fixed, const int32_t* fi, const int32_t* fj, const double* fw, int64_t m,
+                         const int32_t* ci, const int32_t* cj, const double* cw, double min_sel_tol, machip_problem** out) {
+    machip_problem* p = new machip_problem();
+    p->device = device; p->n = (int)n; p->m = p->m_pad = (long)m; p->tol_sel = min_sel_tol;
+    auto body = [&]() -> int {
+        HIP_TRY(hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking));
+        ST_TRY(build_pattern(p, n_fixed, fi, fj, fw, m, ci, cj, cw));
+        const size_t mp = (size_t)m + 64 * 8;   // slack so a later all-gather padding fits
+        ST_TRY(dev_alloc(&p->ci, mp)); ST_TRY(dev_alloc(&p->cj, mp)); ST_TRY(dev_alloc(&p->cw, mp));
+        ST_TRY(dev_alloc(&p->x, mp)); ST_TRY(alloc_fw(p));
+        if (m) {
+            HIP_TRY(hipMemcpyAsync(p->ci, ci, sizeof(int) * (size_t)m, hipMemcpyHostToDevice, p->stream));
+            HIP_TRY(hipMemcpyAsync(p->cj, cj, sizeof(int) * (size_t)m, hipMemcpyHostToDevice, p->stream));
+            HIP_TRY(hipMemcpyAsync(p->cw, cw, sizeof(double) * (size_t)m, hipMemcpyHostToDevice, p->stream));
+        }
+        HIP_TRY(hipMemsetAsync(p->x, 0, sizeof(double) * mp, p->stream));
+        HIP_TRY(hipMemsetAsync(p->g, 0, sizeof(double) * mp, p->stream));
+        HIP_TRY(hipStreamSynchronize(p->stream));      // (the caller's arrays are borrowed for the duration of the call only)
+        ST_TRY(alloc_assembly(p));
+        ST_TRY(alloc_fw_select(p));
+        ST_TRY(alloc_common(p));
+        p->sol.pat = p->pattern();
+        p->sol.pan_allowed = p->band_dups_ok;     // panel.h walks rows as this library assembles them (diagonal first)
+        // pose-graph shape: do the fixed edges contain (nearly) the whole chain (i, i+1)?  Decides
+        // whether the preconditioned eigen-solver mode is considered (solver.h, precond.h).
+        {
+            std::vector<char> has((size_t)n, 0);
+            for (int64_t e = 0; e < n_fixed; ++e) {
+                const int a = std::min(fi[e], fj[e]), b = std::max(fi[e], fj[e]);
+                if (a >= 0 && b < n && b == a + 1 && fw[e] > 0.0) has[(size_t)a] = 1;
+            }
+            long cnt = 0;
+            for (int64_t i = 0; i + 1 < n; ++i) cnt += has[(size_t)i];
+            p->sol.chain_like = cnt >= (long)(0.98 * (double)(n - 1));
+            p->sol.chain_edges = cnt;
+        }
+        return MACHIP_OK;
+    };
+    const int st = body();
+    if (st != MACHIP_OK) { destroy_handle(p); return st; }
+    *out = p;
+    return MACHIP_OK;
+}
+
+// machip_fiedler_csr after its argument checks
+inline int fiedler_csr(int device, int64_t n, const int32_t* indptr, const int32_t* indices, const double* data, double tol,
+                       int max_steps, const double* x0, double* lambda2, double* v_out, double* X_out, int q, machip_solve_stats* stats) {
+    // The row pointers are validated as a whole BEFORE anything is read through them (this entry point takes arbitrary
+    // caller matrices): first entry 0, monotone, hence every row's range inside [0, indptr[n]) -- and all of that on the
+    // host, before the first device call, so a malformed matrix is a BAD_ARG on any machine.
+    const long nnz = indptr[n];
+    if (indptr[0] != 0 || nnz < 0) return fail(MACHIP_BAD_ARG, "bad indptr: indptr[0] must be 0 and indptr[n] >= 0 (int32 row pointers: nnz < 2^31)");
+    for (int64_t r = 0; r < n; ++r)
+        if (indptr[r + 1] < indptr[r]) return fail(MACHIP_BAD_ARG, "indptr not monotone");
+    double lnorm = 0.0;
+    int maxlen_csr = 0;
+    long chain_cnt = 0;   // super-diagonal entries: a pose-graph Laplacian carries the chain (i, i+1)
+    for (int64_t r = 0; r < n; ++r) {
+        double s = 0.0;
+        for (long pp = indptr[r]; pp < (long)indptr[r + 1]; ++pp) {
+            if (indices[pp] < 0 || indices[pp] >= n) return fail(MACHIP_BAD_ARG, "column index out of range");
+            s += std::fabs(data[pp]);
+            if (indices[pp] == r + 1 && data[pp] != 0.0) ++chain_cnt;
+        }
+        lnorm = std::max(lnorm, s);   // nx:232
+        maxlen_csr = std::max(maxlen_csr, (int)(indptr[r + 1] - indptr[r]));
+    }
+    if (machip_device_count() <= 0) return fail(MACHIP_NO_DEVICE, "no HIP device visible");
+    HIP_TRY(hipSetDevice(device));
+    // One CSR-only handle is kept between calls (stream, ~25 device buffers, pinned mirrors, chunk graphs: creating them
+    // costs more than a small solve -- a Madow loop or a sweep through find_fiedler_pair paid it per call).  It is reused
+    // when device and n match and the matrix fits; every solve starts from a clean solver state, so a cached handle
+    // computes exactly what a fresh one does.  A second thread calling concurrently gets a fresh handle of its own.
+    std::unique_lock<std::mutex> lk(g_csr_mu, std::try_to_lock);
+    machip_problem* p = nullptr;
+    bool cached = false;
+    if (lk.owns_lock() && g_csr_cache && g_csr_cache->device == device && g_csr_cache->n == (int)n && (long)g_csr_cache->sol.csr_cap >= nnz) {
+        p = g_csr_cache;
+        cached = true;
+    } else {
+        if (lk.owns_lock() && g_csr_cache) { destroy_handle(g_csr_cache); g_csr_cache = nullptr; }
+        p = new machip_problem();
+        p->device = device; p->n = (int)n; p->csr_only = true;
+    }
+    auto body = [&]() -> int {
+        if (!cached) {
+            const size_t cap = (size_t)nnz + (size_t)nnz / 4 + 64;
+            HIP_TRY(hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking));
+            ST_TRY(dev_alloc(&p->rowptr, (size_t)n + 1)); ST_TRY(dev_alloc(&p->col, cap)); ST_TRY(dev_alloc(&p->val, cap));
+            ST_TRY(alloc_common(p));
+            p->sol.csr_cap = cap;
+        }
+        HIP_TRY(hipMemcpyAsync(p->rowptr, indptr, sizeof(int) * ((size_t)n + 1), hipMemcpyHostToDevice, p->stream));
+        if (nnz) {
+            HIP_TRY(hipMemcpyAsync(p->col, indices, sizeof(int) * (size_t)nnz, hipMemcpyHostToDevice, p->stream));
+            HIP_TRY(hipMemcpyAsync(p->val, data, sizeof(double) * (size_t)nnz, hipMemcpyHostToDevice, p->stream));
+        }
+        HIP_TRY(hipStreamSynchronize(p->stream));
+        p->nnz = nnz; p->lnorm = lnorm; p->maxlen = maxlen_csr; p->assembled = true; p->have_vec = false;
+        // clean solver state: nothing learnt from, or left over by, an earlier matrix
+        Solver& S = p->sol;
+        S.forget_history();
+        S.have_start = false; S.J_last = 0; S.last_was_lob = false; S.last_seq_f32 = false; S.solver_mode = 0; S.precision = 0;
+        S.opt = default_options();       // (a cached handle too starts from the process defaults of THIS call: include/machip.h says so -- advisor finding on round 5)
+        // same solver selection as a MAC handle gets (solver.h): chain-like matrices may run the
+        // single-workgroup / preconditioned modes; "support" = off-chain edges
+        p->sol.chain_like = chain_cnt >= (long)(0.98 * (double)(n - 1));
+        p->sol.chain_edges = chain_cnt;
+        p->support = std::max<long>(0, (nnz - n) / 2 - chain_cnt);
+        return MACHIP_OK;
+    };
+    int st = body();
+    if (st == MACHIP_OK) st = machip_fiedler(p, tol, max_steps, x0, 0, lambda2, v_out, X_out, q, stats);
+    const std::string keep = g_err;
+    if (lk.owns_lock() && completed(st)) g_csr_cache = p;          // keep it for the next call
+    else {
+        if (cached) g_csr_cache = nullptr;
+        destroy_handle(p);
+    }
+    g_err = keep;
+    return st;
+}
+
+inline void release_cache() {
+    std::lock_guard<std::mutex> lk(g_csr_mu);
+    if (g_csr_cache) { destroy_handle(g_csr_cache); g_csr_cache = nullptr; }
+}
+
+inline int profile_spmv(machip_problem* p, int reps, double* avg_us, double* bytes_per_launch) {
+    if (!p->assembled) ST_TRY(assemble(p));
+    Solver& S = p->sol;
+    const SpmvPlan pl = plan_pipe(p->sol.opt, p->n, p->nnz, p->maxlen);
+    // The dominant kernel of the path: one fused Lanczos step (k_pipe_*).  Re-launching step 1 of
+    // a scratch sequence is idempotent (same Z read, same Z/V column written), so `reps`
+    // back-to-back launches time exactly the kernel the solve runs, on the same L(x).
+    k_fill_start<<<S.vgrid(), kBlock, 0, p->stream>>>(S.u, p->n, 77ull);
+    const PipeView L = S.pview(pl);
+    k_pipe_init<<<pl.grid, kBlock, 0, p->stream>>>(L, S.u, (int)(++S.epoch));
+    launch_pipe(pl, p->stream, p->csr(), L, 0);
+    launch_pipe(pl, p->stream, p->csr(), L, 1);
+    k_pipe_tail<<<1, 64, 0, p->stream>>>(L, 2);      // jA = 2
+    for (int i = 0; i < 3; ++i) launch_pipe(pl, p->stream, p->csr(), L, 0);
+    HIP_TRY(hipEventRecord(S.ev0, p->stream));
+    for (int i = 0; i < reps; ++i) launch_pipe(pl, p->stream, p->csr(), L, 0);
+    HIP_TRY(hipEventRecord(S.ev1, p->stream));
+    HIP_TRY(hipEventSynchronize(S.ev1));
+    float ms = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms, S.ev0, S.ev1));
+    *avg_us = 1e3 * (double)ms / reps;
+    if (bytes_per_launch) {
+        // SURVEY 8(d) B_spmv = nnz*(8+4) + (n+1)*4 + n*8 [x] + n*8 [y], with the fused vector
+        // work on top: the gathered operand is the 16-byte record Z[c] (counted once per row),
+        // own-row Z read 16 B, next Z written 16 B, Lanczos vector v_j written 8 B.
+        *bytes_per_launch = (double)p->nnz * 12.0 + ((double)p->n + 1.0) * 4.0 + (double)p->n * 56.0;
+    }
+    return MACHIP_OK;
+}
+
+inline int membench(int64_t bytes, int reps, double* read_gbs, double* triad_gbs) {
+    const long cnt2 = (long)(bytes / 16);
+    double2 *a = nullptr, *b = nullptr, *c = nullptr;
+    double* out = nullptr;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    hipStream_t ms_ = nullptr;
+    auto body = [&]() -> int {
+        HIP_TRY(hipStreamCreateWithFlags(&ms_, hipStreamNonBlocking));      // (never the legacy stream)
+        ST_TRY(dev_alloc(&a, (size_t)cnt2)); ST_TRY(dev_alloc(&b, (size_t)cnt2)); ST_TRY(dev_alloc(&c, (size_t)cnt2)); ST_TRY(dev_alloc(&out, 8));
+        HIP_TRY(hipMemsetAsync(a, 0, (size_t)cnt2 * 16, ms_)); HIP_TRY(hipMemsetAsync(b, 0, (size_t)cnt2 * 16, ms_)); HIP_TRY(hipMemsetAsync(c, 0, (size_t)cnt2 * 16, ms_));
+        HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1));
+        const int grid = 256 * 16;           // 16 workgroups of 256 threads per CU
+        float ms = 0.f;
+        k_mb_read<<<grid, kBlock, 0, ms_>>>(a, cnt2, out);
+        HIP_TRY(hipEventRecord(e0, ms_));
+        for (int r = 0; r < reps; ++r) k_mb_read<<<grid, kBlock, 0, ms_>>>(r & 1 ? b : a, cnt2, out);
+        HIP_TRY(hipEventRecord(e1, ms_)); HIP_TRY(hipEventSynchronize(e1));
+        HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
+        *read_gbs = (double)cnt2 * 16.0 * reps / (ms * 1e-3) / 1e9;
+        k_mb_triad<<<grid, kBlock, 0, ms_>>>(a, b, c, 3.0, cnt2);
+        HIP_TRY(hipEventRecord(e0, ms_));
+        for (int r = 0; r < reps; ++r) k_mb_triad<<<grid, kBlock, 0, ms_>>>(a, b, c, 3.0, cnt2);
+        HIP_TRY(hipEventRecord(e1, ms_)); HIP_TRY(hipEventSynchronize(e1));
+        HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
+        *triad_gbs = (double)cnt2 * 48.0 * reps / (ms * 1e-3) / 1e9;      // two reads + one write per element
+        HIP_TRY(hipGetLastError());
+        return MACHIP_OK;
+    };
+    const int st = body();
+    const std::string keep = g_err;
+    if (ms_) (void)hipStreamSynchronize(ms_);
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+    for (void* q : {(void*)a, (void*)b, (void*)c, (void*)out}) if (q) (void)hipFree(q);
+    if (ms_) (void)hipStreamDestroy(ms_);
+    g_err = keep;
+    return st;
+}
+
+}  // namespace machip

@@ -169,6 +169,8 @@ struct Solver {
     long support_hint = -1;     // active candidate edges of the matrix about to be solved (-1 = unknown)
     long hist_lan_steps = -1, hist_lob_iters = -1;   // steps / iterations of the last solve in each mode
     long hist_exact_iters = -1;                       // ... of the last solve the exact chain + closures preconditioner served
+    // nothing learnt from an earlier problem (the cached CSR handle, an evaluation lane): no previous vector, no warm-start credit, no step counts
+    void forget_history() { have_prev = false; warm_skip = 0; warm_fails = 0; last_pr = 0.0; hist_lan_steps = -1; hist_lob_iters = -1; hist_exact_iters = -1; last_steps = 0; last_steps_lowp = 0; }
     // Lanczos -> exact hand-over (solve(): chain-like graphs beyond the single-workgroup sizes with at most wb_soft() closures): the
     // Lanczos loop gives up when its own forecast of the remaining steps costs more than 1.3x the exact mode's estimate, twice in a row
     static constexpr int kSwitchToExact = 1000;       // internal status of solve_lanczos, never leaves solve()
