@@ -43,7 +43,7 @@ enum EspRelaxSpace : int { kEspRelaxNode = 0, kEspRelaxEdge = 1, kEspRelaxEdgeTr
 constexpr int kEspMaxFold = 256;
 constexpr int kEspDefaultFold = 64;
 constexpr int kEspGrid = 256;          // workgroups of the score / update pass (= partials of the argmax)
-constexpr int kEspGjLookMin = 1024;    // look-ahead pivot blocks from this many rows on (solver.h: option gj_look_min)
+constexpr int kEspGjLookMin = 1024;    // look-ahead pivot blocks from this many rows on (solver_lob.h: option gj_look_min)
 
 struct EspBest {
     double val;
@@ -300,7 +300,7 @@ struct machip_esp {
     }
 
     // A^-1 of the ld x ld matrix in `src`: ld / 32 blocked Gauss-Jordan steps on the matrix cores, ping-pong between src and dst,
-    // look-ahead pivot blocks from 1 024 rows on -- exactly as solver.h inverts the capacitance matrix (woodbury.h).  The result
+    // look-ahead pivot blocks from 1 024 rows on -- exactly as solver_lob.h inverts the capacitance matrix (woodbury.h).  The result
     // is in `src` afterwards (the pointers are swapped per step); *bad <- 1 on a non-positive pivot.  LD: the pivot blocks'
     // log-determinants into ldet[ld / 32] as well.
     template <bool LD>

@@ -411,7 +411,7 @@ __global__ __launch_bounds__(kBlock) void k_spmv_stream(CsrView A, const double*
     op.end(sm);
 }
 
-// ---- landscape weighting of the cold-start vector (late round 5; solver.h `landscape_start`) ----------------
+// ---- landscape weighting of the cold-start vector (late round 5; solver_lanczos.h `landscape_start`) ----------------
 // On sparse random graphs the Fiedler vector is LOCALISED: a handful of vertices carry it (participation ratio 1-5 on every
 // iterate of configs[1] / configs[3]) -- the weakest spot of the graph, which the Frank-Wolfe update then reinforces, so the
 // spot moves every iteration and the previous vector is no better a start than a random one (measured: `use_cache` +3 % steps).
@@ -570,7 +570,7 @@ struct PipeViewT {
     int chunk;        // > 0: this chunk has no tail kernel -- its last step (jrel == chunk - 1) advances jN itself, and its records
                       // reach the host through the NEXT chunk's first step (or a tail kernel the host adds when no chunk follows)
     int pub;          // > 0: the chunk before this one had `pub` steps and no tail: the first step publishes its records
-    int pubstep;      // != 0: EVERY step hands its three values (alpha_{j-1}, l1_{j-1}, beta_j) to the host as it derives them (solver.h,
+    int pubstep;      // != 0: EVERY step hands its three values (alpha_{j-1}, l1_{j-1}, beta_j) to the host as it derives them (solver_lanczos.h,
                       // "streamed records": the host follows the recurrence step by step and decides where the solve ends)
     double* sig;      // != nullptr: SHIFTED records (panel_u.h, round 6): the sums are those of (u_j, v_j) with u_j = t_j - sigma_j v_j,
                       // sigma_j = alpha_{j-1}; sig[jrel & 1] = sigma_{j-1} on entry of step j, the prologue adds alpha'_{j-1} = u.v and
@@ -757,7 +757,7 @@ __device__ __forceinline__ void pipe_publish(const PV& L, const PipeCoef& c, int
     }
     // (round 5: no system-scope fence / release in front of the flag -- they made the one wave wait for the PCIe round trip of its
     // record stores.  The host never trusts the flag alone: every record slot of the chunk was poisoned with NaN before the chunk
-    // was enqueued and is awaited individually (solver.h wait_slot), so a flag that overtakes its records costs nothing.)
+    // was enqueued and is awaited individually (solver_lanczos.h lan_chunk_await), so a flag that overtakes its records costs nothing.)
     if (threadIdx.x == 0) {
         const unsigned long long epoch = (unsigned long long)(unsigned int)L.st->epoch;
         __hip_atomic_store(L.hflag, (epoch << 32) | (unsigned long long)(unsigned int)j, __ATOMIC_RELAXED,
@@ -1232,7 +1232,7 @@ __global__ __launch_bounds__(kBlock) void k_resid_l1(const double* __restrict__ 
     for (int r = blockIdx.x * kBlock + threadIdx.x; r < n; r += gridDim.x * kBlock) {
         const double vr = v[r];
         s += fabs(w[r] - rq * vr);
-        q4 += (vr * vr) * (vr * vr);       // sum v^4 of the unit vector: 1 / (its participation ratio) -- how localised the pair is (solver.h, landscape gate)
+        q4 += (vr * vr) * (vr * vr);       // sum v^4 of the unit vector: 1 / (its participation ratio) -- how localised the pair is (solver_lanczos.h, landscape gate)
     }
     s = block_sum(s, sm);
     q4 = block_sum(q4, sm);

@@ -225,7 +225,7 @@ void launch_asm(machip_problem* p, const PanSpec& S) {
 
 inline int assemble(machip_problem* p) {
     if (p->csr_only) return fail(MACHIP_BAD_ARG, "handle wraps a caller CSR; nothing to assemble");
-    // the fill pass writes the column-panel form's per-row tables on the side where that form can run at this n (solver.h)
+    // the fill pass writes the column-panel form's per-row tables on the side where that form can run at this n (solver_panel.h)
     PanSpec S;
     ST_TRY(p->sol.pan_spec_prepare(&S));
     if (!p->xb_valid) {     // x came from the host (or a copy): the support bitmap is taken here; k_fw_final leaves the next iterate's

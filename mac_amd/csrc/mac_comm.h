@@ -140,7 +140,7 @@ inline int compute_gradient(machip_problem* p, bool have_vec_now = false, long f
 }
 
 // Collective eigen-solve of an in-process communicator whose step is row-partitioned: every rank has assembled the same
-// L(x); rank 0's solver drives all ranks' streams (solver.h, ShardGroup) and hands lambda_2, the statistics and the
+// L(x); rank 0's solver drives all ranks' streams (solver_shard.h, ShardGroup) and hands lambda_2, the statistics and the
 // Fiedler vector to the peers.
 inline int group_fiedler(machip_problem* p, double tol, int max_steps, int warm_start, double* lambda2, machip_solve_stats* stats) {
     LocalGroup& G = *p->lgroup;

@@ -13,7 +13,7 @@
 //     L v_j = (L u_{j-1} - (alpha_{j-1} - sigma_{j-1}) w_{j-1}) / beta_j,
 // the factor becomes |alpha_{j-1} - alpha_{j-2}| / beta_j, which is << 1 once the recurrence has left its first steps (alpha_j settles
 // at the centre of the spectrum): tools/experiments/shifted_operand_emulation.py -- same step counts, same lambda_2, drift 1e-16 on every
-// configs[1] / configs[3] iterate.  The host watches the accumulated factor (solver.h, `amp`) and restarts a sequence in record form if it
+// configs[1] / configs[3] iterate.  The host watches the accumulated factor (solver_lanczos.h, `amp`) and restarts a sequence in record form if it
 // ever grows (never seen; forced by option panel_u_amp in the tests).
 //
 // The recurrence in the shifted variables (alpha' = alpha - sigma):  the six sums are MEASURED on (u_j, v_j) exactly as kernels.h
@@ -75,7 +75,7 @@ __global__ __launch_bounds__(kPanThreads) void k_pan_mul8(const double* __restri
     __shared__ double yblk[ROWS];
     static_assert((SVN + ROWS) * 8 <= 163840 - 128, "panel + row-block image exceed the LDS");
     const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    // (b_first: row-partitioned step between processes, solver.h launch_chunk_ipc_pan -- this rank launches the row blocks its rows of the
+    // (b_first: row-partitioned step between processes, solver_shard.h launch_chunk_ipc_pan -- this rank launches the row blocks its rows of the
     // row kernel need, all panels each; cells, sums and their order are those of the whole launch)
     const int bl = blockIdx.x / A.NP, p = blockIdx.x - bl * A.NP, b = bl + b_first;
     const int c0 = p * A.C;

@@ -215,7 +215,7 @@ __global__ __launch_bounds__(256) void k_gj_step(const double* __restrict__ src,
     __shared__ double sT[kGjT][kGjB + 1];      // -(A_iK P); rows inside the pivot block: P
     __shared__ double sB[kGjB][kGjT + 1];      // A_Kj: pivot rows x columns of the tile; columns inside the pivot block: identity
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    // Look-ahead (large matrices, solver.h): with `pin` the inverse of THIS step's pivot block comes from the previous launch -- the
+    // Look-ahead (large matrices, solver_lob.h): with `pin` the inverse of THIS step's pivot block comes from the previous launch -- the
     // workgroup whose tile holds the NEXT pivot block inverts it once its tile is updated and leaves it in `pout` --, so only one
     // workgroup per step runs the ~7 us scalar inversion instead of all of them in front of their products (1 156 workgroups at
     // s = 2 137: 40 -> ~20 us per step).  That workgroup is dispatched first: the tile grid is rotated so that (0, 0) is its tile.

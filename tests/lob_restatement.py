@@ -1,4 +1,4 @@
-"""NumPy/SciPy restatement of MAC's preconditioned eigen-solver (mac_amd/csrc/solver.h `solve_lob`, precond.h, woodbury.h), written
+"""NumPy/SciPy restatement of MAC's preconditioned eigen-solver (mac_amd/csrc/solver_lob.h `solve_lob`, precond.h, woodbury.h), written
 by reading those headers (for the tests; not a port of any kernel).  It exists to count: everything the suite compares -- lambda_2,
 the Fiedler vector, the residual -- is decided by the sparse L(x); the preconditioner only proposes search directions, so a kernel
 of it can be subtly wrong with every value right.  What a wrong preconditioner costs is iterations, and `stats.lanczos_steps` of a

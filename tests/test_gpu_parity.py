@@ -273,7 +273,7 @@ def test_preconditioned_mode_fallbacks_and_errors():
 def test_lanczos_hands_over_to_the_exact_mode_on_its_own_forecast():
     """Chain of 9 000 nodes + 1 800 short closures (20 % of n: denser than the static rule for the preconditioned mode admits, no history
     on a fresh handle): the automatic mode starts with Lanczos, whose convergence forecast says thousands of steps to go, and hands
-    over to the exact chain + closures mode (solver.h, switch_est_us) -- far fewer steps than the forced Lanczos solve, the same
+    over to the exact chain + closures mode (solver.h switch_est_us, solver_lanczos.h lan_vote) -- far fewer steps than the forced Lanczos solve, the same
     lambda_2 (1e-8) and vector, SciPy's shift-invert value; a second solve starts in the exact mode.  A warm start from the converged
     vector stays with Lanczos (its forecast is short)."""
     import scipy.sparse.linalg as spla
@@ -673,7 +673,7 @@ def test_teacher_forced_config4_all_twenty_iterates(form):
 
 
 def test_landscape_field_matches_numpy_and_weighted_cold_start_needs_fewer_steps():
-    """Late round 5 (kernels.h k_land_*, solver.h landscape_start): a cold Lanczos start is the stored start vector times
+    """Late round 5 (kernels.h k_land_*, solver_lanczos.h landscape_start): a cold Lanczos start is the stored start vector times
     (u / max u)^128, u = three Jacobi sweeps on L u = 1 from u = 1/diag -- the Fiedler vector of a sparse random graph is localised
     on the peaks of that landscape (participation ratio 1-5 on every iterate of configs[1] / configs[3]).  (a) machip_landscape
     against NumPy on the assembled Laplacian, both SpMV row mappings; (b) on the first two matrices of the configs[1] trajectory the
@@ -1272,7 +1272,7 @@ def _stream_cases():
 
 @pytest.mark.parametrize("case", list(_stream_cases()), ids=lambda c: c[0])
 def test_streamed_records_end_a_solve_at_the_same_step_whatever_feeds_the_queue(case):
-    """Round 5, streamed records (solver.h): every Lanczos step hands its (alpha, l1, beta) to the host, which analyses the
+    """Round 5, streamed records (solver_lanczos.h): every Lanczos step hands its (alpha, l1, beta) to the host, which analyses the
     tridiagonal at a sequence of points that depends on the records alone and ends the solve at the first point whose residual
     estimate is below the trigger.  WHAT feeds the queue -- the timing-driven feeder of the unpartitioned solve (stream = 1), the
     chunk-at-a-time feeder of the row-partitioned solves (stream = 2), an impatient feeder (look 2, no whole chunks ahead) -- must
@@ -2555,13 +2555,13 @@ def test_ipc_row_partitioned_eigensolve_between_processes_is_bit_identical(world
 
 @pytest.mark.parametrize("world", [2, 3])
 def test_ipc_row_partitioned_panel_step_is_bit_identical_to_one_rank(world):
-    """VERDICT r5 item 2 (round 6, solver.h launch_chunk_ipc_pan): the row-partitioned eigen-solve between processes in COLUMN-PANEL form.  The
+    """VERDICT r5 item 2 (round 6, solver_shard.h launch_chunk_ipc_pan): the row-partitioned eigen-solve between processes in COLUMN-PANEL form.  The
     shifted recurrence partitions by the row kernel's workgroups: a rank launches `k_pan_mul8` for the row blocks its rows lie in (a block
     that straddles two ranks is multiplied by both) and `k_pan_finu` for its workgroups, which write their rows of the next 8-byte operand and
     their six sums into every rank's copy (the operand lives in the IPC-mapped record buffers).  configs[3] with the panel step forced, five
     iterations, `world` processes on this one GPU: f / dual / ||g|| / step counts and the final x equal the one-process panel run bit for bit,
     every solve ran the panel step (mode 2) row-partitioned (comm mode 5).  (Round 5's library lost 2 of 30 such runs in GATHER form to a
-    timing-dependent analysis point of the chunk feeder -- solver.h `more_coming` -- which this test family caught only now.)"""
+    timing-dependent analysis point of the chunk feeder -- solver_lanczos.h `more_coming` -- which this test family caught only now.)"""
     single = _run_ipc_job(1, "c4", 5, opts={"panel": 1})[0]
     assert single[0] == 0 and single[1][0] == "RESULT" and set(single[1][1]["solver_modes"]) == {2}, single
     multi = _run_ipc_job(world, "c4", 5, opts={"panel": 1})
@@ -2575,7 +2575,7 @@ def test_ipc_row_partitioned_panel_step_is_bit_identical_to_one_rank(world):
 
 
 def test_ipc_ranks_agree_on_where_every_solve_ends_run_after_run():
-    """Round 6 regression (solver.h, `more_coming`): the chunk feeder of a row-partitioned solve analysed the tridiagonal at the END OF THE
+    """Round 6 regression (solver_lanczos.h, `more_coming`): the chunk feeder of a row-partitioned solve analysed the tridiagonal at the END OF THE
     QUEUE whenever the records up to there had landed before the loop came by -- short of the next analysis point, and only on the rank whose
     timing happened to be so; from there the ranks' analysis points differed, one went to the explicit check while the other waited for more
     steps, and both sat out the time limit: 2 of 30 two-rank configs[3] runs of round 5's library, 3 of 14 with the panel step.  Eight
@@ -2669,7 +2669,7 @@ def test_bench_dry_run_checks_first_contact_on_one_gpu():
 
 
 def test_exact_preconditioner_counts_fixed_off_chain_edges_as_closures():
-    """ADVICE r3 (solver.h wb_alloc): the Woodbury buffers are sized from the ACTIVE CANDIDATES, but every off-chain entry of L(x) is a
+    """ADVICE r3 (solver_lob.h wb_alloc): the Woodbury buffers are sized from the ACTIVE CANDIDATES, but every off-chain entry of L(x) is a
     closure -- fixed edges off the chain included.  400 fixed closures + 40 candidates: the first extraction finds more closures than
     the buffers hold (256), the buffers must grow and the exact preconditioner must run (a handful of iterations), not be skipped
     silently for the tridiagonal one (hundreds on this weakly linked chain).  lambda_2 against SciPy's shift-invert Lanczos."""

@@ -373,7 +373,8 @@ def test_record_follower_ends_a_sequence_on_the_records_alone():
     increasing, at most a chunk apart, every point before the last has its estimate above the target and the last one below
     (estimates recomputed here with LAPACK); the last point is the first crossing (to within two steps); records beyond it do not
     matter, fewer records give a prefix of the same points; a breakdown ends the sequence where it happens; a constant start
-    vector is refused."""
+    vector is refused.  (Estimates, breakdown and refusal are Follower::ingest, which the chunk-granular loop of solver_lanczos.h
+    reads its records through as well.)"""
     rng = np.random.default_rng(3)
     n = 600
     a = rng.integers(0, n, 6 * n); b = rng.integers(0, n, 6 * n)

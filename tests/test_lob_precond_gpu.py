@@ -1,4 +1,4 @@
-"""MAC's preconditioned eigen-solver on the GPU (solver mode 2: precond.h, woodbury.h, solve_lob in solver.h), pinned through the
+"""MAC's preconditioned eigen-solver on the GPU (solver mode 2: precond.h, woodbury.h, solve_lob in solver_lob.h), pinned through the
 iterations the library reports.
 
 The preconditioner only proposes search directions: lambda_2, the Fiedler vector and the residual are decided by the sparse L(x),

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""CPU emulation behind the landscape weighting of the cold-start vector (mac_amd/csrc/kernels.h k_land_*, solver.h landscape_start).
+"""CPU emulation behind the landscape weighting of the cold-start vector (mac_amd/csrc/kernels.h k_land_*, solver_lanczos.h landscape_start).
 
 Runs the bench trajectory of a config in NumPy / SciPy (plain Lanczos on 1-perp, no re-orthogonalisation, stop when the recurrence's
 residual estimate passes the reference's rule nx:232,246) and counts Lanczos steps per solve for several start vectors:
