@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define MACHIP_ABI_VERSION 18   /* 18: machip_eig_exchange_free (the exchange on lambda_2 on MACHIP_EIG_MATRIX_FREE / _TREE handles; option eig_xch_free_swaps), machip_eig_history; 17: MACHIP_EIG_MATRIX_FREE_TREE (GreedyEig on any connected fixed graph without a dense Sigma; machip_eig_seeds); 16: MACHIP_EIG_MATRIX_FREE (GreedyEig on a chain without a dense Sigma; options eig_free_rows, eig_free_split); 15: machip_eig_exchange (best-swap local search on lambda_2; option eig_xch_max_mb); 14: machip_esp_exchange_edge (the exchange in the candidates' space on MACHIP_ESP_EDGE_RELAX / MACHIP_ESP_EDGE_RELAX_TREE handles); 13: machip_esp_exchange (best-swap local search on the log tree count; options esp_xch_lds_kb, esp_xch_max_mb, esp_xch_profile); 12: MACHIP_ESP_EDGE_RELAX (the relaxation in the candidates' space on a chain-fixed graph; machip_esp_relax_info); 11: MACHIP_ESP_SPANNING_TREE (the matrix-free route of GreedyESP for any connected fixed graph; machip_esp_tree_plan, machip_esp_seeds); 10: MACHIP_ESP_MATRIX_FREE (GreedyESP on a chain without a dense Sigma, option esp_free_split); 9: the relaxation of GreedyESP's problem (machip_esp_relax_*); 8: GreedyEig handle (machip_eig_*); 7: GreedyESP handle (machip_esp_*); 6: machip_solve_stats.drift, machip_panel_plan fills 12 entries; 5: per-handle option table (machip_set_option), machip_comm_drop_ipc; 4: inter-process communicator */
+#define MACHIP_ABI_VERSION 19   /* 19: machip_lowest_pairs, machip_lowest_pairs_csr (the q lowest non-trivial eigenpairs, every one converged to the stop rule; option pairs_vcap), machip_lowest_pairs_time, machip_gradient_block; 18: machip_eig_exchange_free (the exchange on lambda_2 on MACHIP_EIG_MATRIX_FREE / _TREE handles; option eig_xch_free_swaps), machip_eig_history; 17: MACHIP_EIG_MATRIX_FREE_TREE (GreedyEig on any connected fixed graph without a dense Sigma; machip_eig_seeds); 16: MACHIP_EIG_MATRIX_FREE (GreedyEig on a chain without a dense Sigma; options eig_free_rows, eig_free_split); 15: machip_eig_exchange (best-swap local search on lambda_2; option eig_xch_max_mb); 14: machip_esp_exchange_edge (the exchange in the candidates' space on MACHIP_ESP_EDGE_RELAX / MACHIP_ESP_EDGE_RELAX_TREE handles); 13: machip_esp_exchange (best-swap local search on the log tree count; options esp_xch_lds_kb, esp_xch_max_mb, esp_xch_profile); 12: MACHIP_ESP_EDGE_RELAX (the relaxation in the candidates' space on a chain-fixed graph; machip_esp_relax_info); 11: MACHIP_ESP_SPANNING_TREE (the matrix-free route of GreedyESP for any connected fixed graph; machip_esp_tree_plan, machip_esp_seeds); 10: MACHIP_ESP_MATRIX_FREE (GreedyESP on a chain without a dense Sigma, option esp_free_split); 9: the relaxation of GreedyESP's problem (machip_esp_relax_*); 8: GreedyEig handle (machip_eig_*); 7: GreedyESP handle (machip_esp_*); 6: machip_solve_stats.drift, machip_panel_plan fills 12 entries; 5: per-handle option table (machip_set_option), machip_comm_drop_ipc; 4: inter-process communicator */
 
 typedef enum machip_status {
     MACHIP_OK = 0,
@@ -110,10 +110,49 @@ int machip_get_laplacian(machip_problem* p, int32_t* indptr, int32_t* indices, d
  * accurate to 1e-3 .. 1e-7 (tests: er2000_x0), after a short sequence (a restart from an almost
  * converged vector, 33 steps on er300_x0) or after the preconditioned / exact modes, which keep
  * no Krylov basis, they are an arbitrary orthonormal completion.  A caller that needs more than
- * the Fiedler pair must not take them for eigenvectors. */
+ * the Fiedler pair must not take them for eigenvectors: machip_lowest_pairs (below) returns q
+ * eigenpairs that each obey the stop rule. */
 int machip_fiedler(machip_problem* p, double tol, int max_steps, const double* x0, int warm_start,
                    double* lambda2, double* v_out, double* X_out, int q,
                    machip_solve_stats* stats);
+
+/* The q lowest non-trivial eigenpairs of the assembled L(x), 1 <= q <= min(16, n - 1): EVERY column obeys the stop rule
+ * ||L v - lambda v||_1 / ||L||_inf < tol with ||v||_2 = 1; the values ascend, the vectors are mutually orthonormal and orthogonal to
+ * the constant vector.  Column 0 is what machip_fiedler computes for the same start vector and tolerance (same mode choice, same
+ * bits); columns 1 .. q-1 come one after the other from a Lanczos recurrence on L restricted to the complement of the constant
+ * vector and the columns found so far (mac_amd/csrc/solver_pairs.h; fp64 whatever machip_set_precision says, no
+ * preconditioner), each from a fresh start vector, so exact multiplicities come out.  The q values are then sorted (stable).  If
+ * column 0 did not end up first, the Fiedler solve had returned a true but higher eigenpair: *reordered_out = 1 and
+ * *first_rank_out = the number of columns whose value lies below column 0's by more than tol ||L||_inf (0 otherwise) -- lambda_out[0]
+ * is the smallest value found either way.  The outputs are sorted by exact value, so among the members of a multiple lambda_2, which
+ * differ in their last bits, the Fiedler solve's vector can stand at any of their ranks with reordered = 0: output column 0 is the
+ * vector machip_fiedler returns only while reordered = 0 AND lambda_2 is simple at that resolution.  What this does NOT
+ * prove: that nothing lies below lambda_out[0] (a start vector with a negligible component along an eigenvector misses it here as
+ * in any Krylov method).
+ * X0: n x q column-major start block, or NULL: the stored start vector (machip_set_start; warm_start as in machip_fiedler) for
+ * column 0 and columns 1 .. q-1 of RandomState(7).normal(size=(q, n)).T, the reference's block (fiedler.py:27-32) continued.
+ * max_steps: per column (0: the library's defaults).  Outputs, by rank: lambda_out (q), V_out (n x q column-major), residual_out
+ * (q: the measured ||L v - lambda v||_1 / ||L||_inf), steps_out, restarts_out, status_out (q: MACHIP_OK or MACHIP_NOT_CONVERGED --
+ * a column that reached its step cap says so and carries its measured residual; if column 0 itself missed the rule the others are
+ * not attempted: NOT_CONVERGED, lambda NaN, residual +inf).  All but lambda_out may be NULL.  Returns MACHIP_OK when the columns
+ * were run (their statuses tell), MACHIP_DISCONNECTED as machip_fiedler does, MACHIP_BAD_ARG for q out of range, a start vector
+ * inside the span of the columns before it, an evaluation lane or a handle that belongs to a communicator (one GPU, one rank).
+ * Option pairs_vcap: most basis columns a deflated sequence fills before it restarts from its Ritz vector (0: the basis budget).
+ * The handle's Fiedler state (vector, gradient, warm start) is afterwards what the column-0 solve alone would have left. */
+int machip_lowest_pairs(machip_problem* p, int q, double tol, int max_steps, const double* X0, int warm_start,
+                        double* lambda_out, double* V_out, double* residual_out, int32_t* steps_out, int32_t* restarts_out,
+                        int32_t* status_out, int32_t* reordered_out, int32_t* first_rank_out);
+/* The same for an arbitrary CSR Laplacian, on the handle machip_fiedler_csr keeps. */
+int machip_lowest_pairs_csr(int device, int64_t n, const int32_t* indptr, const int32_t* indices, const double* data,
+                            int q, double tol, int max_steps, const double* X0, int warm_start,
+                            double* lambda_out, double* V_out, double* residual_out, int32_t* steps_out, int32_t* restarts_out,
+                            int32_t* status_out, int32_t* reordered_out, int32_t* first_rank_out);
+/* Device time, in ms and by rank, of the columns of the handle's last machip_lowest_pairs call (hipEvents on its stream around each
+ * column: its steps, the host's looks at the records between chunks, Ritz vectors and checks; column 0: the Fiedler solve's gpu_ms). */
+int machip_lowest_pairs_time(machip_problem* p, int q, double* ms_out);
+/* Supergradients of q given vectors (V: n x q column-major, host): G_out (m x q column-major), column c = g_k of machip_gradient
+ * for V's column c -- the same kernel, bit-exact given the vector.  Leaves the handle's own gradient alone. */
+int machip_gradient_block(machip_problem* p, int q, const double* V, double* G_out);
 
 /* Store the cold-start vector (n doubles) used by every later machip_fiedler /
  * machip_fw_step call that passes x0 = NULL and warm_start = 0: the drop-in sends the

@@ -41,6 +41,10 @@ _i32p = C.POINTER(C.c_int32)
 _f64p = C.POINTER(C.c_double)
 _lib = None
 
+# lambda, V, residual, steps, restarts, status, reordered, first_rank: the outputs machip_lowest_pairs and its CSR form share
+_PAIRS_TAIL = [_f64p, _f64p, _f64p, _i32p, _i32p, _i32p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+PAIRS_CHUNK = 16              # kPairsChunk (mac_amd/csrc/solver_pairs.h): steps of a deflated column between two looks at its records
+
 # name -> (restype, argtypes); every symbol declared in include/machip.h
 SIGNATURES = {
     "machip_version": (C.c_int, []),
@@ -56,6 +60,10 @@ SIGNATURES = {
     "machip_get_laplacian": (C.c_int, [C.c_void_p, _i32p, _i32p, _f64p]),
     "machip_fiedler": (C.c_int, [C.c_void_p, C.c_double, C.c_int, _f64p, C.c_int, _f64p, _f64p, _f64p, C.c_int,
                                  C.POINTER(SolveStats)]),
+    "machip_lowest_pairs": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_int, _f64p, C.c_int] + _PAIRS_TAIL),
+    "machip_lowest_pairs_csr": (C.c_int, [C.c_int, C.c_int64, _i32p, _i32p, _f64p, C.c_int, C.c_double, C.c_int, _f64p, C.c_int] + _PAIRS_TAIL),
+    "machip_lowest_pairs_time": (C.c_int, [C.c_void_p, C.c_int, _f64p]),
+    "machip_gradient_block": (C.c_int, [C.c_void_p, C.c_int, _f64p, _f64p]),
     "machip_set_start": (C.c_int, [C.c_void_p, _f64p]),
     "machip_gradient": (C.c_int, [C.c_void_p, _f64p]),
     "machip_lp_topk": (C.c_int, [C.c_void_p, C.c_int64, _f64p]),
@@ -324,6 +332,28 @@ class Problem:
                                       C.byref(lam), p_f64(v), p_f64(X), int(q), C.byref(self.stats))
         check(st)
         return lam.value, v, (X.T if X is not None else None)
+
+    def lowest_pairs(self, q=4, tol=1e-8, max_steps=0, X0=None, warm_start=False, raise_on_cap=False):
+        """The q lowest non-trivial eigenpairs of L(x), every one converged to the stop rule (machip_lowest_pairs):
+        ``(lams, V, info)``, V n x q; X0: n x q start block (None: the stored start vector and the reference's block)."""
+        X0 = None if X0 is None else np.asfortranarray(X0, dtype=np.float64)
+        assert X0 is None or X0.shape == (self.n, q)
+        return _pairs_call(lambda *tail: self._lib.machip_lowest_pairs(self._h, int(q), float(tol), int(max_steps), p_f64(X0),
+                                                                       int(bool(warm_start)), *tail), self.n, q, raise_on_cap)
+
+    def lowest_pairs_time(self, q):
+        """Device ms per column (by rank) of the last lowest_pairs call on this handle (machip_lowest_pairs_time)."""
+        ms = np.zeros(int(q))
+        check(self._lib.machip_lowest_pairs_time(self._h, int(q), p_f64(ms)))
+        return ms
+
+    def gradient_block(self, V):
+        """Supergradients of the columns of V (n x q): m x q, column c bit-exact given V[:, c] (machip_gradient_block)."""
+        V = np.asfortranarray(V, dtype=np.float64)
+        assert V.ndim == 2 and V.shape[0] == self.n
+        G = np.empty((self.m, V.shape[1]), order="F")
+        check(self._lib.machip_gradient_block(self._h, int(V.shape[1]), p_f64(V), p_f64(G)))
+        return G
 
     def set_start(self, x0):
         x0 = f64(x0)
@@ -834,6 +864,33 @@ def fiedler_csr(indptr, indices, data, n, tol=1e-8, max_steps=0, x0=None, q=0, d
                                  int(max_steps), p_f64(x0a), C.byref(lam), p_f64(v), p_f64(X), int(q),
                                  C.byref(stats)))
     return lam.value, v, (X.T if X is not None else None), stats
+
+
+def _pairs_call(call, n, q, raise_on_cap):
+    """Run a machip_lowest_pairs* entry point (call(*output pointers) -> status) and shape its outputs: (lams, V, info)."""
+    q = int(q)
+    nq = max(q, 1)
+    lams, V, res = np.full(nq, np.nan), np.zeros((n, nq), order="F"), np.full(nq, np.inf)
+    steps, restarts, status = (np.zeros(nq, dtype=np.int32) for _ in range(3))
+    reordered, first_rank = C.c_int32(0), C.c_int32(0)
+    check(call(p_f64(lams), p_f64(V), p_f64(res), p_i32(steps), p_i32(restarts), p_i32(status), C.byref(reordered), C.byref(first_rank)))
+    info = {"residual": res, "steps": steps, "restarts": restarts, "status": status, "reordered": int(reordered.value),
+            "first_rank": int(first_rank.value), "gap": float(lams[1] - lams[0]) if q >= 2 else None}
+    if raise_on_cap and np.any(status == NOT_CONVERGED):
+        bad = [int(c) for c in np.nonzero(status == NOT_CONVERGED)[0]]
+        raise NotConverged(NOT_CONVERGED, f"lowest_pairs: column(s) {bad} hit the step cap before the residual test passed "
+                                          f"(residuals {[float(res[c]) for c in bad]})")
+    return lams, V, info
+
+
+def lowest_pairs_csr(indptr, indices, data, n, q=4, tol=1e-8, max_steps=0, X0=None, device=0, raise_on_cap=False):
+    """machip_lowest_pairs_csr: the q lowest non-trivial eigenpairs of a CSR Laplacian -> (lams, V, info)."""
+    lib = load()
+    indptr, indices, data = i32(indptr), i32(indices), f64(data)
+    X0 = None if X0 is None else np.asfortranarray(X0, dtype=np.float64)
+    assert X0 is None or X0.shape == (n, q)
+    return _pairs_call(lambda *tail: lib.machip_lowest_pairs_csr(int(device), int(n), p_i32(indptr), p_i32(indices), p_f64(data), int(q),
+                                                                 float(tol), int(max_steps), p_f64(X0), 0, *tail), int(n), q, raise_on_cap)
 
 
 def host_tridiag_smallest(a, b):

@@ -416,9 +416,10 @@ inline int create_handle(int device, int64_t n, int64_t n_fixed, const int32_t* 
     return MACHIP_OK;
 }
 
-// machip_fiedler_csr after its argument checks
-inline int fiedler_csr(int device, int64_t n, const int32_t* indptr, const int32_t* indices, const double* data, double tol,
-                       int max_steps, const double* x0, double* lambda2, double* v_out, double* X_out, int q, machip_solve_stats* stats) {
+// The entry points that take a caller's CSR (machip_fiedler_csr, machip_lowest_pairs_csr) after their argument checks: validate the
+// matrix, wrap it in the cached CSR-only handle, run(handle).
+template <class Run>
+inline int with_csr_handle(int device, int64_t n, const int32_t* indptr, const int32_t* indices, const double* data, Run&& run) {
     // The row pointers are validated as a whole BEFORE anything is read through them (this entry point takes arbitrary
     // caller matrices): first entry 0, monotone, hence every row's range inside [0, indptr[n]) -- and all of that on the
     // host, before the first device call, so a malformed matrix is a BAD_ARG on any machine.
@@ -484,7 +485,7 @@ inline int fiedler_csr(int device, int64_t n, const int32_t* indptr, const int32
         return MACHIP_OK;
     };
     int st = body();
-    if (st == MACHIP_OK) st = machip_fiedler(p, tol, max_steps, x0, 0, lambda2, v_out, X_out, q, stats);
+    if (st == MACHIP_OK) st = run(p);
     const std::string keep = g_err;
     if (lk.owns_lock() && completed(st)) g_csr_cache = p;          // keep it for the next call
     else {
@@ -493,6 +494,92 @@ inline int fiedler_csr(int device, int64_t n, const int32_t* indptr, const int32
     }
     g_err = keep;
     return st;
+}
+
+inline int fiedler_csr(int device, int64_t n, const int32_t* indptr, const int32_t* indices, const double* data, double tol,
+                       int max_steps, const double* x0, double* lambda2, double* v_out, double* X_out, int q, machip_solve_stats* stats) {
+    return with_csr_handle(device, n, indptr, indices, data,
+                           [&](machip_problem* p) { return machip_fiedler(p, tol, max_steps, x0, 0, lambda2, v_out, X_out, q, stats); });
+}
+
+// machip_lowest_pairs after its argument checks: column 0 is run_fiedler -- the same call, the same bits
+// machip_fiedler makes of it --, columns 1 .. q-1 the deflated Lanczos driver of solver_pairs.h, then a stable sort by value.
+inline int lowest_pairs(machip_problem* p, int q, double tol, int max_steps, const double* X0, int warm_start, double* lambda_out,
+                        double* V_out, double* residual_out, int32_t* steps_out, int32_t* restarts_out, int32_t* status_out,
+                        int32_t* reordered_out, int32_t* first_rank_out) {
+    const int n = p->n;
+    Solver& S = p->sol;
+    ST_TRY(S.pairs_alloc());
+    // the start block: the caller's, or the reference's RandomState(7) block continued to q columns (column 0: the stored start vector)
+    if (q > 1) {
+        std::vector<double> blk;
+        const double* src = X0 ? X0 + (size_t)n : nullptr;
+        if (!X0) {
+            blk.resize((size_t)n * (size_t)(q - 1));
+            RefBlock rb(7u);
+            for (int i = 0; i < n; ++i) (void)rb.normal();
+            for (size_t i = 0; i < blk.size(); ++i) blk[i] = rb.normal();
+            src = blk.data();
+        }
+        HIP_TRY(hipMemcpyAsync(S.pairs->xs + (size_t)n, src, sizeof(double) * (size_t)n * (size_t)(q - 1), hipMemcpyHostToDevice, p->stream));
+        HIP_TRY(hipStreamSynchronize(p->stream));
+    }
+    std::vector<PairsCol> cols((size_t)q);
+    machip_solve_stats st0;
+    memset(&st0, 0, sizeof(st0));
+    double lam0 = 0.0;
+    const int s0 = run_fiedler(p, tol, max_steps, X0, X0 ? 0 : warm_start, &lam0, &st0);
+    if (s0 != MACHIP_OK && s0 != MACHIP_NOT_CONVERGED) return s0;      // (a disconnected graph, an error: as machip_fiedler answers)
+    cols[0].ms = st0.gpu_ms;
+    cols[0].lam = lam0; cols[0].status = s0; cols[0].steps = (int)std::min<int64_t>(st0.lanczos_steps, INT_MAX); cols[0].restarts = (int)st0.restarts;
+    cols[0].res = (st0.residual > 0.0 && std::isfinite(st0.residual)) ? st0.residual : (s0 == MACHIP_OK ? 0.0 : INFINITY);
+    // a column 0 that missed the stop rule is no eigenvector to deflate by: the others stay NOT_CONVERGED with nothing measured
+    if (s0 == MACHIP_OK && q > 1) ST_TRY(S.pairs_rest(p->csr(), p->nnz, p->lnorm, tol, max_steps, q, cols.data()));
+    std::vector<int> order((size_t)q);
+    for (int c = 0; c < q; ++c) order[(size_t)c] = c;
+    auto key = [&](int c) { return std::isfinite(cols[(size_t)c].lam) ? cols[(size_t)c].lam : INFINITY; };
+    std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return key(x) < key(y); });
+    // the rank column 0's VALUE ended at: columns below it by more than the stop rule resolves, tol ||L|| (members of a multiple
+    // eigenvalue differ in the last bits and sort in any order: that is no finding about the Fiedler solve)
+    int first_rank = 0;
+    for (int c = 1; c < q; ++c) first_rank += key(c) < key(0) - tol * p->lnorm;
+    std::vector<double> Vh;
+    if (V_out) {
+        Vh.assign((size_t)n * (size_t)q, 0.0);
+        const int have = s0 == MACHIP_OK ? q : 1;      // columns that hold a vector (column 0: yvec, put back by pairs_rest)
+        if (have == 1) HIP_TRY(hipMemcpyAsync(Vh.data(), S.yvec, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, p->stream));
+        else HIP_TRY(hipMemcpyAsync(Vh.data(), S.pairs->Q + (size_t)n, sizeof(double) * (size_t)n * (size_t)q, hipMemcpyDeviceToHost, p->stream));
+        HIP_TRY(hipStreamSynchronize(p->stream));
+    }
+    for (int r = 0; r < q; ++r) {
+        const PairsCol& k = cols[(size_t)order[(size_t)r]];
+        lambda_out[r] = k.lam;
+        if (V_out) memcpy(V_out + (size_t)r * n, Vh.data() + (size_t)order[(size_t)r] * n, sizeof(double) * (size_t)n);
+        if (residual_out) residual_out[r] = k.res;
+        if (steps_out) steps_out[r] = k.steps;
+        if (restarts_out) restarts_out[r] = k.restarts;
+        if (status_out) status_out[r] = k.status;
+        S.pairs->last_ms[r] = k.ms;
+    }
+    S.pairs->last_q = q;
+    if (reordered_out) *reordered_out = first_rank != 0;
+    if (first_rank_out) *first_rank_out = first_rank;
+    return MACHIP_OK;
+}
+
+// machip_gradient_block after its argument checks: k_grad on each column of a host block (the supergradient is bit-exact given the
+// vector), through the handle's m-vector scratch (round_nearest's: used and done with inside a call), so the handle's own gradient stays
+inline int gradient_block(machip_problem* p, int q, const double* V, double* G_out) {
+    if (!p->scratch_m) ST_TRY(dev_alloc(&p->scratch_m, (size_t)p->m + 64));
+    const int grid = (int)std::max<long>(1, std::min<long>(kMaxGrid * 4, (p->m + kBlock - 1) / kBlock));
+    for (int c = 0; c < q; ++c) {
+        HIP_TRY(hipMemcpyAsync(p->sol.w2, V + (size_t)c * p->n, sizeof(double) * (size_t)p->n, hipMemcpyHostToDevice, p->stream));
+        k_grad<false><<<grid, kBlock, 0, p->stream>>>(p->ci, p->cj, p->cw, p->sol.w2, 0, p->m, p->scratch_m);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(G_out + (size_t)c * p->m, p->scratch_m, sizeof(double) * (size_t)p->m, hipMemcpyDeviceToHost, p->stream));
+        HIP_TRY(hipStreamSynchronize(p->stream));
+    }
+    return MACHIP_OK;
 }
 
 inline void release_cache() {

@@ -169,6 +169,47 @@ int machip_fiedler_csr(int device, int64_t n, const int32_t* indptr, const int32
     return fiedler_csr(device, n, indptr, indices, data, tol, max_steps, x0, lambda2, v_out, X_out, q, stats);      // (validates the matrix on the host, then sets the device)
 }
 
+static int pairs_args(int64_t n, int q, const double* lambda_out) {
+    if (!lambda_out) return fail(MACHIP_BAD_ARG, "machip_lowest_pairs: lambda_out is NULL");
+    if (q < 1 || q > 16 || (int64_t)q > n - 1) return fail(MACHIP_BAD_ARG, "machip_lowest_pairs: q must be in [1, min(16, n - 1)]");
+    return MACHIP_OK;
+}
+
+int machip_lowest_pairs(machip_problem* p, int q, double tol, int max_steps, const double* X0, int warm_start, double* lambda_out,
+                        double* V_out, double* residual_out, int32_t* steps_out, int32_t* restarts_out, int32_t* status_out,
+                        int32_t* reordered_out, int32_t* first_rank_out) {
+    if (!p) return fail(MACHIP_BAD_ARG, "machip_lowest_pairs: NULL handle");
+    ST_TRY(pairs_args(p->n, q, lambda_out));
+    if (p->is_lane || p->comm || p->lgroup || p->ipcg || p->nranks > 1)
+        return fail(MACHIP_BAD_ARG, "machip_lowest_pairs: one GPU, one rank -- not on an evaluation lane or a handle that belongs to a communicator");
+    HIP_TRY(hipSetDevice(p->device));
+    return lowest_pairs(p, q, tol, max_steps, X0, warm_start, lambda_out, V_out, residual_out, steps_out, restarts_out, status_out, reordered_out, first_rank_out);
+}
+
+int machip_lowest_pairs_csr(int device, int64_t n, const int32_t* indptr, const int32_t* indices, const double* data, int q, double tol,
+                            int max_steps, const double* X0, int warm_start, double* lambda_out, double* V_out, double* residual_out,
+                            int32_t* steps_out, int32_t* restarts_out, int32_t* status_out, int32_t* reordered_out, int32_t* first_rank_out) {
+    if (!indptr || !indices || !data) return fail(MACHIP_BAD_ARG, "NULL argument");
+    if (n < 2 || n > 2000000000ll) return fail(MACHIP_BAD_ARG, "n must be in [2, 2e9]");
+    ST_TRY(pairs_args(n, q, lambda_out));
+    return with_csr_handle(device, n, indptr, indices, data, [&](machip_problem* p) {      // (validates the matrix on the host, then sets the device)
+        return lowest_pairs(p, q, tol, max_steps, X0, warm_start, lambda_out, V_out, residual_out, steps_out, restarts_out, status_out, reordered_out, first_rank_out);
+    });
+}
+
+int machip_lowest_pairs_time(machip_problem* p, int q, double* ms_out) {
+    if (!p || !ms_out || !p->sol.pairs || q < 1 || q > p->sol.pairs->last_q) return fail(MACHIP_BAD_ARG, "machip_lowest_pairs_time: no machip_lowest_pairs call of at least q columns on this handle");
+    for (int r = 0; r < q; ++r) ms_out[r] = p->sol.pairs->last_ms[r];
+    return MACHIP_OK;
+}
+
+int machip_gradient_block(machip_problem* p, int q, const double* V, double* G_out) {
+    if (!p || p->csr_only || q < 1 || !V || (!G_out && p->m)) return fail(MACHIP_BAD_ARG, "machip_gradient_block: bad handle, q < 1 or NULL block");
+    if (p->nranks > 1) return fail(MACHIP_BAD_ARG, "machip_gradient_block: not on a handle that belongs to a communicator");
+    HIP_TRY(hipSetDevice(p->device));
+    return gradient_block(p, q, V, G_out);
+}
+
 void machip_release_cache(void) { release_cache(); }
 
 int machip_spmv(machip_problem* p, const double* v, double* y, int variant) {

@@ -48,7 +48,10 @@ namespace machip {
        automatic, at most 128 chunks of at least 32 rows; a value that would make more than 1 024 chunks is raised to           \
        ceil(ld / 1024)); row slices of the history projection, 1..32 (unset: about one            \
        workgroup per CU) */                                                                                                        \
-    X(eig_free_rows) X(eig_free_split)
+    X(eig_free_rows) X(eig_free_split)                                                                                             \
+    /* machip_lowest_pairs (solver_pairs.h; read by every call): most basis columns a deflated column's Krylov sequence may fill     \
+       before it restarts from its Ritz vector (0 / unset: the handle's basis budget; at least 4) */                                \
+    X(pairs_vcap)
 
 enum OptId {
 #define X(n) kOpt_##n,

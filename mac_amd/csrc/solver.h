@@ -12,7 +12,7 @@
 // This file is the DRIVER's core: struct Solver with its state, allocation, the graph cache, the explicit check and solve() with the
 // mode choice.  Its other members are defined in solver_lanczos.h (the Lanczos driver: solve_lanczos in its phases),
 // solver_lob.h (the preconditioned and exact modes), solver_panel.h (host side of the column-panel step) and solver_shard.h
-// (the row-partitioned solves), all included at the end of this file; launch shapes and the dispatch onto kernel instantiations
+// (the row-partitioned solves) and solver_pairs.h (the deflated columns of machip_lowest_pairs), all included at the end of this file; launch shapes and the dispatch onto kernel instantiations
 // are in plan.h, kernels in kernels.h / panel.h / persist.h / precond.h / woodbury.h.
 #pragma once
 #include <functional>
@@ -65,6 +65,8 @@ struct IpcGroup {
     }
 };
 
+struct PairsBuf;      // work space and per-column results of machip_lowest_pairs (solver_pairs.h)
+struct PairsCol;
 struct LanRun;        // one solve_lanczos call, one Krylov sequence of it, one chunk in flight (solver_lanczos.h)
 struct LanSeq;
 struct LanPending;
@@ -255,6 +257,7 @@ struct Solver {
     }
     void destroy() {
         drop_graphs();
+        pairs_free();
         void* ptrs[] = {u, V, tri, part, Z0, Z1, st, st2, y_raw, w2, yvec, ypart, sdev,
                         part_c, part_a2, part_r, scratch3, rq_dev, start, wc, ctri, part_u, part_a, stc,
                         lx_x, lx_Lx, lx_p, lx_Lp, lx_Lw, lx_rT, lx_wT, lx_tl, lx_tdinv, lx_tcu, lx_part, lx_partR,
@@ -464,6 +467,14 @@ struct Solver {
     int lan_finish(LanRun& R, double* lambda2, machip_solve_stats* stats);
     int solve_lanczos(const CsrView& A, long nnz, double lnorm, double tol, int max_steps, int start_mode,
                       int forced_variant, double* lambda2, machip_solve_stats* stats);
+    // ---- the q lowest pairs: deflated columns after the Fiedler solve (solver_pairs.h) ----
+    PairsBuf* pairs = nullptr;      // allocated by the first machip_lowest_pairs call on the handle
+    int pairs_alloc();
+    void pairs_free();
+    int pairs_fin_grid() const;
+    void pairs_project(double* x, int nq, int slot);
+    int pairs_column(const CsrView& A, long nnz, double lnorm, double tol, int max_steps, int c, int cap, PairsCol* out);
+    int pairs_rest(const CsrView& A, long nnz, double lnorm, double tol, int max_steps, int q, PairsCol* cols);
     // ---- preconditioned and exact modes (solver_lob.h) ----
     int lob_alloc(long nnz);
     int lob_c() const;
@@ -694,3 +705,4 @@ struct Solver {
 #include "solver_shard.h"
 #include "solver_lob.h"
 #include "solver_lanczos.h"
+#include "solver_pairs.h"

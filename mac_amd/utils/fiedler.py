@@ -72,3 +72,34 @@ def find_fiedler_pair(L, X=None, method="hip", tol=1e-8, seed=None):
                                       x0=np.ascontiguousarray(X[:, 0]), q=q)
     Xo = np.asfortranarray(Xo)
     return lam, Xo[:, 0], Xo
+
+
+def reference_start_block_q(n, q, seed=None):
+    """RandomState(7).normal(size=(q, n)).T: the reference's start block continued to q columns (its first four columns
+    are the same for every q; what machip_lowest_pairs generates itself when it is given no block)."""
+    if seed is None:
+        seed = np.random.RandomState(7)
+    return np.asarray(seed.normal(size=(q, n))).T
+
+
+def find_lowest_pairs(L, q=4, X=None, tol=1e-8, seed=None, max_steps=0, raise_on_cap=False):
+    """The ``q`` lowest non-trivial eigenpairs of the graph Laplacian ``L`` (any scipy sparse matrix), 1 <= q <= min(16, n-1),
+    EVERY ONE converged to the reference's stop rule ||L v - lambda v||_1 / ||L||_inf < tol (machip_lowest_pairs_csr,
+    DESIGN section 24).  Returns ``(lams, V, info)``: ``lams`` ascending, ``V`` n x q with orthonormal columns orthogonal to 1.
+    Column 0 of the iteration is what ``find_fiedler_pair`` returns for the same start vector -- and V[:, 0] is that vector while
+    ``info["reordered"] == 0`` and lambda_2 is simple: the outputs are sorted by exact value, and the members of a multiple
+    eigenvalue, equal to the last bits only, sort in any order.  The others come from a deflated Lanczos
+    iteration, each from its own column of the start block ``X`` (n x q; default: the reference's RandomState(7) block
+    continued to q columns), so an eigenvalue of multiplicity k fills k columns.
+
+    ``info``: ``residual`` (measured, per column), ``steps``, ``restarts``, ``status`` (0 = converged, 1 = the column hit
+    ``max_steps``: never passed off as converged; raised as ``NotConverged`` only with ``raise_on_cap=True``), ``reordered``
+    / ``first_rank`` (1 / the number of columns below column 0's value by more than tol ||L||_inf, if the Fiedler solve had
+    returned a higher eigenpair than one found after it), ``gap`` = lams[1] - lams[0] for q >= 2.  Not proven: that nothing lies below lams[0]."""
+    L = csr_matrix(L, dtype=np.float64)
+    n = L.shape[0]
+    if X is None:
+        X = reference_start_block_q(n, q, seed)
+    assert X.shape == (n, q)
+    L.sum_duplicates()
+    return _lib.lowest_pairs_csr(L.indptr, L.indices, L.data, n, q=q, tol=tol, max_steps=max_steps, X0=X, raise_on_cap=raise_on_cap)
