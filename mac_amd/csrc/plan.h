@@ -4,8 +4,8 @@
 //   plan_spmv   shape of the stand-alone SpMV kernels (explicit residual check, preconditioned mode)
 //   plan_pipe   shape of the one-kernel Lanczos step (lanes per row, load chains, workgroup size, deferred barrier)
 //   plan_panel  whether the column-panel form runs, and its panels / row blocks (panel.h)
-//   launch_*    the switch from a plan to a template instantiation; launch_pipe_shard: one rank's share of a
-//               row-partitioned step (ShardGroup below)
+//   with_* / launch_*   second half: ONE shape table per kernel family (the switch from plan values to a template instantiation),
+//               which every launch site here and in solver_panel.h / solver_shard.h / solver_pairs.h / solver_lob.h goes through
 //
 // Every number here was measured on MI355X (tools/ubench*.hip, tools/sweep_pipe.py, tools/sweep_panel.py); the comments say
 // which.  Shapes can be overridden through the handle's option table (options.h, machip_set_option; OPT(name, default) below):
@@ -15,7 +15,7 @@
 #pragma once
 #include <algorithm>
 #include <cstdlib>
-#include <vector>
+#include <type_traits>
 
 #include "kernels.h"
 #include "options.h"
@@ -144,6 +144,11 @@ struct PanPlan {
     bool u = false;                  // shifted recurrence with an 8-byte operand (panel_u.h: k_pan_mul8<LPT, TWT> + k_pan_finu); C is even then
     int LPT = 1, TWT = 8;            // ... 16-byte operand loads per thread, tiles per worker wave the instantiation holds (3 | 5 | 8)
 };
+// The instantiations of k_pan_mul8 (the dispatch below is built from this): tiles per worker wave 3 | 5 | 8, operand loads per thread
+// 1 .. 8, 9 next to the smallest row-block image only; a panel of C columns runs on one when the shape's LDS share holds it
+constexpr int pan_twt(int tww) { return tww <= 3 ? 3 : tww <= 5 ? 5 : 8; }
+constexpr bool pan_u_shape(int lpt, int twt) { return lpt >= 1 && (twt == 3 ? lpt <= 9 : (twt == 5 || twt == 8) && lpt <= 8); }
+constexpr bool pan_u_holds(int lpt, int twt, int C) { return pan_u_shape(lpt, twt) && C <= pan_u_cols(lpt, twt); }
 constexpr int kPanUCmax = pan_u_cols(9, 3);      // widest panel any k_pan_mul8 instantiation holds (17 568 columns)
 // nnz_cap: the most entries the handle's L(x) can ever hold (decides the band form once per handle); shape_only: the shape the
 // automatic mode WOULD take for this n, whatever nnz is (the assembly writes the per-row tables before nnz is known, kernels.h PanSpec)
@@ -188,10 +193,8 @@ inline PanPlan plan_panel(const Options& opt, int n, long nnz, int maxlen, bool 
             const int b = std::max(1, std::min(grid_cap(opt) / c, groups));
             const int nt = (groups + b - 1) / b;
             if (nt > tmax) break;                    // (narrower panels leave fewer row blocks: no single-wave shape)
-            const int tww = (nt + kPanWork - 1) / kPanWork, twt = tww <= 3 ? 3 : tww <= 5 ? 5 : 8;
             const int lpt = ((Cc + 1) / 2 + kPanWorkThreads - 1) / kPanWorkThreads;
-            const int cap = twt == 3 ? pan_u_cols(lpt <= 9 ? lpt : 9, 3) : twt == 5 ? pan_u_cols(lpt <= 8 ? lpt : 8, 5) : pan_u_cols(lpt <= 8 ? lpt : 8, 8);
-            if (lpt <= (twt == 3 ? 9 : 8) && Cc <= cap) { np = c; nb = b; }
+            if (pan_u_holds(lpt, pan_twt((nt + kPanWork - 1) / kPanWork), Cc)) { np = c; nb = b; }
         }
         if (!np) return plan_panel(opt, n, nnz, maxlen, allowed, nnz_cap, shape_only, false);      // (the record form's shape rules, multi-cell shapes included)
     } else if (np_env > 0 || nb_env > 0) {              // explicit shape (tests, sweeps): taken as given, clipped to what the kernels hold
@@ -240,9 +243,8 @@ inline PanPlan plan_panel(const Options& opt, int n, long nnz, int maxlen, bool 
     pp.RPT = (C + kPanWorkThreads - 1) / kPanWorkThreads;
     if (want_u) {
         pp.LPT = ((C + 1) / 2 + kPanWorkThreads - 1) / kPanWorkThreads;      // (16-byte loads per worker thread)
-        pp.TWT = pp.TWW <= 3 ? 3 : pp.TWW <= 5 ? 5 : 8;
-        pp.u = pp.cells == 1 && pp.LPT <= 9 && (pp.LPT < 9 || pp.TWT == 3) &&
-               C <= (pp.TWT == 3 ? pan_u_cols(pp.LPT, 3) : pp.TWT == 5 ? pan_u_cols(pp.LPT, 5) : pan_u_cols(pp.LPT, 8));
+        pp.TWT = pan_twt(pp.TWW);
+        pp.u = pp.cells == 1 && pan_u_holds(pp.LPT, pp.TWT, C);
         if (!pp.u) return plan_panel(opt, n, nnz, maxlen, allowed, nnz_cap, shape_only, false);      // the record form's shape rules
     }
     pp.band = OPT(panel_band, 1) != 0 && (nnz_cap >= 0 ? nnz_cap : nnz) < (1l << 28);     // (CSR positions are packed with 3 count bits)
@@ -252,172 +254,147 @@ inline PanPlan plan_panel(const Options& opt, int n, long nnz, int maxlen, bool 
     return pp;
 }
 
+// ---- dispatch: one shape table per kernel family ------------------------------------------------
+// with_<family>(plan values, f) holds the ONE switch of a family and calls the generic lambda f with the template arguments of the
+// instantiation as std::integral_constant parameters (SV(x) reads one back inside the lambda).  A launch site supplies what differs
+// there -- grid, stream, arguments, the flags SH / TV / ELLW -- and nothing else; a table lists exactly the shapes that exist.
+template <int V> using Ic = std::integral_constant<int, V>;
+#define SV(x) decltype(x)::value
+
+// v in [LO, HI) -> f(v), anything else -> f(HI): records per thread of k_pan_mul / k_pan_mul_multi, LOBPCG chunk lengths (and the
+// one-site k_pan_build rows per thread)
+template <int LO, int HI, class F>
+inline void with_int(int v, F&& f) {
+    if constexpr (LO < HI) { if (v == LO) f(Ic<LO>{}); else with_int<LO + 1, HI>(v, f); }
+    else f(Ic<HI>{});
+}
+template <class F> inline void with_pan_rpt(int rpt, F&& f) { with_int<1, 13>(rpt, f); }
+template <class F> inline void with_lob_chunk(int c, F&& f) { with_int<1, 16>(c, f); }   // (instantiated per chunk length: no guards, everything in registers)
+
+// threads per workgroup: k_pipe_vec in every form, k_pan_fin, k_pan_finu
+template <class F>
+inline void with_block(int block, F&& f) {
+    if (block == 1024) f(Ic<1024>{}); else if (block == 512) f(Ic<512>{}); else f(Ic<256>{});
+}
+// lanes per row of the stand-alone products (k_spmv_*, k_pairs_mul, k_pipe_stream)
+template <class F>
+inline void with_stream_width(int w, F&& f) {
+    switch (w) {
+        case 1: return f(Ic<1>{});
+        case 2: return f(Ic<2>{});
+        case 4: return f(Ic<4>{});
+        case 8: return f(Ic<8>{});
+        default: return f(Ic<16>{});
+    }
+}
+template <class F>
+inline void with_vec_width(int w, F&& f) {
+    switch (w) {
+        case 2: return f(Ic<2>{});
+        case 4: return f(Ic<4>{});
+        case 8: return f(Ic<8>{});
+        case 16: return f(Ic<16>{});
+        case 32: return f(Ic<32>{});
+        default: return f(Ic<64>{});
+    }
+}
+// k_pipe_vec, fp64: f(G, UNR, DEFER).  The deferred-barrier build is a different piece of generated code (its last bits differ
+// from the plain one's at config 4) and exists for the shapes plan_pipe picks with several row tiles per workgroup; every other
+// shape runs DEFER = 1, unlisted ones as <64, 2>.  The plain launch, the sharded launch and pipe_gpb all read THIS list.
+template <class F>
+inline void with_pipe_shape(const SpmvPlan& pl, F&& f) {
+    const int key = pl.width * 10 + pl.unroll;
+    if (pl.defer >= 3) switch (key) {
+        case 41: return f(Ic<4>{}, Ic<1>{}, Ic<3>{});
+        case 42: return f(Ic<4>{}, Ic<2>{}, Ic<3>{});
+        case 82: return f(Ic<8>{}, Ic<2>{}, Ic<3>{});
+        case 84: return f(Ic<8>{}, Ic<4>{}, Ic<3>{});
+        case 162: return f(Ic<16>{}, Ic<2>{}, Ic<3>{});
+        default: break;
+    }
+    switch (key) {
+        case 41: return f(Ic<4>{}, Ic<1>{}, Ic<1>{});
+        case 42: return f(Ic<4>{}, Ic<2>{}, Ic<1>{});
+        case 44: return f(Ic<4>{}, Ic<4>{}, Ic<1>{});
+        case 81: return f(Ic<8>{}, Ic<1>{}, Ic<1>{});
+        case 82: return f(Ic<8>{}, Ic<2>{}, Ic<1>{});
+        case 84: return f(Ic<8>{}, Ic<4>{}, Ic<1>{});
+        case 161: return f(Ic<16>{}, Ic<1>{}, Ic<1>{});
+        case 162: return f(Ic<16>{}, Ic<2>{}, Ic<1>{});
+        case 164: return f(Ic<16>{}, Ic<4>{}, Ic<1>{});
+        case 321: return f(Ic<32>{}, Ic<1>{}, Ic<1>{});
+        case 322: return f(Ic<32>{}, Ic<2>{}, Ic<1>{});
+        case 641: return f(Ic<64>{}, Ic<1>{}, Ic<1>{});
+        default: return f(Ic<64>{}, Ic<2>{}, Ic<1>{});
+    }
+}
+// fp32 storage (mixed-precision mode): the shapes plan_pipe actually chooses; anything else maps to the nearest
+template <class F>
+inline void with_pipe32_shape(const SpmvPlan& pl, F&& f) {
+    switch (pl.width * 10 + pl.unroll) {
+        case 41: return f(Ic<4>{}, Ic<1>{});
+        case 42: case 44: return f(Ic<4>{}, Ic<2>{});
+        case 81: case 82: return f(Ic<8>{}, Ic<2>{});
+        case 84: return f(Ic<8>{}, Ic<4>{});
+        default: return f(Ic<16>{}, Ic<2>{});
+    }
+}
+// k_pan_mul8<LPT, TWT>: every shape pan_u_shape() names, nothing for any other (plan_panel only hands out instantiated shapes)
+template <int LP = 1, class F>
+inline void with_pan_mul8_shape(int lpt, int twt, F&& f) {
+    if constexpr (LP <= 9) {
+        if (lpt != LP) return with_pan_mul8_shape<LP + 1>(lpt, twt, f);
+        if constexpr (pan_u_shape(LP, 3)) if (twt == 3) return f(Ic<LP>{}, Ic<3>{});
+        if constexpr (pan_u_shape(LP, 5)) if (twt == 5) return f(Ic<LP>{}, Ic<5>{});
+        if constexpr (pan_u_shape(LP, 8)) if (twt == 8) return f(Ic<LP>{}, Ic<8>{});
+    }
+}
+// k_pan_finu<BLOCK, NPM>: NPM = the partial products one thread sums, the next instantiated count from NP up
+inline int pan_npm(int NP) { return NP <= 6 ? 6 : NP <= 8 ? 8 : NP <= 12 ? 12 : 16; }
+template <class F>
+inline void with_finu_shape(const PanPlan& pn, F&& f) {
+    with_block(pn.block2, [&](auto B) {
+        switch (pan_npm(pn.NP)) {
+            case 6: return f(B, Ic<6>{});
+            case 8: return f(B, Ic<8>{});
+            case 12: return f(B, Ic<12>{});
+            default: return f(B, Ic<16>{});
+        }
+    });
+}
+
 template <class Op>
 inline void launch_spmv(const SpmvPlan& pl, hipStream_t s, const CsrView& A, const double* x, const Op& op) {
-    if (pl.variant == kStream) {
-        switch (pl.width) {
-            case 1: k_spmv_stream<1, Op><<<pl.grid, kBlock, 0, s>>>(A, x, op); break;
-            case 2: k_spmv_stream<2, Op><<<pl.grid, kBlock, 0, s>>>(A, x, op); break;
-            case 4: k_spmv_stream<4, Op><<<pl.grid, kBlock, 0, s>>>(A, x, op); break;
-            case 8: k_spmv_stream<8, Op><<<pl.grid, kBlock, 0, s>>>(A, x, op); break;
-            default: k_spmv_stream<16, Op><<<pl.grid, kBlock, 0, s>>>(A, x, op); break;
-        }
-    } else {
-        switch (pl.width) {
-            case 2: k_spmv_vec<2, Op><<<pl.grid, kBlock, 0, s>>>(A, x, op); break;
-            case 4: k_spmv_vec<4, Op><<<pl.grid, kBlock, 0, s>>>(A, x, op); break;
-            case 8: k_spmv_vec<8, Op><<<pl.grid, kBlock, 0, s>>>(A, x, op); break;
-            case 16: k_spmv_vec<16, Op><<<pl.grid, kBlock, 0, s>>>(A, x, op); break;
-            case 32: k_spmv_vec<32, Op><<<pl.grid, kBlock, 0, s>>>(A, x, op); break;
-            default: k_spmv_vec<64, Op><<<pl.grid, kBlock, 0, s>>>(A, x, op); break;
-        }
-    }
+    if (pl.variant == kStream) with_stream_width(pl.width, [&](auto W) { k_spmv_stream<SV(W), Op><<<pl.grid, kBlock, 0, s>>>(A, x, op); });
+    else with_vec_width(pl.width, [&](auto W) { k_spmv_vec<SV(W), Op><<<pl.grid, kBlock, 0, s>>>(A, x, op); });
 }
 
-// fp32 storage (mixed-precision mode): the shapes plan_pipe actually chooses; anything else maps to the nearest
-template <int BLOCK>
-inline void launch_pipe_b(const SpmvPlan& pl, hipStream_t s, const CsrViewT<float>& A, const PipeViewT<float>& L, int jrel) {
-    const int key = pl.width * 10 + pl.unroll;
-    switch (key) {
-        case 41: k_pipe_vec<BLOCK, 4, 1, true, float, 1><<<pl.grid, BLOCK, 0, s>>>(PIPE_ARGS(A, L, jrel)); break;
-        case 42: case 44: k_pipe_vec<BLOCK, 4, 2, true, float, 1><<<pl.grid, BLOCK, 0, s>>>(PIPE_ARGS(A, L, jrel)); break;
-        case 81: case 82: k_pipe_vec<BLOCK, 8, 2, true, float, 1><<<pl.grid, BLOCK, 0, s>>>(PIPE_ARGS(A, L, jrel)); break;
-        case 84: k_pipe_vec<BLOCK, 8, 4, true, float, 1><<<pl.grid, BLOCK, 0, s>>>(PIPE_ARGS(A, L, jrel)); break;
-        default: k_pipe_vec<BLOCK, 16, 2, true, float, 1><<<pl.grid, BLOCK, 0, s>>>(PIPE_ARGS(A, L, jrel)); break;
-    }
+// One Lanczos step.  kEll is the padded fixed-width form: 4 lanes per row, all of a row's W = 8 / 16 slots in flight at once, one
+// row tile per workgroup (A.col / A.val are the padded arrays, A.rowptr is not read).
+inline void launch_pipe(const SpmvPlan& pl, hipStream_t s, const CsrView& A, const PipeView& L, int jrel) {
+    if (pl.variant == kStream) return with_stream_width(pl.width, [&](auto W) { k_pipe_stream<SV(W)><<<pl.grid, kBlock, 0, s>>>(A, L, jrel); });
+    with_block(pl.block, [&](auto B) {
+        if (pl.variant != kEll) with_pipe_shape(pl, [&](auto G, auto U, auto D) { k_pipe_vec<SV(B), SV(G), SV(U), true, double, SV(D)><<<pl.grid, SV(B), 0, s>>>(PIPE_ARGS(A, L, jrel)); });
+        else if (pl.unroll == 2) k_pipe_vec<SV(B), 4, 2, true, double, 1, false, 8><<<pl.grid, SV(B), 0, s>>>(PIPE_ARGS(A, L, jrel));
+        else k_pipe_vec<SV(B), 4, 4, true, double, 1, false, 16><<<pl.grid, SV(B), 0, s>>>(PIPE_ARGS(A, L, jrel));
+    });
 }
-
-template <int BLOCK>
-inline void launch_pipe_b(const SpmvPlan& pl, hipStream_t s, const CsrView& A, const PipeView& L, int jrel) {
-    const int key = pl.width * 10 + pl.unroll;
-    if (pl.defer >= 3) {   // several row tiles per workgroup: the shapes plan_pipe picks there (others: DEFER = 1 below)
-        switch (key) {
-            case 41: k_pipe_vec<BLOCK, 4, 1, true, double, 3><<<pl.grid, BLOCK, 0, s>>>(PIPE_ARGS(A, L, jrel)); return;
-            case 42: k_pipe_vec<BLOCK, 4, 2, true, double, 3><<<pl.grid, BLOCK, 0, s>>>(PIPE_ARGS(A, L, jrel)); return;
-            case 82: k_pipe_vec<BLOCK, 8, 2, true, double, 3><<<pl.grid, BLOCK, 0, s>>>(PIPE_ARGS(A, L, jrel)); return;
-            case 84: k_pipe_vec<BLOCK, 8, 4, true, double, 3><<<pl.grid, BLOCK, 0, s>>>(PIPE_ARGS(A, L, jrel)); return;
-            case 162: k_pipe_vec<BLOCK, 16, 2, true, double, 3><<<pl.grid, BLOCK, 0, s>>>(PIPE_ARGS(A, L, jrel)); return;
-            default: break;
-        }
-    }
-    switch (key) {
-        case 41: k_pipe_vec<BLOCK, 4, 1, true, double, 1><<<pl.grid, BLOCK, 0, s>>>(PIPE_ARGS(A, L, jrel)); break;
-        case 42: k_pipe_vec<BLOCK, 4, 2, true, double, 1><<<pl.grid, BLOCK, 0, s>>>(PIPE_ARGS(A, L, jrel)); break;
-        case 44: k_pipe_vec<BLOCK, 4, 4, true, double, 1><<<pl.grid, BLOCK, 0, s>>>(PIPE_ARGS(A, L, jrel)); break;
-        case 84: k_pipe_vec<BLOCK, 8, 4, true, double, 1><<<pl.grid, BLOCK, 0, s>>>(PIPE_ARGS(A, L, jrel)); break;
-        case 164: k_pipe_vec<BLOCK, 16, 4, true, double, 1><<<pl.grid, BLOCK, 0, s>>>(PIPE_ARGS(A, L, jrel)); break;
-        case 81: k_pipe_vec<BLOCK, 8, 1, true, double, 1><<<pl.grid, BLOCK, 0, s>>>(PIPE_ARGS(A, L, jrel)); break;
-        case 82: k_pipe_vec<BLOCK, 8, 2, true, double, 1><<<pl.grid, BLOCK, 0, s>>>(PIPE_ARGS(A, L, jrel)); break;
-        case 161: k_pipe_vec<BLOCK, 16, 1, true, double, 1><<<pl.grid, BLOCK, 0, s>>>(PIPE_ARGS(A, L, jrel)); break;
-        case 162: k_pipe_vec<BLOCK, 16, 2, true, double, 1><<<pl.grid, BLOCK, 0, s>>>(PIPE_ARGS(A, L, jrel)); break;
-        case 321: k_pipe_vec<BLOCK, 32, 1, true, double, 1><<<pl.grid, BLOCK, 0, s>>>(PIPE_ARGS(A, L, jrel)); break;
-        case 322: k_pipe_vec<BLOCK, 32, 2, true, double, 1><<<pl.grid, BLOCK, 0, s>>>(PIPE_ARGS(A, L, jrel)); break;
-        case 641: k_pipe_vec<BLOCK, 64, 1, true, double, 1><<<pl.grid, BLOCK, 0, s>>>(PIPE_ARGS(A, L, jrel)); break;
-        default: k_pipe_vec<BLOCK, 64, 2, true, double, 1><<<pl.grid, BLOCK, 0, s>>>(PIPE_ARGS(A, L, jrel)); break;
-    }
+inline void launch_pipe(const SpmvPlan& pl, hipStream_t s, const CsrViewT<float>& A, const PipeViewT<float>& L, int jrel) {      // (the LDS row-tile variant exists in fp64 only)
+    with_block(pl.block, [&](auto B) {
+        with_pipe32_shape(pl, [&](auto G, auto U) { k_pipe_vec<SV(B), SV(G), SV(U), true, float, 1><<<pl.grid, SV(B), 0, s>>>(PIPE_ARGS(A, L, jrel)); });
+    });
 }
-
-// One rank's share of a row-partitioned step: workgroups [PS.first, PS.first + grid) of the pl.grid-workgroup launch.
-// The SAME instantiation the unsharded switch picks (DEFER included: the deferred-barrier build is a different piece of
-// generated code, and its last bits differ from the plain one's at config 4).
-template <int BLOCK>
-inline void launch_pipe_shard_b(const SpmvPlan& pl, hipStream_t s, const CsrView& A, const PipeView& L, int jrel, const PeerSet& PS, int grid) {
-    const int key = pl.width * 10 + pl.unroll;
-    if (pl.defer >= 3) {
-        switch (key) {
-            case 41: k_pipe_vec<BLOCK, 4, 1, true, double, 3, true><<<grid, BLOCK, 0, s>>>(PIPE_ARGS(A, L, jrel), PS); return;
-            case 42: k_pipe_vec<BLOCK, 4, 2, true, double, 3, true><<<grid, BLOCK, 0, s>>>(PIPE_ARGS(A, L, jrel), PS); return;
-            case 82: k_pipe_vec<BLOCK, 8, 2, true, double, 3, true><<<grid, BLOCK, 0, s>>>(PIPE_ARGS(A, L, jrel), PS); return;
-            case 84: k_pipe_vec<BLOCK, 8, 4, true, double, 3, true><<<grid, BLOCK, 0, s>>>(PIPE_ARGS(A, L, jrel), PS); return;
-            case 162: k_pipe_vec<BLOCK, 16, 2, true, double, 3, true><<<grid, BLOCK, 0, s>>>(PIPE_ARGS(A, L, jrel), PS); return;
-            default: break;
-        }
-    }
-    switch (key) {
-        case 41: k_pipe_vec<BLOCK, 4, 1, true, double, 1, true><<<grid, BLOCK, 0, s>>>(PIPE_ARGS(A, L, jrel), PS); break;
-        case 42: k_pipe_vec<BLOCK, 4, 2, true, double, 1, true><<<grid, BLOCK, 0, s>>>(PIPE_ARGS(A, L, jrel), PS); break;
-        case 44: k_pipe_vec<BLOCK, 4, 4, true, double, 1, true><<<grid, BLOCK, 0, s>>>(PIPE_ARGS(A, L, jrel), PS); break;
-        case 81: k_pipe_vec<BLOCK, 8, 1, true, double, 1, true><<<grid, BLOCK, 0, s>>>(PIPE_ARGS(A, L, jrel), PS); break;
-        case 82: k_pipe_vec<BLOCK, 8, 2, true, double, 1, true><<<grid, BLOCK, 0, s>>>(PIPE_ARGS(A, L, jrel), PS); break;
-        case 84: k_pipe_vec<BLOCK, 8, 4, true, double, 1, true><<<grid, BLOCK, 0, s>>>(PIPE_ARGS(A, L, jrel), PS); break;
-        case 161: k_pipe_vec<BLOCK, 16, 1, true, double, 1, true><<<grid, BLOCK, 0, s>>>(PIPE_ARGS(A, L, jrel), PS); break;
-        case 162: k_pipe_vec<BLOCK, 16, 2, true, double, 1, true><<<grid, BLOCK, 0, s>>>(PIPE_ARGS(A, L, jrel), PS); break;
-        case 164: k_pipe_vec<BLOCK, 16, 4, true, double, 1, true><<<grid, BLOCK, 0, s>>>(PIPE_ARGS(A, L, jrel), PS); break;
-        case 321: k_pipe_vec<BLOCK, 32, 1, true, double, 1, true><<<grid, BLOCK, 0, s>>>(PIPE_ARGS(A, L, jrel), PS); break;
-        case 322: k_pipe_vec<BLOCK, 32, 2, true, double, 1, true><<<grid, BLOCK, 0, s>>>(PIPE_ARGS(A, L, jrel), PS); break;
-        case 641: k_pipe_vec<BLOCK, 64, 1, true, double, 1, true><<<grid, BLOCK, 0, s>>>(PIPE_ARGS(A, L, jrel), PS); break;
-        default: k_pipe_vec<BLOCK, 64, 2, true, double, 1, true><<<grid, BLOCK, 0, s>>>(PIPE_ARGS(A, L, jrel), PS); break;
-    }
+// One rank's share of a row-partitioned step: workgroups [PS.first, PS.first + grid) of the pl.grid-workgroup launch
+inline void launch_pipe_shard(const SpmvPlan& pl, hipStream_t s, const CsrView& A, const PipeView& L, int jrel, const PeerSet& PS, int grid) {
+    with_block(pl.block, [&](auto B) {
+        with_pipe_shape(pl, [&](auto G, auto U, auto D) { k_pipe_vec<SV(B), SV(G), SV(U), true, double, SV(D), true><<<grid, SV(B), 0, s>>>(PIPE_ARGS(A, L, jrel), PS); });
+    });
 }
-// rows per workgroup tile of the instantiation the switches above pick (unlisted shapes run as G = 64)
+// rows per workgroup tile of the instantiation the launches above run
 inline int pipe_gpb(const SpmvPlan& pl) {
     int g = 64;
-    switch (pl.width * 10 + pl.unroll) {
-        case 41: case 42: case 44: g = 4; break;
-        case 81: case 82: case 84: g = 8; break;
-        case 161: case 162: case 164: g = 16; break;
-        case 321: case 322: g = 32; break;
-        default: g = 64; break;
-    }
+    with_pipe_shape(pl, [&](auto G, auto, auto) { g = SV(G); });
     return (pl.block - 64) / g;
-}
-
-// Row-partitioned eigen-solve of an in-process communicator (machip_comm_init_local): the LEADER's
-// solver (rank 0) drives every rank's stream -- per Lanczos step one launch per rank (that rank's share of the step's
-// workgroups, on that rank's copy of matrix and operand, writing next records and partial sums into every copy),
-// ordered by events: step s of rank r waits for step s - 1 of every rank.  Everything else of the solve (host analysis
-// of the tridiagonal, explicit residual check, restarts) runs on the leader alone; the converged vector is copied to
-// the peers.  The basis V is sharded by rows: each rank keeps the rows its workgroups produced and forms its part of
-// the Ritz vector.
-struct ShardRank {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    Z2 *Z0 = nullptr, *Z1 = nullptr;
-    double *part = nullptr, *V = nullptr, *ypart = nullptr, *sdev = nullptr, *yvec = nullptr;
-    CsrView A{};                 // this rank's own assembled copy of L(x)
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    int g0 = 0, g1 = 0;          // workgroups [g0, g1) of a step (set per solve from the plan)
-};
-struct ShardGroup {
-    std::vector<ShardRank> rk;   // rk[0] = the leader
-    hipEvent_t fork = nullptr;
-    bool same_device = true;
-};
-inline void launch_pipe_shard(const SpmvPlan& pl, hipStream_t s, const CsrView& A, const PipeView& L, int jrel, const PeerSet& PS, int grid) {
-    if (pl.block == 1024) launch_pipe_shard_b<1024>(pl, s, A, L, jrel, PS, grid);
-    else if (pl.block == 512) launch_pipe_shard_b<512>(pl, s, A, L, jrel, PS, grid);
-    else launch_pipe_shard_b<256>(pl, s, A, L, jrel, PS, grid);
-}
-
-// Padded fixed-width form (kEll): 4 lanes per row, all of a row's W = 8 / 16 slots in flight at once, one row tile per
-// workgroup (A.col / A.val are the padded arrays, A.rowptr is not read).
-template <int BLOCK>
-inline void launch_pipe_ell_b(const SpmvPlan& pl, hipStream_t s, const CsrView& A, const PipeView& L, int jrel) {
-    if (pl.unroll == 2) k_pipe_vec<BLOCK, 4, 2, true, double, 1, false, 8><<<pl.grid, BLOCK, 0, s>>>(PIPE_ARGS(A, L, jrel));
-    else k_pipe_vec<BLOCK, 4, 4, true, double, 1, false, 16><<<pl.grid, BLOCK, 0, s>>>(PIPE_ARGS(A, L, jrel));
-}
-
-inline void launch_pipe(const SpmvPlan& pl, hipStream_t s, const CsrView& A, const PipeView& L, int jrel) {
-    if (pl.variant == kEll) {
-        if (pl.block == 1024) launch_pipe_ell_b<1024>(pl, s, A, L, jrel);
-        else if (pl.block == 512) launch_pipe_ell_b<512>(pl, s, A, L, jrel);
-        else launch_pipe_ell_b<256>(pl, s, A, L, jrel);
-    } else if (pl.variant == kStream) {
-        switch (pl.width) {
-            case 1: k_pipe_stream<1><<<pl.grid, kBlock, 0, s>>>(A, L, jrel); break;
-            case 2: k_pipe_stream<2><<<pl.grid, kBlock, 0, s>>>(A, L, jrel); break;
-            case 4: k_pipe_stream<4><<<pl.grid, kBlock, 0, s>>>(A, L, jrel); break;
-            case 8: k_pipe_stream<8><<<pl.grid, kBlock, 0, s>>>(A, L, jrel); break;
-            default: k_pipe_stream<16><<<pl.grid, kBlock, 0, s>>>(A, L, jrel); break;
-        }
-    } else if (pl.block == 1024) launch_pipe_b<1024>(pl, s, A, L, jrel);
-    else if (pl.block == 512) launch_pipe_b<512>(pl, s, A, L, jrel);
-    else launch_pipe_b<256>(pl, s, A, L, jrel);
-}
-inline void launch_pipe(const SpmvPlan& pl, hipStream_t s, const CsrViewT<float>& A, const PipeViewT<float>& L, int jrel) {
-    if (pl.block == 1024) launch_pipe_b<1024>(pl, s, A, L, jrel);      // (the LDS row-tile variant exists in fp64 only)
-    else if (pl.block == 512) launch_pipe_b<512>(pl, s, A, L, jrel);
-    else launch_pipe_b<256>(pl, s, A, L, jrel);
 }
 
 }  // namespace machip

@@ -65,6 +65,28 @@ struct IpcGroup {
     }
 };
 
+// Row-partitioned eigen-solve of an in-process communicator (machip_comm_init_local): the LEADER's
+// solver (rank 0) drives every rank's stream -- per Lanczos step one launch per rank (that rank's share of the step's
+// workgroups, on that rank's copy of matrix and operand, writing next records and partial sums into every copy),
+// ordered by events: step s of rank r waits for step s - 1 of every rank.  Everything else of the solve (host analysis
+// of the tridiagonal, explicit residual check, restarts) runs on the leader alone; the converged vector is copied to
+// the peers.  The basis V is sharded by rows: each rank keeps the rows its workgroups produced and forms its part of
+// the Ritz vector.
+struct ShardRank {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    Z2 *Z0 = nullptr, *Z1 = nullptr;
+    double *part = nullptr, *V = nullptr, *ypart = nullptr, *sdev = nullptr, *yvec = nullptr;
+    CsrView A{};                 // this rank's own assembled copy of L(x)
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    int g0 = 0, g1 = 0;          // workgroups [g0, g1) of a step (set per solve from the plan)
+};
+struct ShardGroup {
+    std::vector<ShardRank> rk;   // rk[0] = the leader
+    hipEvent_t fork = nullptr;
+    bool same_device = true;
+};
+
 struct PairsBuf;      // work space and per-column results of machip_lowest_pairs (solver_pairs.h)
 struct PairsCol;
 struct LanRun;        // one solve_lanczos call, one Krylov sequence of it, one chunk in flight (solver_lanczos.h)

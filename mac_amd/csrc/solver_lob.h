@@ -102,14 +102,7 @@ inline void Solver::lob_launch_chunk(const CsrView& AT, const SpmvPlan& pl, cons
         k_lob_tail<<<1, 64, 0, stream>>>(L, steps);
         return;
     }
-    switch (L.c) {   // the solver kernel is instantiated per chunk length: no guards, everything in registers
-#define MACHIP_LOB_CASE(C) case C: lob_launch_chunk_t<C>(AT, pl, L, steps); break;
-        MACHIP_LOB_CASE(1) MACHIP_LOB_CASE(2) MACHIP_LOB_CASE(3) MACHIP_LOB_CASE(4) MACHIP_LOB_CASE(5) MACHIP_LOB_CASE(6)
-        MACHIP_LOB_CASE(7) MACHIP_LOB_CASE(8) MACHIP_LOB_CASE(9) MACHIP_LOB_CASE(10) MACHIP_LOB_CASE(11) MACHIP_LOB_CASE(12)
-        MACHIP_LOB_CASE(13) MACHIP_LOB_CASE(14) MACHIP_LOB_CASE(15)
-#undef MACHIP_LOB_CASE
-        default: lob_launch_chunk_t<16>(AT, pl, L, steps); break;
-    }
+    with_lob_chunk(L.c, [&](auto C) { lob_launch_chunk_t<SV(C)>(AT, pl, L, steps); });
 }
 inline int Solver::lob_enqueue_chunk(const CsrView& A, const CsrView& AT, const SpmvPlan& pl, const LobView& L, int steps) {
     if (!use_graph() || wb_active.s > 0) { lob_launch_chunk(AT, pl, L, steps); return MACHIP_OK; }   // (closure count is baked into the launches)
@@ -160,14 +153,7 @@ inline int Solver::wb_build(const LobView& L, int s) {
         k_wb_big_fwd<<<dim3(gw, s), kTriThreads, 0, stream>>>(L, W, Bg);
         k_wb_big_mid<<<dim3(gw, s), kTriThreads, 0, stream>>>(L, W, Bg);
         k_wb_big_fin<<<dim3(gw, s), kTriThreads, 0, stream>>>(L, W, Bg);
-    } else switch (L.c) {
-#define MACHIP_LOB_CASE(C) case C: k_wb_cols<C><<<s, kTriThreads, 0, stream>>>(L, W); break;
-        MACHIP_LOB_CASE(1) MACHIP_LOB_CASE(2) MACHIP_LOB_CASE(3) MACHIP_LOB_CASE(4) MACHIP_LOB_CASE(5) MACHIP_LOB_CASE(6)
-        MACHIP_LOB_CASE(7) MACHIP_LOB_CASE(8) MACHIP_LOB_CASE(9) MACHIP_LOB_CASE(10) MACHIP_LOB_CASE(11) MACHIP_LOB_CASE(12)
-        MACHIP_LOB_CASE(13) MACHIP_LOB_CASE(14) MACHIP_LOB_CASE(15)
-#undef MACHIP_LOB_CASE
-        default: k_wb_cols<16><<<s, kTriThreads, 0, stream>>>(L, W); break;
-    }
+    } else with_lob_chunk(L.c, [&](auto C) { k_wb_cols<SV(C)><<<s, kTriThreads, 0, stream>>>(L, W); });
     const int g2s = (int)std::min<long>(kMaxGrid, ((long)W.ld * W.ld + kBlock - 1) / kBlock);
     k_wb_cap<<<g2s, kBlock, 0, stream>>>(L, W);
     // C^-1: ld / 32 blocked Gauss-Jordan steps on the matrix cores, ping-pong between the two buffers (woodbury.h)
@@ -246,14 +232,7 @@ inline int Solver::solve_lob(const CsrView& A, long nnz, double lnorm, double to
     if (n > kTriMaxN) k_tri_factor_big<<<1, kTriThreads, 0, stream>>>(A, L.stride, sigma, lx_tl, lx_tdinv, lx_tcu, lx_as, lx_bs, lx_bad, chain_only);
     else {
         k_tri_band<<<g2, kBlock, 0, stream>>>(A, L.c, L.stride, lx_ba, lx_bd, lx_bu);
-        switch (L.c) {
-#define MACHIP_LOB_CASE(C) case C: k_tri_factor<C><<<1, kTriThreads, 0, stream>>>(n, lx_ba, lx_bd, lx_bu, sigma, lx_tl, lx_tdinv, lx_tcu, lx_bad, chain_only); break;
-        MACHIP_LOB_CASE(1) MACHIP_LOB_CASE(2) MACHIP_LOB_CASE(3) MACHIP_LOB_CASE(4) MACHIP_LOB_CASE(5) MACHIP_LOB_CASE(6)
-        MACHIP_LOB_CASE(7) MACHIP_LOB_CASE(8) MACHIP_LOB_CASE(9) MACHIP_LOB_CASE(10) MACHIP_LOB_CASE(11) MACHIP_LOB_CASE(12)
-        MACHIP_LOB_CASE(13) MACHIP_LOB_CASE(14) MACHIP_LOB_CASE(15)
-#undef MACHIP_LOB_CASE
-        default: k_tri_factor<16><<<1, kTriThreads, 0, stream>>>(n, lx_ba, lx_bd, lx_bu, sigma, lx_tl, lx_tdinv, lx_tcu, lx_bad, chain_only); break;
-        }
+        with_lob_chunk(L.c, [&](auto C) { k_tri_factor<SV(C)><<<1, kTriThreads, 0, stream>>>(n, lx_ba, lx_bd, lx_bu, sigma, lx_tl, lx_tdinv, lx_tcu, lx_bad, chain_only); });
     }
     CsrView AT = A;
     k_lob_perm_cols<<<(int)std::min<long>(kMaxGrid, (nnz + kBlock - 1) / kBlock), kBlock, 0, stream>>>(A.col, nnz, L.c, L.stride, lx_colT);

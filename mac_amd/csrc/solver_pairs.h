@@ -120,24 +120,8 @@ __global__ __launch_bounds__(kBlock) void k_pairs_mul(CsrView A, PairsMul M) {
 }
 
 inline void launch_pairs_mul(const SpmvPlan& pl, hipStream_t s, const CsrView& A, const PairsMul& M) {
-    if (pl.variant == kStream) {
-        switch (pl.width) {
-            case 1: k_pairs_mul<true, 1><<<pl.grid, kBlock, 0, s>>>(A, M); break;
-            case 2: k_pairs_mul<true, 2><<<pl.grid, kBlock, 0, s>>>(A, M); break;
-            case 4: k_pairs_mul<true, 4><<<pl.grid, kBlock, 0, s>>>(A, M); break;
-            case 8: k_pairs_mul<true, 8><<<pl.grid, kBlock, 0, s>>>(A, M); break;
-            default: k_pairs_mul<true, 16><<<pl.grid, kBlock, 0, s>>>(A, M); break;
-        }
-    } else {
-        switch (pl.width) {
-            case 2: k_pairs_mul<false, 2><<<pl.grid, kBlock, 0, s>>>(A, M); break;
-            case 4: k_pairs_mul<false, 4><<<pl.grid, kBlock, 0, s>>>(A, M); break;
-            case 8: k_pairs_mul<false, 8><<<pl.grid, kBlock, 0, s>>>(A, M); break;
-            case 16: k_pairs_mul<false, 16><<<pl.grid, kBlock, 0, s>>>(A, M); break;
-            case 32: k_pairs_mul<false, 32><<<pl.grid, kBlock, 0, s>>>(A, M); break;
-            default: k_pairs_mul<false, 64><<<pl.grid, kBlock, 0, s>>>(A, M); break;
-        }
-    }
+    if (pl.variant == kStream) with_stream_width(pl.width, [&](auto W) { k_pairs_mul<true, SV(W)><<<pl.grid, kBlock, 0, s>>>(A, M); });
+    else with_vec_width(pl.width, [&](auto W) { k_pairs_mul<false, SV(W)><<<pl.grid, kBlock, 0, s>>>(A, M); });
 }
 
 // Q^T x for a vector that is not a step's product (a start vector, a Ritz vector): partials in k_pairs_mul's layout (q_i.t slots)

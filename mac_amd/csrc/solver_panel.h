@@ -1,6 +1,6 @@
 // solver_panel.h -- host side of the column-panel step (panel.h, panel_u.h): the per-row tables the assembly writes on the side,
-// the panel form's buffers and its build, the dispatch of one step onto the kernel instantiations, plain products on the panel
-// form.  Members of Solver (solver.h); the shapes come from plan.h.
+// the panel form's buffers and its build, the launches of one step, plain products on the panel form.  Members of Solver (solver.h);
+// the shapes and the tables that pick the kernel instantiations come from plan.h.
 #pragma once
 #include "solver.h"
 
@@ -11,15 +11,9 @@ template <class Op>
 inline void Solver::panel_spmv(const double* x, const Op& op, int grid) {
     const int g1 = pan.NB * pan.NP;
     const PipeView L = pview(SpmvPlan());
-    switch (pan.LPT * 10 + pan.TWT) {
-#define MACHIP_PANU_CASE(LP, TW) case LP * 10 + TW: k_pan_mul8<LP, TW, double><<<g1, kPanThreads, 0, stream>>>(x, panv.tptr, panv.thead, panv.bval, panv.bcol, panv.n, panv.C, panv.NP | (panv.TWW << 16), panv.NTB << 16, panv, L, -1); break;
-#define MACHIP_PANU_ROW(LP) MACHIP_PANU_CASE(LP, 3) MACHIP_PANU_CASE(LP, 5) MACHIP_PANU_CASE(LP, 8)
-        MACHIP_PANU_ROW(1) MACHIP_PANU_ROW(2) MACHIP_PANU_ROW(3) MACHIP_PANU_ROW(4) MACHIP_PANU_ROW(5) MACHIP_PANU_ROW(6)
-        MACHIP_PANU_ROW(7) MACHIP_PANU_ROW(8) MACHIP_PANU_CASE(9, 3)
-#undef MACHIP_PANU_ROW
-#undef MACHIP_PANU_CASE
-        default: break;
-    }
+    with_pan_mul8_shape(pan.LPT, pan.TWT, [&](auto LP, auto TW) {
+        k_pan_mul8<SV(LP), SV(TW), double><<<g1, kPanThreads, 0, stream>>>(x, panv.tptr, panv.thead, panv.bval, panv.bcol, panv.n, panv.C, panv.NP | (panv.TWW << 16), panv.NTB << 16, panv, L, -1);
+    });
     k_pan_rowop<Op><<<grid, kBlock, 0, stream>>>(panv, x, op);
 }
 // ---- column-panel step (panel.h) ---------------------------------------------------------------
@@ -120,19 +114,8 @@ inline int Solver::ensure_panel(const CsrView& A, long nnz, const PanPlan& pn, b
         // must not take the old flag for them -- advisor finding on round 5)
         pan_rows_ready = true; pan_rows_NP = pn.NP; pan_rows_C = pn.C; pan_rows_band = band;
     }
-    {
-        const int g = pan_build_grid(pn.NB, pn.NP);
-        switch ((64 * pn.NTB + kPanThreads - 1) / kPanThreads) {      // rows per thread of the build kernel
-            case 1: k_pan_build<1><<<g, kPanThreads, 0, stream>>>(A, panv); break;
-            case 2: k_pan_build<2><<<g, kPanThreads, 0, stream>>>(A, panv); break;
-            case 3: k_pan_build<3><<<g, kPanThreads, 0, stream>>>(A, panv); break;
-            case 4: k_pan_build<4><<<g, kPanThreads, 0, stream>>>(A, panv); break;
-            case 5: k_pan_build<5><<<g, kPanThreads, 0, stream>>>(A, panv); break;
-            case 6: k_pan_build<6><<<g, kPanThreads, 0, stream>>>(A, panv); break;
-            case 7: k_pan_build<7><<<g, kPanThreads, 0, stream>>>(A, panv); break;
-            default: k_pan_build<8><<<g, kPanThreads, 0, stream>>>(A, panv); break;
-        }
-    }
+    const int g = pan_build_grid(pn.NB, pn.NP);      // (rows per thread of the build kernel: 1 .. 8)
+    with_int<1, 8>((64 * pn.NTB + kPanThreads - 1) / kPanThreads, [&](auto R) { k_pan_build<SV(R)><<<g, kPanThreads, 0, stream>>>(A, panv); });
     HIP_TRY(hipGetLastError());
     (void)nnz;
     return MACHIP_OK;
@@ -145,54 +128,18 @@ inline int Solver::ensure_panel(const CsrView& A, long nnz, const PanPlan& pn, b
 inline void Solver::launch_pan_step(const PipeView& L, int s, int jhost) {
     const int g1 = pan.NB * pan.NP;
     if (pan_u) {             // shifted recurrence (panel_u.h): 8-byte operand, no prologue in the matrix kernel; the row kernel leads
-        if (pan32 && jhost >= 0 && jhost >= pan32_from) {      // mixed mode: this step reads fp32 tile values (TWT = 3 shapes only: solve() checks)
-            switch (pan.LPT) {
-#define MACHIP_PANU32_CASE(LP) case LP: k_pan_mul8<LP, 3, float><<<g1, kPanThreads, 0, stream>>>(PAN_MUL8_ARGS(panv, pu, L, s), pan_bv32); break;
-                MACHIP_PANU32_CASE(1) MACHIP_PANU32_CASE(2) MACHIP_PANU32_CASE(3) MACHIP_PANU32_CASE(4) MACHIP_PANU32_CASE(5) MACHIP_PANU32_CASE(6)
-                MACHIP_PANU32_CASE(7) MACHIP_PANU32_CASE(8) MACHIP_PANU32_CASE(9)
-#undef MACHIP_PANU32_CASE
-                default: break;
-            }
-        } else
-        switch (pan.LPT * 10 + pan.TWT) {
-#define MACHIP_PANU_CASE(LP, TW) case LP * 10 + TW: k_pan_mul8<LP, TW><<<g1, kPanThreads, 0, stream>>>(PAN_MUL8_ARGS(panv, pu, L, s)); break;
-#define MACHIP_PANU_ROW(LP) MACHIP_PANU_CASE(LP, 3) MACHIP_PANU_CASE(LP, 5) MACHIP_PANU_CASE(LP, 8)
-            MACHIP_PANU_ROW(1) MACHIP_PANU_ROW(2) MACHIP_PANU_ROW(3) MACHIP_PANU_ROW(4) MACHIP_PANU_ROW(5) MACHIP_PANU_ROW(6)
-            MACHIP_PANU_ROW(7) MACHIP_PANU_ROW(8) MACHIP_PANU_CASE(9, 3)
-#undef MACHIP_PANU_ROW
-#undef MACHIP_PANU_CASE
-            default: break;      // (plan_panel only hands out instantiated shapes)
-        }
-        const int npm = pan.NP <= 6 ? 6 : pan.NP <= 8 ? 8 : pan.NP <= 12 ? 12 : 16;
-        switch (pan.block2 * 100 + npm) {
-#define MACHIP_FINU_CASE(B, M) case B * 100 + M: k_pan_finu<B, M><<<pan.grid2, B, 0, stream>>>(PAN_FINU_ARGS(panv, pu, L, s, jhost) MACHIP_FINU_CLK); break;
-#define MACHIP_FINU_ROW(B) MACHIP_FINU_CASE(B, 6) MACHIP_FINU_CASE(B, 8) MACHIP_FINU_CASE(B, 12) MACHIP_FINU_CASE(B, 16)
-            MACHIP_FINU_ROW(256) MACHIP_FINU_ROW(512) MACHIP_FINU_ROW(1024)
-#undef MACHIP_FINU_ROW
-#undef MACHIP_FINU_CASE
-            default: break;
-        }
+        if (pan32 && jhost >= 0 && jhost >= pan32_from)       // mixed mode: this step reads fp32 tile values (TWT = 3 shapes only: solve() checks)
+            with_pan_mul8_shape(pan.LPT, 3, [&](auto LP, auto) { k_pan_mul8<SV(LP), 3, float><<<g1, kPanThreads, 0, stream>>>(PAN_MUL8_ARGS(panv, pu, L, s), pan_bv32); });
+        else
+            with_pan_mul8_shape(pan.LPT, pan.TWT, [&](auto LP, auto TW) { k_pan_mul8<SV(LP), SV(TW)><<<g1, kPanThreads, 0, stream>>>(PAN_MUL8_ARGS(panv, pu, L, s)); });
+        with_finu_shape(pan, [&](auto B, auto M) { k_pan_finu<SV(B), SV(M)><<<pan.grid2, SV(B), 0, stream>>>(PAN_FINU_ARGS(panv, pu, L, s, jhost) MACHIP_FINU_CLK); });
         return;
     }
     if (pan.cells > 1) {     // several row blocks per workgroup, the panel loaded once (k_pan_mul_multi)
         const int gm = pan.NP * ((pan.NB + pan.cells - 1) / pan.cells);
-        switch (pan.RPT) {
-#define MACHIP_PAN_CASE(R) case R: k_pan_mul_multi<R><<<gm, kPanThreads, 0, stream>>>(PAN_MUL_ARGS(panv, L, s)); break;
-            MACHIP_PAN_CASE(1) MACHIP_PAN_CASE(2) MACHIP_PAN_CASE(3) MACHIP_PAN_CASE(4) MACHIP_PAN_CASE(5) MACHIP_PAN_CASE(6)
-            MACHIP_PAN_CASE(7) MACHIP_PAN_CASE(8) MACHIP_PAN_CASE(9) MACHIP_PAN_CASE(10) MACHIP_PAN_CASE(11) MACHIP_PAN_CASE(12)
-#undef MACHIP_PAN_CASE
-            default: k_pan_mul_multi<13><<<gm, kPanThreads, 0, stream>>>(PAN_MUL_ARGS(panv, L, s)); break;
-        }
-    } else switch (pan.RPT) {
-#define MACHIP_PAN_CASE(R) case R: k_pan_mul<R><<<g1, kPanThreads, 0, stream>>>(PAN_MUL_ARGS(panv, L, s)); break;
-        MACHIP_PAN_CASE(1) MACHIP_PAN_CASE(2) MACHIP_PAN_CASE(3) MACHIP_PAN_CASE(4) MACHIP_PAN_CASE(5) MACHIP_PAN_CASE(6)
-        MACHIP_PAN_CASE(7) MACHIP_PAN_CASE(8) MACHIP_PAN_CASE(9) MACHIP_PAN_CASE(10) MACHIP_PAN_CASE(11) MACHIP_PAN_CASE(12)
-#undef MACHIP_PAN_CASE
-        default: k_pan_mul<13><<<g1, kPanThreads, 0, stream>>>(PAN_MUL_ARGS(panv, L, s)); break;
-    }
-    if (pan.block2 == 1024) k_pan_fin<1024><<<pan.grid2, 1024, 0, stream>>>(PAN_FIN_ARGS(panv, L, s));
-    else if (pan.block2 == 512) k_pan_fin<512><<<pan.grid2, 512, 0, stream>>>(PAN_FIN_ARGS(panv, L, s));
-    else k_pan_fin<256><<<pan.grid2, 256, 0, stream>>>(PAN_FIN_ARGS(panv, L, s));
+        with_pan_rpt(pan.RPT, [&](auto R) { k_pan_mul_multi<SV(R)><<<gm, kPanThreads, 0, stream>>>(PAN_MUL_ARGS(panv, L, s)); });
+    } else with_pan_rpt(pan.RPT, [&](auto R) { k_pan_mul<SV(R)><<<g1, kPanThreads, 0, stream>>>(PAN_MUL_ARGS(panv, L, s)); });
+    with_block(pan.block2, [&](auto B) { k_pan_fin<SV(B)><<<pan.grid2, SV(B), 0, stream>>>(PAN_FIN_ARGS(panv, L, s)); });
 }
 
 }  // namespace machip

@@ -79,27 +79,11 @@ inline void Solver::launch_chunk_ipc_pan(const SpmvPlan& pl, int steps, int j0) 
     const long r_lo = (long)ipc->g0 * pan.block2, r_hi = std::min<long>((long)ipc->g1 * pan.block2, (long)n);
     const int b0 = (int)(r_lo / Rb), b1 = (int)((r_hi + Rb - 1) / Rb);
     const int g1m = std::max(1, b1 - b0) * pan.NP, gf = ipc->g1 - ipc->g0;
-    const int npm = pan.NP <= 6 ? 6 : pan.NP <= 8 ? 8 : pan.NP <= 12 ? 12 : 16;
     k_ipc_wait<<<1, 64, 0, stream>>>(ipc->view, 0);              // (whatever the previous chunk / the sequence start left pending)
     for (int s = 0; s < steps; ++s) {
         const int jhost = j0 >= 0 ? j0 + s : -1;
-        switch (pan.LPT * 10 + pan.TWT) {
-#define MACHIP_PANU_CASE(LP, TW) case LP * 10 + TW: k_pan_mul8<LP, TW, double><<<g1m, kPanThreads, 0, stream>>>(PAN_MUL8_ARGS_AT(panv, pu, L, s, b0)); break;
-#define MACHIP_PANU_ROW(LP) MACHIP_PANU_CASE(LP, 3) MACHIP_PANU_CASE(LP, 5) MACHIP_PANU_CASE(LP, 8)
-            MACHIP_PANU_ROW(1) MACHIP_PANU_ROW(2) MACHIP_PANU_ROW(3) MACHIP_PANU_ROW(4) MACHIP_PANU_ROW(5) MACHIP_PANU_ROW(6)
-            MACHIP_PANU_ROW(7) MACHIP_PANU_ROW(8) MACHIP_PANU_CASE(9, 3)
-#undef MACHIP_PANU_ROW
-#undef MACHIP_PANU_CASE
-            default: break;
-        }
-        switch (pan.block2 * 100 + npm) {
-#define MACHIP_FINU_CASE(B, M) case B * 100 + M: k_pan_finu<B, M, true><<<gf, B, 0, stream>>>(PAN_FINU_ARGS(panv, pu, L, s, jhost), d_ps, PS.first, PS.total); break;
-#define MACHIP_FINU_ROW(B) MACHIP_FINU_CASE(B, 6) MACHIP_FINU_CASE(B, 8) MACHIP_FINU_CASE(B, 12) MACHIP_FINU_CASE(B, 16)
-            MACHIP_FINU_ROW(256) MACHIP_FINU_ROW(512) MACHIP_FINU_ROW(1024)
-#undef MACHIP_FINU_ROW
-#undef MACHIP_FINU_CASE
-            default: break;
-        }
+        with_pan_mul8_shape(pan.LPT, pan.TWT, [&](auto LP, auto TW) { k_pan_mul8<SV(LP), SV(TW), double><<<g1m, kPanThreads, 0, stream>>>(PAN_MUL8_ARGS_AT(panv, pu, L, s, b0)); });
+        with_finu_shape(pan, [&](auto B, auto M) { k_pan_finu<SV(B), SV(M), true><<<gf, SV(B), 0, stream>>>(PAN_FINU_ARGS(panv, pu, L, s, jhost), d_ps, PS.first, PS.total); });
         k_ipc_pubwait<<<1, 64, 0, stream>>>(ipc->view, 0);       // mine delivered; every peer has delivered its operand rows / partial sums of this step
     }
     k_pipe_tail<<<1, 64, 0, stream>>>(L, steps);

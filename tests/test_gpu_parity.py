@@ -1019,6 +1019,60 @@ def test_in_process_ranks_match_single_rank(R):
         P.close()
 
 
+PIPE_KEYS = [(4, 1), (4, 2), (4, 4), (8, 1), (8, 2), (8, 4), (16, 1), (16, 2), (16, 4), (32, 1), (32, 2), (64, 1), (64, 2)]
+PIPE_SHAPES = ([(g, u, 256, 1, 0) for g, u in PIPE_KEYS] +
+               [(g, u, 256, 3, 8) for g, u in [(4, 1), (4, 2), (8, 2), (8, 4), (16, 2)]] +     # the deferred-barrier builds: 8 workgroups, several row tiles each
+               [(8, 4, 512, 1, 0), (4, 1, 1024, 1, 0)])
+
+
+@pytest.mark.parametrize("g_,unroll,block,defer,maxgrid", PIPE_SHAPES)
+def test_sharded_step_picks_the_plain_steps_instantiation(g_, unroll, block, defer, maxgrid):
+    """Every listed shape of the one-kernel gather step (lanes per row, load chains, workgroup size, deferred barrier), forced
+    through the options on er2000: two in-process ranks -- the sharded launch of the step, and the rows-per-workgroup figure
+    that decides which basis rows a rank owns -- reproduce a single handle under the same options bit for bit: f, dual bound,
+    ||g||, x and the gradient.  The other step forms are switched off for both (panel, padded, single-workgroup), and the
+    single handle must report the gather step (solve mode 1), or the comparison would mean nothing."""
+    import threading
+    g = load_golden("er2000_solve")
+    n, k = int(g["n"]), int(g["k"])
+    start = reference_start_block(n)[:, 0].copy()
+    shape = dict(g=g_, unroll=unroll, block=block, defer=defer)
+    if maxgrid:
+        shape["maxgrid"] = maxgrid
+
+    def drive(P, out, i):
+        try:
+            P.set_start(start); P.set_x(g["x_init"])
+            fs = []
+            for it in range(2):
+                fs.append(P.fw_step(k, it)); P.fw_commit()
+            out[i] = (np.array(fs), P.get_x(), P.gradient(), int(P.stats.lanczos_steps), P.solve_mode()[0])
+        except Exception as exc:       # a failing rank must not leave its peer in the barrier
+            out[i] = exc
+            P.close()
+    with _lib.default_options(panel=0, ell=0, persist=0, **shape):
+        single = [None]
+        P0 = problem_of(g); drive(P0, single, 0); P0.close()
+        assert not isinstance(single[0], Exception), single[0]
+        assert single[0][4] == 1, "the single handle did not run the one-kernel gather step"
+        Ps = [problem_of(g) for _ in range(2)]
+        _lib.comm_init_local(Ps)
+        assert _lib.load().machip_comm_mode(Ps[0]._h) == 3
+        out = [None, None]
+        th = [threading.Thread(target=drive, args=(Ps[r], out, r)) for r in range(2)]
+        for t in th:
+            t.start()
+        for t in th:
+            t.join(timeout=300)
+        for r in range(2):
+            assert not isinstance(out[r], Exception), out[r]
+            for a, b, what in zip(out[r][:3], single[0][:3], ("f / dual bound / ||g||", "x", "gradient")):
+                assert np.array_equal(a, b), f"rank {r}: {what} differs from the single handle's"
+        assert out[0][3] == out[1][3] > 0
+        for P in Ps:
+            P.close()
+
+
 @pytest.mark.parametrize("cfg,R,iters", [("c2", 4, 3), ("c4", 2, 2), ("c4", 8, 2)])
 def test_row_partitioned_eigensolve_is_bit_identical_at_bench_sizes(cfg, R, iters):
     """The row-partitioned Lanczos step of the in-process communicator (rank r launches its share of every step's
