@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define MACHIP_ABI_VERSION 19   /* 19: machip_lowest_pairs, machip_lowest_pairs_csr (the q lowest non-trivial eigenpairs, every one converged to the stop rule; option pairs_vcap), machip_lowest_pairs_time, machip_gradient_block; 18: machip_eig_exchange_free (the exchange on lambda_2 on MACHIP_EIG_MATRIX_FREE / _TREE handles; option eig_xch_free_swaps), machip_eig_history; 17: MACHIP_EIG_MATRIX_FREE_TREE (GreedyEig on any connected fixed graph without a dense Sigma; machip_eig_seeds); 16: MACHIP_EIG_MATRIX_FREE (GreedyEig on a chain without a dense Sigma; options eig_free_rows, eig_free_split); 15: machip_eig_exchange (best-swap local search on lambda_2; option eig_xch_max_mb); 14: machip_esp_exchange_edge (the exchange in the candidates' space on MACHIP_ESP_EDGE_RELAX / MACHIP_ESP_EDGE_RELAX_TREE handles); 13: machip_esp_exchange (best-swap local search on the log tree count; options esp_xch_lds_kb, esp_xch_max_mb, esp_xch_profile); 12: MACHIP_ESP_EDGE_RELAX (the relaxation in the candidates' space on a chain-fixed graph; machip_esp_relax_info); 11: MACHIP_ESP_SPANNING_TREE (the matrix-free route of GreedyESP for any connected fixed graph; machip_esp_tree_plan, machip_esp_seeds); 10: MACHIP_ESP_MATRIX_FREE (GreedyESP on a chain without a dense Sigma, option esp_free_split); 9: the relaxation of GreedyESP's problem (machip_esp_relax_*); 8: GreedyEig handle (machip_eig_*); 7: GreedyESP handle (machip_esp_*); 6: machip_solve_stats.drift, machip_panel_plan fills 12 entries; 5: per-handle option table (machip_set_option), machip_comm_drop_ipc; 4: inter-process communicator */
+#define MACHIP_ABI_VERSION 20   /* 20: option pairs_precond (preconditioned deflated columns of machip_lowest_pairs), machip_lowest_pairs_info, machip_lowest_pairs_csr2; 19: machip_lowest_pairs, machip_lowest_pairs_csr (the q lowest non-trivial eigenpairs, every one converged to the stop rule; option pairs_vcap), machip_lowest_pairs_time, machip_gradient_block; 18: machip_eig_exchange_free (the exchange on lambda_2 on MACHIP_EIG_MATRIX_FREE / _TREE handles; option eig_xch_free_swaps), machip_eig_history; 17: MACHIP_EIG_MATRIX_FREE_TREE (GreedyEig on any connected fixed graph without a dense Sigma; machip_eig_seeds); 16: MACHIP_EIG_MATRIX_FREE (GreedyEig on a chain without a dense Sigma; options eig_free_rows, eig_free_split); 15: machip_eig_exchange (best-swap local search on lambda_2; option eig_xch_max_mb); 14: machip_esp_exchange_edge (the exchange in the candidates' space on MACHIP_ESP_EDGE_RELAX / MACHIP_ESP_EDGE_RELAX_TREE handles); 13: machip_esp_exchange (best-swap local search on the log tree count; options esp_xch_lds_kb, esp_xch_max_mb, esp_xch_profile); 12: MACHIP_ESP_EDGE_RELAX (the relaxation in the candidates' space on a chain-fixed graph; machip_esp_relax_info); 11: MACHIP_ESP_SPANNING_TREE (the matrix-free route of GreedyESP for any connected fixed graph; machip_esp_tree_plan, machip_esp_seeds); 10: MACHIP_ESP_MATRIX_FREE (GreedyESP on a chain without a dense Sigma, option esp_free_split); 9: the relaxation of GreedyESP's problem (machip_esp_relax_*); 8: GreedyEig handle (machip_eig_*); 7: GreedyESP handle (machip_esp_*); 6: machip_solve_stats.drift, machip_panel_plan fills 12 entries; 5: per-handle option table (machip_set_option), machip_comm_drop_ipc; 4: inter-process communicator */
 
 typedef enum machip_status {
     MACHIP_OK = 0,
@@ -138,6 +138,12 @@ int machip_fiedler(machip_problem* p, double tol, int max_steps, const double* x
  * were run (their statuses tell), MACHIP_DISCONNECTED as machip_fiedler does, MACHIP_BAD_ARG for q out of range, a start vector
  * inside the span of the columns before it, an evaluation lane or a handle that belongs to a communicator (one GPU, one rank).
  * Option pairs_vcap: most basis columns a deflated sequence fills before it restarts from its Ritz vector (0: the basis budget).
+ * Option pairs_precond (0, the default: the deflated Lanczos above, bit for bit; 1: opt in): on a chain-like graph in fp64 with
+ * n <= 2^21, columns 1 .. q-1 run a block-size-1 LOBPCG in the complement of the columns found so far, preconditioned as the Fiedler
+ * solve's modes 6 / 7 are (mac_amd/csrc/solver_pairs_lob.h; the preconditioner is column 0's when that solve ran
+ * mode 6 / 7, else built once per call).  steps_out then counts iterations.  A column whose iteration ends without a passing check
+ * (breakdown, the cap, patience) is finished by the deflated Lanczos from the last checked vector, its steps added; max_steps caps
+ * the sum.  On any other handle the option changes nothing.  machip_lowest_pairs_info tells which route produced each column.
  * The handle's Fiedler state (vector, gradient, warm start) is afterwards what the column-0 solve alone would have left. */
 int machip_lowest_pairs(machip_problem* p, int q, double tol, int max_steps, const double* X0, int warm_start,
                         double* lambda_out, double* V_out, double* residual_out, int32_t* steps_out, int32_t* restarts_out,
@@ -147,6 +153,18 @@ int machip_lowest_pairs_csr(int device, int64_t n, const int32_t* indptr, const 
                             int q, double tol, int max_steps, const double* X0, int warm_start,
                             double* lambda_out, double* V_out, double* residual_out, int32_t* steps_out, int32_t* restarts_out,
                             int32_t* status_out, int32_t* reordered_out, int32_t* first_rank_out);
+/* machip_lowest_pairs_csr with option pairs_precond for this call (-1: the process default) and machip_lowest_pairs_info's outputs. */
+int machip_lowest_pairs_csr2(int device, int64_t n, const int32_t* indptr, const int32_t* indices, const double* data,
+                             int q, double tol, int max_steps, const double* X0, int warm_start,
+                             double* lambda_out, double* V_out, double* residual_out, int32_t* steps_out, int32_t* restarts_out,
+                             int32_t* status_out, int32_t* reordered_out, int32_t* first_rank_out,
+                             int pairs_precond, int32_t* method_out, int32_t* closures_out, double* build_ms_out);
+/* How the columns of the handle's last machip_lowest_pairs call were produced, by rank.  method_out (q): the solver mode -- the
+ * Fiedler solve's own (machip_solve_mode) for the column it produced; 1 deflated Lanczos; 6 / 7 LOBPCG preconditioned by the
+ * tridiagonal chain / the exact chain + closures inverse; 9 such iterations, then finished by the deflated Lanczos.  *closures_out:
+ * closures of the exact preconditioner the deflated columns ran with (0: none did).  *build_ms_out: device ms of the one-off
+ * preconditioner build (0 when column 0's was reused or none was built).  Each may be NULL. */
+int machip_lowest_pairs_info(machip_problem* p, int q, int32_t* method_out, int32_t* closures_out, double* build_ms_out);
 /* Device time, in ms and by rank, of the columns of the handle's last machip_lowest_pairs call (hipEvents on its stream around each
  * column: its steps, the host's looks at the records between chunks, Ritz vectors and checks; column 0: the Fiedler solve's gpu_ms). */
 int machip_lowest_pairs_time(machip_problem* p, int q, double* ms_out);

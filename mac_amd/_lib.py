@@ -43,6 +43,8 @@ _lib = None
 
 # lambda, V, residual, steps, restarts, status, reordered, first_rank: the outputs machip_lowest_pairs and its CSR form share
 _PAIRS_TAIL = [_f64p, _f64p, _f64p, _i32p, _i32p, _i32p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+PAIRS_METHODS = {"lanczos": 0, "lobpcg": 1}      # option pairs_precond (solver_pairs_lob.h); info["method"] 9 = kPairsModeFinished
+PAIRS_MODE_LANCZOS, PAIRS_MODE_TRI, PAIRS_MODE_EXACT, PAIRS_MODE_FINISHED = 1, 6, 7, 9
 PAIRS_CHUNK = 16              # kPairsChunk (mac_amd/csrc/solver_pairs.h): steps of a deflated column between two looks at its records
 
 # name -> (restype, argtypes); every symbol declared in include/machip.h
@@ -62,6 +64,9 @@ SIGNATURES = {
                                  C.POINTER(SolveStats)]),
     "machip_lowest_pairs": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_int, _f64p, C.c_int] + _PAIRS_TAIL),
     "machip_lowest_pairs_csr": (C.c_int, [C.c_int, C.c_int64, _i32p, _i32p, _f64p, C.c_int, C.c_double, C.c_int, _f64p, C.c_int] + _PAIRS_TAIL),
+    "machip_lowest_pairs_csr2": (C.c_int, [C.c_int, C.c_int64, _i32p, _i32p, _f64p, C.c_int, C.c_double, C.c_int, _f64p, C.c_int] + _PAIRS_TAIL
+                                 + [C.c_int, _i32p, _i32p, _f64p]),
+    "machip_lowest_pairs_info": (C.c_int, [C.c_void_p, C.c_int, _i32p, _i32p, _f64p]),
     "machip_lowest_pairs_time": (C.c_int, [C.c_void_p, C.c_int, _f64p]),
     "machip_gradient_block": (C.c_int, [C.c_void_p, C.c_int, _f64p, _f64p]),
     "machip_set_start": (C.c_int, [C.c_void_p, _f64p]),
@@ -333,13 +338,22 @@ class Problem:
         check(st)
         return lam.value, v, (X.T if X is not None else None)
 
-    def lowest_pairs(self, q=4, tol=1e-8, max_steps=0, X0=None, warm_start=False, raise_on_cap=False):
+    def lowest_pairs(self, q=4, tol=1e-8, max_steps=0, X0=None, warm_start=False, raise_on_cap=False, method="lanczos"):
         """The q lowest non-trivial eigenpairs of L(x), every one converged to the stop rule (machip_lowest_pairs):
-        ``(lams, V, info)``, V n x q; X0: n x q start block (None: the stored start vector and the reference's block)."""
+        ``(lams, V, info)``, V n x q; X0: n x q start block (None: the stored start vector and the reference's block).
+        method: "lanczos" (columns 1 .. q-1 by the deflated Lanczos), "lobpcg" (preconditioned where the graph is eligible,
+        DESIGN section 25; info["method"] tells per column) or None (what the handle's option pairs_precond says)."""
         X0 = None if X0 is None else np.asfortranarray(X0, dtype=np.float64)
         assert X0 is None or X0.shape == (self.n, q)
-        return _pairs_call(lambda *tail: self._lib.machip_lowest_pairs(self._h, int(q), float(tol), int(max_steps), p_f64(X0),
-                                                                       int(bool(warm_start)), *tail), self.n, q, raise_on_cap)
+        keep = self.get_option("pairs_precond")
+        if method is not None:
+            self.set_option("pairs_precond", PAIRS_METHODS[method])
+        try:
+            return _pairs_call(lambda *tail: self._lib.machip_lowest_pairs(self._h, int(q), float(tol), int(max_steps), p_f64(X0),
+                                                                           int(bool(warm_start)), *tail), self.n, q, raise_on_cap,
+                               lambda m, cl, ms: self._lib.machip_lowest_pairs_info(self._h, int(q), m, cl, ms))
+        finally:
+            self.set_option("pairs_precond", keep)
 
     def lowest_pairs_time(self, q):
         """Device ms per column (by rank) of the last lowest_pairs call on this handle (machip_lowest_pairs_time)."""
@@ -866,16 +880,25 @@ def fiedler_csr(indptr, indices, data, n, tol=1e-8, max_steps=0, x0=None, q=0, d
     return lam.value, v, (X.T if X is not None else None), stats
 
 
-def _pairs_call(call, n, q, raise_on_cap):
-    """Run a machip_lowest_pairs* entry point (call(*output pointers) -> status) and shape its outputs: (lams, V, info)."""
+def _pairs_call(call, n, q, raise_on_cap, how=None):
+    """Run a machip_lowest_pairs* entry point (call(*output pointers) -> status) and shape its outputs: (lams, V, info).
+    how(method, closures, build_ms pointers) -> status fills the route's outputs after a call on a handle; None: `call` took them
+    itself as its last three arguments (machip_lowest_pairs_csr2)."""
     q = int(q)
     nq = max(q, 1)
     lams, V, res = np.full(nq, np.nan), np.zeros((n, nq), order="F"), np.full(nq, np.inf)
-    steps, restarts, status = (np.zeros(nq, dtype=np.int32) for _ in range(3))
-    reordered, first_rank = C.c_int32(0), C.c_int32(0)
-    check(call(p_f64(lams), p_f64(V), p_f64(res), p_i32(steps), p_i32(restarts), p_i32(status), C.byref(reordered), C.byref(first_rank)))
+    steps, restarts, status, method = (np.zeros(nq, dtype=np.int32) for _ in range(4))
+    reordered, first_rank, closures, build_ms = C.c_int32(0), C.c_int32(0), C.c_int32(0), C.c_double(0.0)
+    tail = (p_f64(lams), p_f64(V), p_f64(res), p_i32(steps), p_i32(restarts), p_i32(status), C.byref(reordered), C.byref(first_rank))
+    route = (p_i32(method), C.cast(C.byref(closures), _i32p), C.cast(C.byref(build_ms), _f64p))
+    if how is None:
+        check(call(*tail, *route))
+    else:
+        check(call(*tail))
+        check(how(*route))
     info = {"residual": res, "steps": steps, "restarts": restarts, "status": status, "reordered": int(reordered.value),
-            "first_rank": int(first_rank.value), "gap": float(lams[1] - lams[0]) if q >= 2 else None}
+            "first_rank": int(first_rank.value), "gap": float(lams[1] - lams[0]) if q >= 2 else None,
+            "method": method, "closures": int(closures.value), "build_ms": float(build_ms.value)}
     if raise_on_cap and np.any(status == NOT_CONVERGED):
         bad = [int(c) for c in np.nonzero(status == NOT_CONVERGED)[0]]
         raise NotConverged(NOT_CONVERGED, f"lowest_pairs: column(s) {bad} hit the step cap before the residual test passed "
@@ -883,14 +906,17 @@ def _pairs_call(call, n, q, raise_on_cap):
     return lams, V, info
 
 
-def lowest_pairs_csr(indptr, indices, data, n, q=4, tol=1e-8, max_steps=0, X0=None, device=0, raise_on_cap=False):
-    """machip_lowest_pairs_csr: the q lowest non-trivial eigenpairs of a CSR Laplacian -> (lams, V, info)."""
+def lowest_pairs_csr(indptr, indices, data, n, q=4, tol=1e-8, max_steps=0, X0=None, device=0, raise_on_cap=False, method="lanczos"):
+    """machip_lowest_pairs_csr2: the q lowest non-trivial eigenpairs of a CSR Laplacian -> (lams, V, info); method as
+    Problem.lowest_pairs takes it (None: the process default of option pairs_precond)."""
     lib = load()
     indptr, indices, data = i32(indptr), i32(indices), f64(data)
     X0 = None if X0 is None else np.asfortranarray(X0, dtype=np.float64)
     assert X0 is None or X0.shape == (n, q)
-    return _pairs_call(lambda *tail: lib.machip_lowest_pairs_csr(int(device), int(n), p_i32(indptr), p_i32(indices), p_f64(data), int(q),
-                                                                 float(tol), int(max_steps), p_f64(X0), 0, *tail), int(n), q, raise_on_cap)
+    precond = -1 if method is None else PAIRS_METHODS[method]
+    return _pairs_call(lambda *out: lib.machip_lowest_pairs_csr2(int(device), int(n), p_i32(indptr), p_i32(indices), p_f64(data), int(q),
+                                                                 float(tol), int(max_steps), p_f64(X0), 0, *out[:8], precond, *out[8:]),
+                       int(n), q, raise_on_cap)
 
 
 def host_tridiag_smallest(a, b):

@@ -531,6 +531,8 @@ inline int lowest_pairs(machip_problem* p, int q, double tol, int max_steps, con
     const int s0 = run_fiedler(p, tol, max_steps, X0, X0 ? 0 : warm_start, &lam0, &st0);
     if (s0 != MACHIP_OK && s0 != MACHIP_NOT_CONVERGED) return s0;      // (a disconnected graph, an error: as machip_fiedler answers)
     cols[0].ms = st0.gpu_ms;
+    cols[0].method = S.last_mode;
+    S.pairs->last_closures = 0; S.pairs->build_ms = 0.0;
     cols[0].lam = lam0; cols[0].status = s0; cols[0].steps = (int)std::min<int64_t>(st0.lanczos_steps, INT_MAX); cols[0].restarts = (int)st0.restarts;
     cols[0].res = (st0.residual > 0.0 && std::isfinite(st0.residual)) ? st0.residual : (s0 == MACHIP_OK ? 0.0 : INFINITY);
     // a column 0 that missed the stop rule is no eigenvector to deflate by: the others stay NOT_CONVERGED with nothing measured
@@ -560,11 +562,19 @@ inline int lowest_pairs(machip_problem* p, int q, double tol, int max_steps, con
         if (restarts_out) restarts_out[r] = k.restarts;
         if (status_out) status_out[r] = k.status;
         S.pairs->last_ms[r] = k.ms;
+        S.pairs->last_method[r] = k.method;
     }
     S.pairs->last_q = q;
     if (reordered_out) *reordered_out = first_rank != 0;
     if (first_rank_out) *first_rank_out = first_rank;
     return MACHIP_OK;
+}
+
+// machip_lowest_pairs_info: how the columns of the handle's last machip_lowest_pairs call were produced
+inline void lowest_pairs_info(const PairsBuf& B, int q, int32_t* method_out, int32_t* closures_out, double* build_ms_out) {
+    if (method_out) for (int r = 0; r < q; ++r) method_out[r] = B.last_method[r];
+    if (closures_out) *closures_out = B.last_closures;
+    if (build_ms_out) *build_ms_out = B.build_ms;
 }
 
 // machip_gradient_block after its argument checks: k_grad on each column of a host block (the supergradient is bit-exact given the

@@ -197,6 +197,27 @@ int machip_lowest_pairs_csr(int device, int64_t n, const int32_t* indptr, const 
     });
 }
 
+int machip_lowest_pairs_csr2(int device, int64_t n, const int32_t* indptr, const int32_t* indices, const double* data, int q, double tol,
+                             int max_steps, const double* X0, int warm_start, double* lambda_out, double* V_out, double* residual_out,
+                             int32_t* steps_out, int32_t* restarts_out, int32_t* status_out, int32_t* reordered_out, int32_t* first_rank_out,
+                             int pairs_precond, int32_t* method_out, int32_t* closures_out, double* build_ms_out) {
+    if (!indptr || !indices || !data) return fail(MACHIP_BAD_ARG, "NULL argument");
+    if (n < 2 || n > 2000000000ll) return fail(MACHIP_BAD_ARG, "n must be in [2, 2e9]");
+    ST_TRY(pairs_args(n, q, lambda_out));
+    return with_csr_handle(device, n, indptr, indices, data, [&](machip_problem* p) {
+        if (pairs_precond >= 0) p->sol.opt.v[kOpt_pairs_precond] = pairs_precond;      // (else: the process default, as every option of this handle)
+        const int st = lowest_pairs(p, q, tol, max_steps, X0, warm_start, lambda_out, V_out, residual_out, steps_out, restarts_out, status_out, reordered_out, first_rank_out);
+        if (st == MACHIP_OK) lowest_pairs_info(*p->sol.pairs, q, method_out, closures_out, build_ms_out);
+        return st;
+    });
+}
+
+int machip_lowest_pairs_info(machip_problem* p, int q, int32_t* method_out, int32_t* closures_out, double* build_ms_out) {
+    if (!p || !p->sol.pairs || q < 1 || q > p->sol.pairs->last_q) return fail(MACHIP_BAD_ARG, "machip_lowest_pairs_info: no machip_lowest_pairs call of at least q columns on this handle");
+    lowest_pairs_info(*p->sol.pairs, q, method_out, closures_out, build_ms_out);
+    return MACHIP_OK;
+}
+
 int machip_lowest_pairs_time(machip_problem* p, int q, double* ms_out) {
     if (!p || !ms_out || !p->sol.pairs || q < 1 || q > p->sol.pairs->last_q) return fail(MACHIP_BAD_ARG, "machip_lowest_pairs_time: no machip_lowest_pairs call of at least q columns on this handle");
     for (int r = 0; r < q; ++r) ms_out[r] = p->sol.pairs->last_ms[r];

@@ -51,7 +51,10 @@ namespace machip {
     X(eig_free_rows) X(eig_free_split)                                                                                             \
     /* machip_lowest_pairs (solver_pairs.h; read by every call): most basis columns a deflated column's Krylov sequence may fill     \
        before it restarts from its Ritz vector (0 / unset: the handle's basis budget; at least 4) */                                \
-    X(pairs_vcap)
+    X(pairs_vcap)                                                                                                                  \
+    /* the same: 1 -- columns 1 .. q-1 run the preconditioned iteration of solver_pairs_lob.h where the handle is eligible (a chain-like \
+       graph, fp64, n <= 2^21), Lanczos finishing a column it does not converge; 0 / unset -- the deflated Lanczos */                \
+    X(pairs_precond)
 
 enum OptId {
 #define X(n) kOpt_##n,

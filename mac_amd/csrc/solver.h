@@ -12,7 +12,7 @@
 // This file is the DRIVER's core: struct Solver with its state, allocation, the graph cache, the explicit check and solve() with the
 // mode choice.  Its other members are defined in solver_lanczos.h (the Lanczos driver: solve_lanczos in its phases),
 // solver_lob.h (the preconditioned and exact modes), solver_panel.h (host side of the column-panel step) and solver_shard.h
-// (the row-partitioned solves) and solver_pairs.h (the deflated columns of machip_lowest_pairs), all included at the end of this file; launch shapes and the dispatch onto kernel instantiations
+// (the row-partitioned solves) and solver_pairs.h / solver_pairs_lob.h (the deflated columns of machip_lowest_pairs: Lanczos / preconditioned), all included at the end of this file; launch shapes and the dispatch onto kernel instantiations
 // are in plan.h, kernels in kernels.h / panel.h / persist.h / precond.h / woodbury.h.
 #pragma once
 #include <functional>
@@ -93,6 +93,8 @@ struct LanRun;        // one solve_lanczos call, one Krylov sequence of it, one 
 struct LanSeq;
 struct LanPending;
 using GraphKey = std::tuple<int, int, int, int, int>;
+// what lob_prepare leaves for the iterations on one matrix: launch shape, buffers, the product's view with permuted columns
+struct LobPrep { SpmvPlan pl; LobView L; CsrView AT; bool may_escalate = false; };
 
 struct Solver {
     Options opt = default_options();    // the handle's option table (machip_set_option); a copy of the process defaults at creation
@@ -502,12 +504,22 @@ struct Solver {
     int lob_c() const;
     int lob_stride() const;
     LobView lview(const SpmvPlan& pl) const;
-    template <int CMAX> void lob_launch_chunk_t(const CsrView& AT, const SpmvPlan& pl, const LobView& L, int steps);
-    void lob_launch_chunk(const CsrView& AT, const SpmvPlan& pl, const LobView& L, int steps);
-    int lob_enqueue_chunk(const CsrView& A, const CsrView& AT, const SpmvPlan& pl, const LobView& L, int steps);
+    // (nq: locked columns projected out of w in every iteration -- a deflated column of machip_lowest_pairs; 0: the Fiedler solve)
+    template <int CMAX> void lob_launch_chunk_t(const CsrView& AT, const SpmvPlan& pl, const LobView& L, int steps, int nq);
+    void lob_launch_chunk(const CsrView& AT, const SpmvPlan& pl, const LobView& L, int steps, int nq);
+    int lob_enqueue_chunk(const CsrView& A, const CsrView& AT, const SpmvPlan& pl, const LobView& L, int steps, int nq);
     int wb_alloc();
     int wb_extract(const CsrView& A, int hc[2]);
     int wb_build(const LobView& L, int s);
+    int lob_prepare(const CsrView& A, long nnz, double lnorm, LobPrep* P);
+    int lob_iterate(const CsrView& A, const LobPrep& P, double lnorm, double tol, int max_steps, int nq, double r1,
+                    double* lam, double* res, long* iters, long* spmvs, long* restarts_out);
+    // ---- preconditioned deflated columns of machip_lowest_pairs (solver_pairs_lob.h) ----
+    void lobq_project(const LobView& L, int nq);
+    void lobq_lock(const LobView& L, int col);
+    bool pairs_lob_eligible() const;
+    int pairs_lob_prepare(const CsrView& A, long nnz, double lnorm, LobPrep* P, bool reuse, bool timed);
+    int pairs_column_lob(const CsrView& A, long nnz, double lnorm, double tol, int max_steps, int c, LobPrep* P, PairsCol* out);
     int solve_lob(const CsrView& A, long nnz, double lnorm, double tol, int max_steps, int start_mode,
                   double* lam, double* res, long* iters, long* spmvs, long* restarts_out);
 
@@ -728,3 +740,4 @@ struct Solver {
 #include "solver_lob.h"
 #include "solver_lanczos.h"
 #include "solver_pairs.h"
+#include "solver_pairs_lob.h"

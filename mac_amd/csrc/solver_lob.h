@@ -1,6 +1,7 @@
 // solver_lob.h -- the preconditioned modes of the eigen-solver: a block-size-1 LOBPCG on L preconditioned by the tridiagonal chain
 // (precond.h) or, up to wb_soft() / wb_hard() closures, by the exact chain + closures inverse (woodbury.h).  Buffers, one chunk of
-// iterations, the build of the exact preconditioner and the host loop solve_lob.  Members of Solver (solver.h).
+// iterations, the build of the preconditioner (lob_prepare), the host loop (lob_iterate: shared with the deflated columns of
+// machip_lowest_pairs, solver_pairs_lob.h) and the Fiedler solve made of the two, solve_lob.  Members of Solver (solver.h).
 #pragma once
 #include "solver.h"
 
@@ -56,7 +57,7 @@ inline LobView Solver::lview(const SpmvPlan& pl) const {
     return L;
 }
 template <int CMAX>
-inline void Solver::lob_launch_chunk_t(const CsrView& AT, const SpmvPlan& pl, const LobView& L, int steps) {
+inline void Solver::lob_launch_chunk_t(const CsrView& AT, const SpmvPlan& pl, const LobView& L, int steps, int nq) {
     OpLob op;
     op.L = L;
     // Round 4: between two products the update of iteration s - 1, the tridiagonal solve of iteration s and g = U^T y run as ONE
@@ -75,13 +76,14 @@ inline void Solver::lob_launch_chunk_t(const CsrView& AT, const SpmvPlan& pl, co
             k_wb_h<<<std::min(kMaxGrid, (W.s + 3) / 4), kBlock, 0, stream>>>(W);
             k_wb_w<<<(int)std::min<size_t>(kMaxGrid, W.cap / kWbwRows), kWbwThreads, 0, stream>>>(L, W);
         }
+        if (nq > 0) lobq_project(L, nq);      // (a deflated column: w <- w - Q Q^T w, solver_pairs_lob.h)
         launch_spmv(pl, stream, AT, L.wT, op);
         if (fuse && s + 1 < steps) k_lob_fused<CMAX><<<1, kTriThreads, 0, stream>>>(L, W0, s);
         else k_lob_update<<<L.P_a, kBlock, 0, stream>>>(L, s);
     }
     k_lob_tail<<<1, 64, 0, stream>>>(L, steps);
 }
-inline void Solver::lob_launch_chunk(const CsrView& AT, const SpmvPlan& pl, const LobView& L, int steps) {
+inline void Solver::lob_launch_chunk(const CsrView& AT, const SpmvPlan& pl, const LobView& L, int steps, int nq) {
     if (n > kTriMaxN) {
         OpLob op;
         op.L = L;
@@ -96,18 +98,20 @@ inline void Solver::lob_launch_chunk(const CsrView& AT, const SpmvPlan& pl, cons
                 k_wb_h<<<std::min(kMaxGrid, (W.s + 3) / 4), kBlock, 0, stream>>>(W);
                 k_wb_w<<<(int)std::min<size_t>(kMaxGrid, W.cap / kWbwRows), kWbwThreads, 0, stream>>>(L, W);
             }
+            if (nq > 0) lobq_project(L, nq);
             launch_spmv(pl, stream, AT, L.wT, op);
             k_lob_update<<<L.P_a, kBlock, 0, stream>>>(L, s);
         }
         k_lob_tail<<<1, 64, 0, stream>>>(L, steps);
         return;
     }
-    with_lob_chunk(L.c, [&](auto C) { lob_launch_chunk_t<SV(C)>(AT, pl, L, steps); });
+    with_lob_chunk(L.c, [&](auto C) { lob_launch_chunk_t<SV(C)>(AT, pl, L, steps, nq); });
 }
-inline int Solver::lob_enqueue_chunk(const CsrView& A, const CsrView& AT, const SpmvPlan& pl, const LobView& L, int steps) {
-    if (!use_graph() || wb_active.s > 0) { lob_launch_chunk(AT, pl, L, steps); return MACHIP_OK; }   // (closure count is baked into the launches)
+inline int Solver::lob_enqueue_chunk(const CsrView& A, const CsrView& AT, const SpmvPlan& pl, const LobView& L, int steps, int nq) {
+    // (closure count and locked-column count are baked into the launches: the cached chunk graphs stay column 0's)
+    if (!use_graph() || wb_active.s > 0 || nq > 0) { lob_launch_chunk(AT, pl, L, steps, nq); return MACHIP_OK; }
     const GraphKey key = std::make_tuple(1000 + pl.variant, pl.width, pl.grid, L.c + (n > kTriMaxN ? 100 : 0), steps);
-    return replay_chunk(A, key, [&] { lob_launch_chunk(AT, pl, L, steps); });
+    return replay_chunk(A, key, [&] { lob_launch_chunk(AT, pl, L, steps, 0); });
 }
 inline int Solver::wb_alloc() {
     // sized for the closures this solve actually has (+25 %, whole 256s), not for the tier's limit: 16 384 would mean
@@ -191,22 +195,22 @@ inline int Solver::wb_extract(const CsrView& A, int hc[2]) {
     return MACHIP_OK;
 }
 
-// Returns MACHIP_OK (converged: yvec, *lam, *res set), MACHIP_NOT_CONVERGED (caller falls back to
-// Lanczos) or an error.
-inline int Solver::solve_lob(const CsrView& A, long nnz, double lnorm, double tol, int max_steps, int start_mode,
-                             double* lam, double* res, long* iters, long* spmvs, long* restarts_out) {
+// The preconditioner of one matrix: T factored on the device (the chain alone under the exact preconditioner), the product's
+// gather indices in the solver's layout, the closures' capacitance matrix inverted -- wb_active.s > 0 then.  MACHIP_NOT_CONVERGED: the
+// capacitance matrix is not positive definite numerically.  lx_bad (T not positive definite) is read by the caller, behind its first wait.
+inline int Solver::lob_prepare(const CsrView& A, long nnz, double lnorm, LobPrep* P) {
     ST_TRY(lob_alloc(nnz));
-    SpmvPlan pl = plan_spmv(opt, n, nnz, kAuto);
-    LobView L = lview(pl);
+    P->pl = plan_spmv(opt, n, nnz, kAuto);
+    P->L = lview(P->pl);
+    const LobView& L = P->L;
     const int g2 = vgrid();
-    const bool debug = OPT(debug, 0) != 0;
     const double scale = lnorm > 0 ? lnorm : 1.0;
     // ---- exact preconditioner (woodbury.h) when the graph is chain + at most kWbMaxS closures ----
     wb_active.s = 0;
     int wb_s = 0;
     lob_escalate = false;
     const bool wb_enabled = OPT(woodbury, 1) != 0 && chain_like && support_hint >= 0;
-    const bool may_escalate = wb_enabled && support_hint > wb_limit_now && support_hint <= wb_hard();
+    P->may_escalate = wb_enabled && support_hint > wb_limit_now && support_hint <= wb_hard();
     if (wb_enabled && support_hint <= wb_limit_now) {
         ST_TRY(wb_alloc());
         int hc[2] = {0, 0};
@@ -234,14 +238,27 @@ inline int Solver::solve_lob(const CsrView& A, long nnz, double lnorm, double to
         k_tri_band<<<g2, kBlock, 0, stream>>>(A, L.c, L.stride, lx_ba, lx_bd, lx_bu);
         with_lob_chunk(L.c, [&](auto C) { k_tri_factor<SV(C)><<<1, kTriThreads, 0, stream>>>(n, lx_ba, lx_bd, lx_bu, sigma, lx_tl, lx_tdinv, lx_tcu, lx_bad, chain_only); });
     }
-    CsrView AT = A;
+    P->AT = A;
     k_lob_perm_cols<<<(int)std::min<long>(kMaxGrid, (nnz + kBlock - 1) / kBlock), kBlock, 0, stream>>>(A.col, nnz, L.c, L.stride, lx_colT);
-    AT.col = lx_colT;
+    P->AT.col = lx_colT;
     if (wb_s > 0) {
         const int st = wb_build(L, wb_s);
         if (st != MACHIP_OK && st != MACHIP_NOT_CONVERGED) return st;
         if (st == MACHIP_NOT_CONVERGED) return MACHIP_NOT_CONVERGED;   // capacitance not SPD numerically: Lanczos takes over
     }
+    return MACHIP_OK;
+}
+
+// Returns MACHIP_OK (converged: yvec, *lam, *res set), MACHIP_NOT_CONVERGED (caller falls back to
+// Lanczos) or an error.
+inline int Solver::solve_lob(const CsrView& A, long nnz, double lnorm, double tol, int max_steps, int start_mode,
+                             double* lam, double* res, long* iters, long* spmvs, long* restarts_out) {
+    LobPrep P;
+    const int st_prep = lob_prepare(A, nnz, lnorm, &P);
+    if (st_prep != MACHIP_OK) return st_prep;
+    const SpmvPlan& pl = P.pl;
+    const int g2 = vgrid();
+    const double scale = lnorm > 0 ? lnorm : 1.0;
     // ---- start vector: normalised into yvec, w2 = L yvec, Rayleigh quotient ----
     const double* src = (start_mode == 1 && have_prev) ? yvec : (have_start ? start : nullptr);
     if (!src) { k_fill_start<<<g2, kBlock, 0, stream>>>(u, n, 0x1234567ull); src = u; }
@@ -256,6 +273,23 @@ inline int Solver::solve_lob(const CsrView& A, long nnz, double lnorm, double to
     if (hbad || !(rq == rq)) return MACHIP_NOT_CONVERGED;
     *lam = rq; *res = r1 / scale;
     if (*res < tol) return MACHIP_OK;
+    return lob_iterate(A, P, lnorm, tol, max_steps, 0, r1, lam, res, iters, spmvs, restarts_out);
+}
+
+// The host loop of the preconditioned modes from a start vector that has been checked (unit norm in yvec, w2 = L yvec, its Rayleigh
+// quotient in rq_dev, its residual's 1-norm r1): chunks of iterations watched through the records, the explicit check, restarts.
+// nq > 0: a deflated column of machip_lowest_pairs (solver_pairs_lob.h) -- w = M^-1 r is projected against the first nq columns of
+// pairs->Q in every iteration, x twice before every explicit check.  nq = 0 is the Fiedler solve.  Statuses as solve_lob's.
+inline int Solver::lob_iterate(const CsrView& A, const LobPrep& P, double lnorm, double tol, int max_steps, int nq, double r1,
+                               double* lam, double* res, long* iters, long* spmvs, long* restarts_out) {
+    const SpmvPlan& pl = P.pl;
+    const LobView& L = P.L;
+    const CsrView& AT = P.AT;
+    const bool may_escalate = P.may_escalate;
+    const int g2 = vgrid();
+    const bool debug = OPT(debug, 0) != 0;
+    const double scale = lnorm > 0 ? lnorm : 1.0;
+    double rq = 0.0;
     const int cap = std::min(kLobCap, max_steps > 0 ? max_steps : kLobCap);
     const int patience = std::max(64, OPT(lob_patience, 10000));   // iterations without a new best residual
     // (exact preconditioner: a handful of iterations in all, each six launches -- short chunks, no speculation)
@@ -281,7 +315,7 @@ inline int Solver::solve_lob(const CsrView& A, long nnz, double lnorm, double to
                 ramp = std::min(chunk0, ramp * 2);
                 if (near) chunk = std::min(chunk, std::max(2, (int)(0.75 * to_go) + 1));
                 chunk = std::min(chunk, cap - it_enq);
-                ST_TRY(lob_enqueue_chunk(A, AT, pl, L, chunk));
+                ST_TRY(lob_enqueue_chunk(A, AT, pl, L, chunk, nq));
                 it_enq += chunk;
                 *spmvs += chunk;
                 pend.push_back(it_enq);
@@ -318,13 +352,14 @@ inline int Solver::solve_lob(const CsrView& A, long nnz, double lnorm, double to
         // ---- explicit check of the current x (fresh SpMV), also the refresh point of a restart ----
         HIP_TRY(hipStreamSynchronize(stream));
         HIP_TRY(hipMemcpyAsync(y_raw, lx_x, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, stream));
+        if (nq > 0) { pairs_project(y_raw, nq, 2); pairs_project(y_raw, nq, 2); }
         k_vec_sums<<<g2, kBlock, 0, stream>>>(y_raw, n, part_c);
         ST_TRY(check_vector(A, pl, &rq, &r1));
         *spmvs += 1;
         *iters = it_enq;
         *restarts_out = restarts;
         if (debug) fprintf(stderr, "[machip]    lobpcg check it=%d rq=%.15g res=%.3e (tol %.1e)\n", it_enq, rq, r1 / scale, tol);
-        if (!(rq == rq)) return MACHIP_NOT_CONVERGED;
+        if (!(rq == rq)) { *lam = rq; return MACHIP_NOT_CONVERGED; }      // (yvec is no vector any more: the caller must not start from it)
         *lam = rq; *res = r1 / scale;
         if (*res < tol) return MACHIP_OK;
         if (it_enq >= cap || ++restarts > 12 || it_enq - best_it > patience) return MACHIP_NOT_CONVERGED;

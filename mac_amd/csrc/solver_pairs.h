@@ -25,7 +25,9 @@ namespace machip {
 constexpr int kPairsMaxLock = 16;                       // the constant vector + at most 15 accepted columns are projected out
 constexpr int kPairsPM = 1 + 2 * kPairsMaxLock;         // k_pairs_mul's sums per workgroup: t.v | q_i.t | q_i.v
 constexpr int kPairsChunk = 16;                         // steps between two looks at the records
-constexpr int kPairsGrid = 256;                         // most workgroups of the vector kernels (every consumer re-reads one partial each)
+constexpr int kPairsModeLanczos = 1;                    // machip_lowest_pairs_info: a column of the deflated Lanczos below
+constexpr int kPairsModeFinished = 9;                   // ... of preconditioned iterations (solver_pairs_lob.h) finished by it
+constexpr int kPairsGrid = 256;                        // most workgroups of the vector kernels (every consumer re-reads one partial each)
 
 struct PairsBuf {
     double *Q = nullptr;       // n x 17: the constant vector, then the accepted columns in the order they were found
@@ -38,9 +40,19 @@ struct PairsBuf {
     size_t rec_cap = 0;
     double last_ms[kPairsMaxLock] = {};      // device time per column of the last call, by rank (machip_lowest_pairs_time)
     int last_q = 0;
+    // the preconditioned route (solver_pairs_lob.h; option pairs_precond)
+    double *QT = nullptr;      // the locked columns in the tridiagonal solver's chunk-transposed layout, 16 x (c x stride)
+    double *qpart = nullptr;   // kPairsGrid x 16: k_lobq_dots partials
+    int qt_cols = 0;           // columns of QT that hold this call's locked block
+    bool lob_off = false;      // this call has no preconditioner (not positive definite numerically): its columns run Lanczos
+    int last_method[kPairsMaxLock] = {};     // by rank: the mode that produced each column of the last call (machip_lowest_pairs_info)
+    int last_closures = 0;                   // closures of the exact preconditioner the deflated columns ran with (0: none did)
+    double build_ms = 0.0;                   // device time of the one-off preconditioner build (0: column 0's was reused, or none)
 };
 
-struct PairsCol { double lam = NAN, res = INFINITY, ms = 0.0; int steps = 0, restarts = 0, status = MACHIP_NOT_CONVERGED; };
+// method: the solver mode that produced the column (solver.h last_mode; 1 deflated Lanczos, 6 / 7 preconditioned, 9 preconditioned
+// iterations finished by Lanczos)
+struct PairsCol { double lam = NAN, res = INFINITY, ms = 0.0; int steps = 0, restarts = 0, status = MACHIP_NOT_CONVERGED, method = 1; };
 
 // every lane of the calling wave gets the sum of cnt partials, added in one fixed order
 __device__ __forceinline__ double pairs_wave_partials(const double* part, int cnt, int stride = 1) {
@@ -244,7 +256,7 @@ __global__ __launch_bounds__(kBlock) void k_pairs_fill(double* __restrict__ x, i
 
 inline void Solver::pairs_free() {
     if (!pairs) return;
-    void* b[] = {pairs->Q, pairs->t, pairs->xs, pairs->pm, pairs->pf, pairs->gq, pairs->rec};
+    void* b[] = {pairs->Q, pairs->t, pairs->xs, pairs->pm, pairs->pf, pairs->gq, pairs->rec, pairs->QT, pairs->qpart};
     for (void* q : b) if (q) (void)hipFree(q);
     delete pairs;
     pairs = nullptr;
@@ -375,16 +387,49 @@ inline int Solver::pairs_rest(const CsrView& A, long nnz, double lnorm, double t
     if (OPT(pairs_vcap, 0) > 0) cap = std::min(cap, OPT(pairs_vcap, 0));
     cap = std::max(cap, 4);
     const int steps_cap = max_steps > 0 ? max_steps : (int)std::min<long>(200000, std::max<long>(2000, 20l * n));
+    // option pairs_precond: the columns run the preconditioned iteration of solver_pairs_lob.h where the handle is eligible; what that
+    // touches of the handle beyond yvec and last_pr is put back as well
+    const bool precond = OPT(pairs_precond, 0) != 0 && pairs_lob_eligible();
+    const long keep_lob = hist_lob_iters, keep_exact = hist_exact_iters;
+    const bool keep_prev = have_prev, keep_esc = lob_escalate;
+    const int keep_limit = wb_limit_now;
+    const WbView keep_wb = wb_active;
+    LobPrep P;
+    bool prepared = false;
+    B.qt_cols = 0; B.lob_off = false; B.last_closures = 0; B.build_ms = 0.0;
     int st = MACHIP_OK;
     for (int c = 1; c < q && st == MACHIP_OK; ++c) {
+        if (precond && !prepared && !B.lob_off) {      // once per call, before column 1
+            const bool reuse = last_was_lob && (last_mode == 6 || last_mode == 7);
+            if (!reuse) wb_limit_now = wb_soft();
+            const int sp = pairs_lob_prepare(A, nnz, lnorm, &P, reuse, true);
+            if (sp == MACHIP_OK) prepared = true;
+            else if (sp == MACHIP_NOT_CONVERGED) B.lob_off = true;
+            else { st = sp; break; }
+        }
         (void)hipEventRecord(evs0, stream);
-        st = pairs_column(A, nnz, lnorm, tol, steps_cap, c, cap, &cols[c]);
+        if (precond && prepared && !B.lob_off) {
+            st = pairs_column_lob(A, nnz, lnorm, tol, steps_cap, c, &P, &cols[c]);
+            if (st == MACHIP_OK && cols[c].method == 7) B.last_closures = wb_active.s;
+            if (st == MACHIP_OK && cols[c].status != MACHIP_OK) {
+                // no check passed (breakdown, the iteration cap, patience): the deflated Lanczos finishes the column from the last
+                // checked vector, as solve() finishes column 0; its steps are added to the column's count
+                const PairsCol lob = cols[c];
+                if (std::isfinite(lob.lam) && hipMemcpyAsync(B.xs + (size_t)c * n, yvec, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, stream) != hipSuccess)
+                    st = fail(MACHIP_HIP_ERROR, "machip_lowest_pairs: copy of a checked vector failed");
+                if (st == MACHIP_OK) st = pairs_column(A, nnz, lnorm, tol, std::max(0, steps_cap - lob.steps), c, cap, &cols[c]);
+                if (cols[c].steps == 0 && std::isfinite(lob.lam)) { cols[c].lam = lob.lam; cols[c].res = lob.res; }      // (the cap left Lanczos no step: the last check's figures)
+                cols[c].steps += lob.steps; cols[c].restarts += lob.restarts;
+                cols[c].method = lob.steps > 0 ? kPairsModeFinished : kPairsModeLanczos;
+            }
+        } else st = pairs_column(A, nnz, lnorm, tol, steps_cap, c, cap, &cols[c]);
         float ms = 0.f;      // the column on the stream's clock: steps, the host's looks at the records between chunks, Ritz vectors and checks
         if (st == MACHIP_OK && hipEventRecord(evs1, stream) == hipSuccess && hipEventSynchronize(evs1) == hipSuccess &&
             hipEventElapsedTime(&ms, evs0, evs1) == hipSuccess) cols[c].ms = ms;
         if (st == MACHIP_OK) st = hipMemcpyAsync(B.Q + (size_t)(c + 1) * n, yvec, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, stream) == hipSuccess
                                       ? MACHIP_OK : fail(MACHIP_HIP_ERROR, "machip_lowest_pairs: copy of an accepted column failed");
     }
+    hist_lob_iters = keep_lob; hist_exact_iters = keep_exact; have_prev = keep_prev; lob_escalate = keep_esc; wb_limit_now = keep_limit; wb_active = keep_wb;
     keep_hook.swap(after_check);
     last_pr = keep_pr;
     const std::string keep = g_err;

@@ -118,18 +118,19 @@ class MAC:
             cache.Q = v.reshape(-1, 1)
         return f, gradf
 
-    def lowest_pairs(self, x, q=4, X=None, raise_on_cap=False):
+    def lowest_pairs(self, x, q=4, X=None, raise_on_cap=False, method="lanczos"):
         """``find_lowest_pairs`` for L(x) assembled on the device: the q lowest non-trivial eigenpairs, every one converged
         to ``fiedler_tol`` -> ``(lams, V, info)`` (mac_amd/utils/fiedler.py).  X: n x q start block (default: the stored start
-        vector and the reference's block)."""
+        vector and the reference's block).  method: "lanczos" or "lobpcg", as ``find_lowest_pairs`` takes it."""
         self._dev.set_x(np.asarray(x, dtype=np.float64))
-        return self._dev.lowest_pairs(q=q, tol=self.fiedler_tol, max_steps=self.max_lanczos_steps, X0=X, raise_on_cap=raise_on_cap)
+        return self._dev.lowest_pairs(q=q, tol=self.fiedler_tol, max_steps=self.max_lanczos_steps, X0=X, raise_on_cap=raise_on_cap,
+                                      method=method)
 
-    def problem_block(self, x, q=4):
+    def problem_block(self, x, q=4, method="lanczos"):
         """``(lams, G, V)``: the q lowest eigenpairs of L(x) and, per column, the supergradient ``problem`` computes from the
         Fiedler vector (G is m x q; k_grad on column c, bit-exact given V[:, c]).  Where lambda_2 is multiple or nearly so, the
         supergradients of the cluster's columns span what a single vector picks one member of."""
-        lams, V, _ = self.lowest_pairs(x, q, raise_on_cap=True)
+        lams, V, _ = self.lowest_pairs(x, q, raise_on_cap=True, method=method)
         return lams, self._dev.gradient_block(V), V
 
     def solve_sweep(self, ks, x_inits, rounding="nearest", max_iters=5, relative_duality_gap_tol=1e-4, grad_norm_tol=1e-8,

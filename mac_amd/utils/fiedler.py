@@ -82,7 +82,7 @@ def reference_start_block_q(n, q, seed=None):
     return np.asarray(seed.normal(size=(q, n))).T
 
 
-def find_lowest_pairs(L, q=4, X=None, tol=1e-8, seed=None, max_steps=0, raise_on_cap=False):
+def find_lowest_pairs(L, q=4, X=None, tol=1e-8, seed=None, max_steps=0, raise_on_cap=False, method="lanczos"):
     """The ``q`` lowest non-trivial eigenpairs of the graph Laplacian ``L`` (any scipy sparse matrix), 1 <= q <= min(16, n-1),
     EVERY ONE converged to the reference's stop rule ||L v - lambda v||_1 / ||L||_inf < tol (machip_lowest_pairs_csr,
     DESIGN section 24).  Returns ``(lams, V, info)``: ``lams`` ascending, ``V`` n x q with orthonormal columns orthogonal to 1.
@@ -95,11 +95,18 @@ def find_lowest_pairs(L, q=4, X=None, tol=1e-8, seed=None, max_steps=0, raise_on
     ``info``: ``residual`` (measured, per column), ``steps``, ``restarts``, ``status`` (0 = converged, 1 = the column hit
     ``max_steps``: never passed off as converged; raised as ``NotConverged`` only with ``raise_on_cap=True``), ``reordered``
     / ``first_rank`` (1 / the number of columns below column 0's value by more than tol ||L||_inf, if the Fiedler solve had
-    returned a higher eigenpair than one found after it), ``gap`` = lams[1] - lams[0] for q >= 2.  Not proven: that nothing lies below lams[0]."""
+    returned a higher eigenpair than one found after it), ``gap`` = lams[1] - lams[0] for q >= 2.  Not proven: that nothing lies below lams[0].
+
+    ``method="lobpcg"``: on a chain-like graph (a pose graph) the columns after the first run a LOBPCG in the
+    complement of the columns found so far, preconditioned by the chain (+ closures) as the Fiedler solve's modes 6 / 7 are;
+    ``info["steps"]`` then counts iterations.  On any other graph the columns run Lanczos all the same: ``info["method"]`` says, per
+    column, which mode produced it (column 0: the Fiedler solve's; 1 deflated Lanczos; 6 / 7 preconditioned by the tridiagonal chain /
+    exactly; 9 preconditioned iterations finished by Lanczos), ``info["closures"]`` the closures of the exact preconditioner (or 0),
+    ``info["build_ms"]`` the device time of its one-off build."""
     L = csr_matrix(L, dtype=np.float64)
     n = L.shape[0]
     if X is None:
         X = reference_start_block_q(n, q, seed)
     assert X.shape == (n, q)
     L.sum_duplicates()
-    return _lib.lowest_pairs_csr(L.indptr, L.indices, L.data, n, q=q, tol=tol, max_steps=max_steps, X0=X, raise_on_cap=raise_on_cap)
+    return _lib.lowest_pairs_csr(L.indptr, L.indices, L.data, n, q=q, tol=tol, max_steps=max_steps, X0=X, raise_on_cap=raise_on_cap, method=method)
