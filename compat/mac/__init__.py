@@ -19,6 +19,8 @@ reference's own ``from mac.solvers.greedy_eig import GreedyEig`` (``mac_amd/solv
 ESPRelaxation (no counterpart in the reference: the convex relaxation GreedyESP's paper pairs the greedy with) is
 ``from mac.solvers import ESPRelaxation`` (``mac_amd/solvers/esp_relax.py``); ``ESPRelaxation(..., edge_space=True)`` is its
 candidate-space form for chain-fixed graphs of any length.
+GreedyKirchhoff (no counterpart in the reference either: the greedy under the A-optimal criterion, tr L^+) is
+``from mac.solvers import GreedyKirchhoff`` (``mac_amd/solvers/kirchhoff.py``).
 ``mac.utils.cholesky`` (the reference's CHOLMOD wrapper) is not provided: importing it raises ImportError, as it does in the
 reference without its optional SuiteSparse dependency.
 """
@@ -31,6 +33,7 @@ _ALIASES = {
     "mac.solvers.baseline": "mac_amd.solvers.baseline",
     "mac.solvers.greedy_eig": "mac_amd.solvers.greedy_eig",
     "mac.solvers.esp_relax": "mac_amd.solvers.esp_relax",
+    "mac.solvers.kirchhoff": "mac_amd.solvers.kirchhoff",
     "mac.utils": "mac_amd.utils",
     "mac.utils.graphs": "mac_amd.utils.graphs",
     "mac.utils.fiedler": "mac_amd.utils.fiedler",

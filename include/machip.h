@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define MACHIP_ABI_VERSION 20   /* 20: option pairs_precond (preconditioned deflated columns of machip_lowest_pairs), machip_lowest_pairs_info, machip_lowest_pairs_csr2; 19: machip_lowest_pairs, machip_lowest_pairs_csr (the q lowest non-trivial eigenpairs, every one converged to the stop rule; option pairs_vcap), machip_lowest_pairs_time, machip_gradient_block; 18: machip_eig_exchange_free (the exchange on lambda_2 on MACHIP_EIG_MATRIX_FREE / _TREE handles; option eig_xch_free_swaps), machip_eig_history; 17: MACHIP_EIG_MATRIX_FREE_TREE (GreedyEig on any connected fixed graph without a dense Sigma; machip_eig_seeds); 16: MACHIP_EIG_MATRIX_FREE (GreedyEig on a chain without a dense Sigma; options eig_free_rows, eig_free_split); 15: machip_eig_exchange (best-swap local search on lambda_2; option eig_xch_max_mb); 14: machip_esp_exchange_edge (the exchange in the candidates' space on MACHIP_ESP_EDGE_RELAX / MACHIP_ESP_EDGE_RELAX_TREE handles); 13: machip_esp_exchange (best-swap local search on the log tree count; options esp_xch_lds_kb, esp_xch_max_mb, esp_xch_profile); 12: MACHIP_ESP_EDGE_RELAX (the relaxation in the candidates' space on a chain-fixed graph; machip_esp_relax_info); 11: MACHIP_ESP_SPANNING_TREE (the matrix-free route of GreedyESP for any connected fixed graph; machip_esp_tree_plan, machip_esp_seeds); 10: MACHIP_ESP_MATRIX_FREE (GreedyESP on a chain without a dense Sigma, option esp_free_split); 9: the relaxation of GreedyESP's problem (machip_esp_relax_*); 8: GreedyEig handle (machip_eig_*); 7: GreedyESP handle (machip_esp_*); 6: machip_solve_stats.drift, machip_panel_plan fills 12 entries; 5: per-handle option table (machip_set_option), machip_comm_drop_ipc; 4: inter-process communicator */
+#define MACHIP_ABI_VERSION 21   /* 21: GreedyKirchhoff on the dense machip_esp handle (machip_esp_kirchhoff_select, _gains, _eval: greedy A-optimal selection and the total effective resistance of any selection); 20: option pairs_precond (preconditioned deflated columns of machip_lowest_pairs), machip_lowest_pairs_info, machip_lowest_pairs_csr2; 19: machip_lowest_pairs, machip_lowest_pairs_csr (the q lowest non-trivial eigenpairs, every one converged to the stop rule; option pairs_vcap), machip_lowest_pairs_time, machip_gradient_block; 18: machip_eig_exchange_free (the exchange on lambda_2 on MACHIP_EIG_MATRIX_FREE / _TREE handles; option eig_xch_free_swaps), machip_eig_history; 17: MACHIP_EIG_MATRIX_FREE_TREE (GreedyEig on any connected fixed graph without a dense Sigma; machip_eig_seeds); 16: MACHIP_EIG_MATRIX_FREE (GreedyEig on a chain without a dense Sigma; options eig_free_rows, eig_free_split); 15: machip_eig_exchange (best-swap local search on lambda_2; option eig_xch_max_mb); 14: machip_esp_exchange_edge (the exchange in the candidates' space on MACHIP_ESP_EDGE_RELAX / MACHIP_ESP_EDGE_RELAX_TREE handles); 13: machip_esp_exchange (best-swap local search on the log tree count; options esp_xch_lds_kb, esp_xch_max_mb, esp_xch_profile); 12: MACHIP_ESP_EDGE_RELAX (the relaxation in the candidates' space on a chain-fixed graph; machip_esp_relax_info); 11: MACHIP_ESP_SPANNING_TREE (the matrix-free route of GreedyESP for any connected fixed graph; machip_esp_tree_plan, machip_esp_seeds); 10: MACHIP_ESP_MATRIX_FREE (GreedyESP on a chain without a dense Sigma, option esp_free_split); 9: the relaxation of GreedyESP's problem (machip_esp_relax_*); 8: GreedyEig handle (machip_eig_*); 7: GreedyESP handle (machip_esp_*); 6: machip_solve_stats.drift, machip_panel_plan fills 12 entries; 5: per-handle option table (machip_set_option), machip_comm_drop_ipc; 4: inter-process communicator */
 
 typedef enum machip_status {
     MACHIP_OK = 0,
@@ -475,6 +475,24 @@ int machip_esp_tree_plan(int64_t n, int64_t n_fixed, const int32_t* fi, const in
                          double* R, int32_t* pre, int32_t* end, int64_t* n_seeds, int32_t* su, int32_t* sv, double* sw);
 /* *seeds_out = the seeds of a MACHIP_ESP_SPANNING_TREE handle (distinct fixed links - (n - 1)); 0 on every other handle. */
 int machip_esp_seeds(machip_esp* h, int64_t* seeds_out);
+
+/* GreedyKirchhoff: greedy A-optimal selection on the same handle (mac_amd/csrc/kirchhoff.h).  The criterion is tr L^+ of the whole
+ * graph's Laplacian (the total effective resistance; Kirchhoff index / n) = tr Sigma - (1^T Sigma 1) / n; adding candidate e lowers it
+ * by gain_e = w_e (|z_e|^2 - (1^T z_e)^2 / n) / (1 + s_e), z_e = Sigma a_e padded with 0 for node 0, s_e its weighted resistance.
+ * All three work on the dense forms only (info4[0] = 0 or 1) and refuse, before any device work, with MACHIP_BAD_ARG a handle made
+ * with MACHIP_ESP_MATRIX_FREE (alone or with MACHIP_ESP_SPANNING_TREE / MACHIP_ESP_EDGE_RELAX*: the criterion needs Sigma) and with
+ * MACHIP_DISCONNECTED a handle whose beta != 0 (a disconnected fixed graph has an infinite index).
+ * One greedy run from Sigma0 up to K = ks[nb-1] picks, arguments as machip_esp_select (every output required): each step takes
+ * the unselected candidate of largest gain (ties: lowest index); gain_out[k] = the pick's gain, so that the sum of the gains is
+ * tr L^+ before the run minus tr L^+ after it.  Per pick the run streams Sigma once (8 ld^2 bytes).  Results repeat bit for bit. */
+int machip_esp_kirchhoff_select(machip_esp* h, int nb, const int64_t* ks, int32_t* order_out, double* gain_out, double* t_ms_out);
+/* gain_e of every candidate (m doubles; selected ones included) re-scored exactly from Sigma of the current graph -- F plus the
+ * last run's selections, whose pending updates are folded first; F alone on a fresh handle. */
+int machip_esp_kirchhoff_gains(machip_esp* h, double* gains_out);
+/* Scores a selection of any origin: restarts from Sigma0, applies the nsel candidates idx[] (distinct, in [0, m); nsel = 0: none)
+ * as forced picks in the given order, folds, and returns out2 = {tr L^+ of the fixed graph, tr L^+ with the selection}, both by a
+ * two-stage reduction over Sigma (not from summed gains).  Afterwards the handle's current graph is F plus the selection. */
+int machip_esp_kirchhoff_eval(machip_esp* h, int64_t nsel, const int32_t* idx, double* out2);
 
 /* The convex relaxation of GreedyESP's problem on the same handle (mac_amd/csrc/esp_relax.h).  For x in [0, 1]^m:
  *     M(x) = L_red + beta I + sum_e x_e w_e a_e a_e^T,   F(x) = log det M(x) - log det M(0)   (nats; F(0) = 0 exactly; for a 0/1 x

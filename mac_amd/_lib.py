@@ -122,6 +122,9 @@ SIGNATURES = {
     "machip_esp_tree_plan": (C.c_int, [C.c_int64, C.c_int64, _i32p, _i32p, _f64p, _i32p, _f64p, _i32p, _i32p, C.POINTER(C.c_int64),
                                        _i32p, _i32p, _f64p]),
     "machip_esp_seeds": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
+    "machip_esp_kirchhoff_select": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int64), _i32p, _f64p, _f64p]),
+    "machip_esp_kirchhoff_gains": (C.c_int, [C.c_void_p, _f64p]),
+    "machip_esp_kirchhoff_eval": (C.c_int, [C.c_void_p, C.c_int64, _i32p, _f64p]),
     "machip_esp_relax_eval": (C.c_int, [C.c_void_p, _f64p, C.POINTER(C.c_double), _f64p]),
     "machip_esp_relax_run": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_double, C.c_double, _f64p, _f64p, _f64p, _f64p,
                                        C.POINTER(C.c_int), C.POINTER(C.c_double)]),
@@ -617,6 +620,32 @@ class Esp:
         r = np.empty(max(self.m, 1))
         check(self._lib.machip_esp_weighted_resistances(self._h, p_f64(r)))
         return r[:self.m]
+
+    def kirchhoff_select(self, ks):
+        """One greedy A-optimal run up to ks[-1] picks (machip_esp_kirchhoff_select): (order int32[K], gain float64[K] -- each
+        pick's drop of tr L^+ --, t_ms float64[len(ks)]).  Dense handles with a connected fixed graph only."""
+        ks = np.ascontiguousarray(ks, dtype=np.int64)
+        K = int(ks[-1]) if len(ks) else 0
+        order = np.empty(max(K, 1), dtype=np.int32)
+        gain = np.empty(max(K, 1))
+        t = np.empty(max(len(ks), 1))
+        check(self._lib.machip_esp_kirchhoff_select(self._h, len(ks), ks.ctypes.data_as(C.POINTER(C.c_int64)), p_i32(order),
+                                                    p_f64(gain), p_f64(t)))
+        return order[:K], gain[:K], t[:len(ks)]
+
+    def kirchhoff_gains(self):
+        """The drop of tr L^+ every candidate would bring to F plus the last run's selections, re-scored exactly from Sigma
+        (machip_esp_kirchhoff_gains)."""
+        g = np.empty(max(self.m, 1))
+        check(self._lib.machip_esp_kirchhoff_gains(self._h, p_f64(g)))
+        return g[:self.m]
+
+    def kirchhoff_eval(self, idx):
+        """(tr L^+ of the fixed graph, tr L^+ with the candidates ``idx`` added) (machip_esp_kirchhoff_eval)."""
+        idx = i32(idx)
+        out = np.empty(2)
+        check(self._lib.machip_esp_kirchhoff_eval(self._h, len(idx), p_i32(idx), p_f64(out)))
+        return float(out[0]), float(out[1])
 
     def info(self):
         """dict(form = "chain" | "dense" | "chain_free" | "tree_free", ld, fold, pending, beta, seeds)."""

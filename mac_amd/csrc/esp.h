@@ -245,6 +245,7 @@ struct EspRelax;      // esp_relax.h: the state of the convex relaxation, made b
 struct EspTreeState;  // esp_tree.h: the spanning tree's tables and the seeds of a MACHIP_ESP_SPANNING_TREE handle
 struct EspXch;        // esp_exchange.h: the rows of Sigma the exchange keeps, made by the first exchange call
 struct EspXchEdge;    // esp_exchange_edge.h: the view and the rows of the edge-space exchange, made by its first call
+struct EspKir;        // kirchhoff.h: the arrays of the A-optimal greedy, made by the first Kirchhoff call
 
 }  // namespace machip
 
@@ -274,6 +275,7 @@ struct machip_esp {
     machip::EspTreeState* tr = nullptr;
     machip::EspXch* xc = nullptr;
     machip::EspXchEdge* xe = nullptr;
+    machip::EspKir* kr = nullptr;
 
     machip::EspView view() const {
         machip::EspView V;

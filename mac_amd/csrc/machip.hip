@@ -7,6 +7,7 @@
 #include "esp_free.h"
 #include "esp_tree.h"
 #include "esp_select.h"
+#include "kirchhoff.h"
 #include "esp_relax.h"
 #include "esp_exchange.h"
 #include "esp_exchange_edge.h"
@@ -544,6 +545,7 @@ void machip_esp_destroy(machip_esp* h) {
     esp_tree_release(h);
     esp_xch_release(h->xc);
     esp_xe_release(h->xe);
+    esp_kir_release(h);
     void* bufs[] = {h->bufA, h->bufB, h->cu, h->cv, h->sel, h->pi, h->order, h->bad, h->cw, h->s, h->Zb, h->cb, h->pv, h->gain, h->piv, h->best, h->R, h->part};
     for (void* q : bufs) if (q) (void)hipFree(q);
     if (h->stream) (void)hipStreamDestroy(h->stream);
@@ -592,6 +594,34 @@ int machip_esp_weighted_resistances(machip_esp* h, double* r_out) {
     if (!h || (!r_out && h->m)) return fail(MACHIP_BAD_ARG, "NULL handle or output");
     HIP_TRY(hipSetDevice(h->device));
     return esp_resistances(h, r_out);
+}
+
+// ---- GreedyKirchhoff on GreedyESP's dense handle (kirchhoff.h) ----
+
+int machip_esp_kirchhoff_select(machip_esp* h, int nb, const int64_t* ks, int32_t* order_out, double* gain_out, double* t_ms_out) {
+    if (!h || nb < 1 || !ks) return fail(MACHIP_BAD_ARG, "NULL handle, no budgets or ks is NULL");
+    if (!order_out || !gain_out || !t_ms_out) return fail(MACHIP_BAD_ARG, "NULL output");
+    if (ks[0] <= 0) return fail(MACHIP_BAD_ARG, "budgets must be positive");
+    for (int i = 0; i + 1 < nb; ++i) if (ks[i] > ks[i + 1]) return fail(MACHIP_BAD_ARG, "budgets must be monotonically increasing");
+    if (ks[nb - 1] > h->m) return fail(MACHIP_BAD_ARG, "not enough candidate edges to satisfy the largest budget");
+    ST_TRY(kir_check(h));
+    HIP_TRY(hipSetDevice(h->device));
+    return kir_select(h, nb, ks, order_out, gain_out, t_ms_out);
+}
+
+int machip_esp_kirchhoff_gains(machip_esp* h, double* gains_out) {
+    if (!h || (!gains_out && h->m)) return fail(MACHIP_BAD_ARG, "NULL handle or output");
+    ST_TRY(kir_check(h));
+    HIP_TRY(hipSetDevice(h->device));
+    return kir_gains(h, gains_out);
+}
+
+int machip_esp_kirchhoff_eval(machip_esp* h, int64_t nsel, const int32_t* idx, double* out2) {
+    if (!h || !out2) return fail(MACHIP_BAD_ARG, "NULL handle or output");
+    ST_TRY(kir_eval_check(h, nsel, idx));
+    ST_TRY(kir_check(h));
+    HIP_TRY(hipSetDevice(h->device));
+    return kir_eval(h, nsel, idx, out2);
 }
 
 // ---- the exchange on GreedyESP's handle (esp_exchange.h) and in the candidates' space (esp_exchange_edge.h) ----
